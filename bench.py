@@ -9,10 +9,15 @@ One "step" = the whole circuit applied to a fresh |0...0> (init + every fused pa
 gate list is parsed once, before the timed region).  N > 1 shards the SAME 2^n state over N ranks, one process per
 GPU (strong scaling; top log2 N qubits global, exchanged with RCCL send/recv) — gpu_quantum_simulator_amd/distributed.py.
 
+A plain run sets up, plans, warms up, times the steps and prints the line; --dump-outputs DIR also writes a fixed,
+seeded sample of the state the last timed step left (DIR/*.npy, float64).  Every other record (the cold figures,
+full sweeps, the single-qubit probe, fp32, the other sizes, the CPU baseline and the exchange model) needs --full.
+
 Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   roofline     — dominant kernel class: algorithmic bytes / HIP-event time measured live on the engine's own
                  stream during the timed steps, against the 8 TB/s HBM3E peak; `traffic` = PMC bytes per launch
                  from the committed rocprofv3 summary of this same command (`traffic_source` names it);
+With --full, also
   cpu_baseline — the CPU restatement of quantum_simulator.c's loops (oracle/liboracle.so, kind "port",
                  byte-identical to the compiled reference in the container tests) timed on this host,
                  1 thread, on the first gates of the same circuit (bounded to ~12 s); N = 1 only;
@@ -62,7 +67,7 @@ def parse_args(argv=None):
                     help="64 = the headline / parity configuration; 32 = fp32 state like the reference's CUDA variants "
                          "(an extra measurement, single GPU only, reported with dtype f32)")
     ap.add_argument("--sizes", default="24,28,32",
-                    help="other register sizes measured after the headline run and reported under `sizes` ('' = none)")
+                    help="with --full: other register sizes measured after the headline run and reported under `sizes` ('' = none)")
     ap.add_argument("--size-steps", type=int, default=3)
     ap.add_argument("--no-tune", action="store_true",
                     help="skip the geometry planning step (qsim_tune_circuit) and run every pass with its tile bits in ascending order")
@@ -77,7 +82,69 @@ def parse_args(argv=None):
     ap.add_argument("--no-full-sweeps", action="store_true",
                     help="skip the extra steps with QSIM_OPT_SPARSE_START off (profile runs: every launch then is one of the timed kind)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beside the headline: cold figures, full sweeps, single-qubit probe, fp32, --sizes, "
+                         "CPU baseline, exchange model (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of the state the last step left as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: only what the headline needs
+        args.sizes, args.no_cpu_baseline, args.no_precision32, args.no_one_shot, args.no_full_sweeps = "", True, True, True, True
+    return args
+
+
+DUMP_SEED = 20240117
+DUMP_CHUNK_BITS = 12   # the sample is whole runs of 4096 consecutive amplitudes ...
+DUMP_MAX_CHUNKS = 256  # ... at most 256 of them: 2^20 amplitudes, 16 MiB as (re, im) float64 + 8 MiB of indices
+
+
+def dump_indices(n):
+    """The amplitudes --dump-outputs writes, as (first, count) runs: all of them up to 2^20, else 256 runs of 4096 at
+    seeded, sorted offsets.  Depends on n alone, so two builds (or ranks) given the same arguments pick the same ones."""
+    bits = min(DUMP_CHUNK_BITS, n)
+    chunks = 1 << (n - bits)
+    if chunks <= DUMP_MAX_CHUNKS:
+        return [(0, 1 << n)]
+    import numpy as np
+    picked = np.sort(np.random.default_rng(DUMP_SEED + n).choice(chunks, size=DUMP_MAX_CHUNKS, replace=False))
+    return [(int(c) << bits, 1 << bits) for c in picked]
+
+
+def read_sample(sim, n, sharded):
+    """(logical basis indices, amplitudes) of dump_indices(n) from the live state; collective on every rank when sharded
+    (each rank fills in the amplitudes it holds, in physical order on its shard, and the ranks sum the parts)."""
+    import numpy as np
+    runs = dump_indices(n)
+    idx = np.concatenate([np.arange(first, first + count, dtype=np.int64) for first, count in runs])
+    if not sharded:
+        return idx, np.concatenate([sim.read(first, count) for first, count in runs])
+    import torch
+    phys = np.zeros_like(idx)
+    for q, pq in enumerate(sim.plan.final_pos):  # distributed.physical_index, on the whole array
+        phys |= ((idx >> q) & 1) << pq
+    mine = np.nonzero((phys >> sim.m) == sim.rank)[0]
+    sim.shard.sync()
+    dev = sim.shard.state.device
+    part = torch.zeros((idx.size, 2), dtype=torch.float64, device=dev)
+    local = torch.as_tensor(phys[mine] & ((1 << sim.m) - 1), device=dev)
+    part[torch.as_tensor(mine, device=dev)] = sim.shard.state[local]
+    if sim.dist.get_backend() != "nccl":
+        part = part.cpu()
+    sim.dist.all_reduce(part)
+    return idx, part.cpu().numpy().reshape(-1).view(np.complex128)
+
+
+def write_dump(directory, idx, amps, norm2):
+    """DIR/state_sample.npy: (re, im) float64 per sampled amplitude; DIR/state_sample_index.npy: their basis indices
+    (exact in float64); DIR/norm2.npy: <psi|psi> of the whole state."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "state_sample.npy"), np.ascontiguousarray(amps, dtype=np.complex128).view(np.float64).reshape(-1, 2))
+    np.save(os.path.join(directory, "state_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "norm2.npy"), np.array([norm2], dtype=np.float64))
 
 
 KERNEL_SYMBOL = {"tile": "k_tile<12, 512, false, false>", "gate1": "k_gate1_hi<4, false>",
@@ -432,8 +499,10 @@ class Bench:
             self.dist.barrier()
             self.torch.cuda.synchronize()
 
-    def measure(self, n, depth, vocabulary, seed, steps, warmup, fuse, opts, probe_q=None, with_1q_probe=False, precision=None, cold=False):
+    def measure(self, n, depth, vocabulary, seed, steps, warmup, fuse, opts, probe_q=None, with_1q_probe=False, precision=None, cold=False,
+                sample=False):
         """Builds the simulator for one register size, runs `warmup` + `steps` timed steps, returns the numbers.
+        sample: also read the dump_indices(n) amplitudes of the state the last timed step left (before anything else runs).
         cold: before anything is planned, the very first step on the fresh state is timed on its own (empty plan cache,
         no schedule choice, no measured geometries: what a one-shot run pays), then the second one (cached plan)."""
         from gpu_quantum_simulator_amd import Circuit, Simulator, circuits
@@ -513,6 +582,7 @@ class Bench:
             elapsed = float(t.item())
         stats = sim.stats()
         norm2 = sim.norm2()
+        state_sample = read_sample(sim, n, dist is not None) if sample else None
 
         # For the record: the same steps with every pass sweeping the whole register (QSIM_OPT_SPARSE_START = 0).  By default
         # the first passes after a reset only visit the tiles inside the state's support — same
@@ -552,7 +622,7 @@ class Bench:
 
         res = {"workload": workload, "n": n, "gates": gates, "elapsed": elapsed, "steps": steps, "stats": stats,
                "norm2": norm2, "probe": probe, "fuse": fuse, "tuning": tuning, "full_sweeps": full_sweeps, "cold_ms": cold_ms,
-               "precision": precision, "vocabulary": vocabulary}
+               "precision": precision, "vocabulary": vocabulary, "sample": state_sample}
         if dist is not None:
             xs, xb = sim.exchange_seconds / steps, sim.exchange_bytes / steps
             res["exchange"] = {"per_step": sim.plan.exchanges,
@@ -606,7 +676,8 @@ def main():
     default_workload = (args.precision == 64 and args.probe is None and n == 30 and args.depth == 1000 and args.fuse == 3 and args.gpus == 1
                         and not opts and args.vocabulary == "all" and b.dist is None)
     head = b.measure(n, args.depth, args.vocabulary, seed, args.steps, args.warmup, args.fuse, opts,
-                     probe_q=args.probe, with_1q_probe=True, cold=default_workload and not args.no_one_shot and not (args.wisdom and os.path.exists(args.wisdom)))
+                     probe_q=args.probe, with_1q_probe=args.full, cold=default_workload and not args.no_one_shot and not (args.wisdom and os.path.exists(args.wisdom)),
+                     sample=args.dump_outputs is not None)
 
     # other register sizes, same generator and defaults (north_star: n = 24/28/30/32)
     sizes = []
@@ -636,6 +707,8 @@ def main():
         from gpu_quantum_simulator_amd import _lib as _qlib
         _qlib.load().qsim_tune_table_save(args.wisdom.encode())
     if b.rank == 0:
+        if args.dump_outputs:
+            write_dump(args.dump_outputs, *head["sample"], head["norm2"])
         stats = head["stats"]
         ms_per_step = 1e3 * head["elapsed"] / args.steps
         value = args.depth * args.steps / head["elapsed"]

@@ -1,0 +1,3 @@
+OPENQASM 3.0;
+include "stdgates.inc";
+qubit[3] q;

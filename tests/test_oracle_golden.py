@@ -1,13 +1,12 @@
-"""Pins the oracle: oracle/cpu_ref.c must reproduce, BIT FOR BIT, the amplitudes the real reference
-(quantum_simulator.c compiled by oracle/Makefile `ref`) produced for every committed fixture, and —
-when oracle/_ref is present (container) — must equal the reference run live on fresh circuits."""
+"""Pins the oracle: oracle/cpu_ref.c must reproduce, BIT FOR BIT, what the real reference (quantum_simulator.c
+compiled by oracle/Makefile `ref`) produced for every committed fixture (tests/golden/make_golden.py records them), and —
+where oracle/_ref is built — the reference run live must still give those same bytes."""
 import json
 import os
 
 import numpy as np
 import pytest
 
-from gpu_quantum_simulator_amd import circuits
 
 
 def _cases(golden_dir):
@@ -98,59 +97,73 @@ def test_no_trailing_newline_and_blank_lines(oracle, tmp_path):
 
 @pytest.mark.parametrize("seed,n,kw", [(101, 4, {}), (102, 7, {"crlf": True}), (103, 11, {"physical": True}),
                                        (104, 13, {"qubit_style": "suffix"})])
-def test_oracle_equals_live_reference(oracle, tmp_path, seed, n, kw):
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref not built (no /root/reference on this host)")
-    path = circuits.random_circuit_file(str(tmp_path / "c.qasm"), n, 150, seed, "all", **kw)
-    rn, ref = oracle.reference_run_qasm(path)
+def test_oracle_equals_live_reference(oracle, golden_dir, seed, n, kw):
+    name = f"live_n{n}_seed{seed}"
+    case = _cases(golden_dir)[name]
+    assert (case["n"], case["seed"], case["depth"], case["text"]) == (n, seed, 150, kw)
+    path = os.path.join(golden_dir, name + ".qasm")
+    want = np.load(os.path.join(golden_dir, name + ".npy"), allow_pickle=False)  # the reference's amplitudes
     on, got, _, _ = oracle.run_qasm(path)
-    assert rn == on == n
-    assert got.view(np.float64).tobytes() == ref.view(np.float64).tobytes()
+    assert on == n
+    assert got.view(np.float64).tobytes() == want.tobytes()
+    if oracle.have_reference():
+        rn, ref = oracle.reference_run_qasm(path)
+        assert rn == n and ref.view(np.float64).tobytes() == want.tobytes()
 
 
-def test_oracle_kernels_equal_live_reference(oracle):
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref not built")
+def test_oracle_kernels_equal_live_reference(oracle, golden_dir):
     import ctypes
-    rng = np.random.default_rng(5)
-    n = 9
-    a = (rng.standard_normal(1 << n) + 1j * rng.standard_normal(1 << n)).astype(np.complex128)
+
+    def load(name):
+        return np.ascontiguousarray(np.load(os.path.join(golden_dir, name), allow_pickle=False)).view(np.complex128).reshape(-1)
+
+    n = _cases(golden_dir)["kernels_n9"]["n"]
+    a = load("kernels_n9_state.npy")
     b = a.copy()
-    U = (rng.standard_normal(4) + 1j * rng.standard_normal(4)).astype(np.complex128)  # NOT symmetric
-    dp = ctypes.POINTER(ctypes.c_double)
-    R = oracle.reference_lib()
+    U = load("kernels_n9_matrix.npy")  # NOT symmetric
+    assert U[1] != U[2]
     for q in range(n):
         oracle.apply_1q(a, n, U, q)
-        R.execute_single_qubit_gate(b.view(np.float64).ctypes.data_as(dp), n, U.view(np.float64).ctypes.data_as(dp), q)
         oracle.apply_cx(a, n, q, (q + 3) % n)
-        R.execute_cnot(b.view(np.float64).ctypes.data_as(dp), n, q, (q + 3) % n)
-    assert a.tobytes() == b.tobytes()
+    assert a.tobytes() == load("kernels_n9_out.npy").tobytes()  # the reference's two kernels, same calls, same input
+    if oracle.have_reference():
+        dp = ctypes.POINTER(ctypes.c_double)
+        R = oracle.reference_lib()
+        for q in range(n):
+            R.execute_single_qubit_gate(b.view(np.float64).ctypes.data_as(dp), n, U.view(np.float64).ctypes.data_as(dp), q)
+            R.execute_cnot(b.view(np.float64).ctypes.data_as(dp), n, q, (q + 3) % n)
+        assert a.tobytes() == b.tobytes()
 
 
 def test_measurement_post_path_equals_live_reference(oracle, golden_dir):
-    """quantum_simulator.c:256-293 (dead code in the reference's main, still compiled into oracle/_ref)."""
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref not built")
+    """quantum_simulator.c:256-293 (dead code in the reference's main, still compiled into oracle/_ref): its cumulative
+    distribution and measurement() draws on rand_n10_all, as make_golden.py recorded them (and live where oracle/_ref is)."""
     import ctypes
-    R = oracle.reference_lib()
     dp = ctypes.POINTER(ctypes.c_double)
-    R.compute_state_cumulative_distribution.argtypes = [dp, ctypes.c_int]
-    R.compute_state_cumulative_distribution.restype = ctypes.c_void_p
-    R.measurement.argtypes = [dp, ctypes.c_int]
-    R.measurement.restype = ctypes.c_longlong
     libc = ctypes.CDLL(None)
     n, amps, _, _ = oracle.run_qasm(os.path.join(golden_dir, "rand_n10_all.qasm"))
-    p = R.compute_state_cumulative_distribution(amps.view(np.float64).ctypes.data_as(dp), n)
-    ref_cumul = np.ctypeslib.as_array(ctypes.cast(p, dp), shape=(1 << n,)).copy()
+    ref_cumul = np.load(os.path.join(golden_dir, "rand_n10_all_cumulative.npy"), allow_pickle=False)
+    ref_draws = np.load(os.path.join(golden_dir, "rand_n10_all_measurement.npy"), allow_pickle=False)
+    assert n == _cases(golden_dir)["rand_n10_all_measurement"]["n"] and ref_draws.size == 39
     got = oracle.cumulative(amps, n)
     assert got.tobytes() == ref_cumul.tobytes()
     for seed in range(1, 40):
         libc.srand(seed)
-        want = R.measurement(ref_cumul.ctypes.data_as(dp), n)
-        libc.srand(seed)
         randn = oracle.lib().oracle_draw_randn()
-        assert oracle.measure(got, n, randn) == want
-    libc.free(ctypes.c_void_p(p))
+        assert oracle.measure(got, n, randn) == ref_draws[seed - 1]
+    if oracle.have_reference():
+        R = oracle.reference_lib()
+        R.compute_state_cumulative_distribution.argtypes = [dp, ctypes.c_int]
+        R.compute_state_cumulative_distribution.restype = ctypes.c_void_p
+        R.measurement.argtypes = [dp, ctypes.c_int]
+        R.measurement.restype = ctypes.c_longlong
+        p = R.compute_state_cumulative_distribution(amps.view(np.float64).ctypes.data_as(dp), n)
+        live = np.ctypeslib.as_array(ctypes.cast(p, dp), shape=(1 << n,)).copy()
+        assert live.tobytes() == ref_cumul.tobytes()
+        for seed in range(1, 40):
+            libc.srand(seed)
+            assert R.measurement(live.ctypes.data_as(dp), n) == ref_draws[seed - 1]
+        libc.free(ctypes.c_void_p(p))
     assert oracle.putb(5, 6) == "000101" and oracle.putb(63, 6) == "111111"
     # all-zero prefix is skipped (cumul == 0), a draw above the total lands on the last index
     c = np.array([0.0, 0.0, 0.25, 0.25, 1.0, 1.0, 1.0, 1.0])

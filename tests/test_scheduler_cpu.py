@@ -3,6 +3,7 @@
 The scheduler's output (fused blocks in launch order) is replayed with numpy and compared with the
 oracle running the unfused circuit — this pins the fusion algebra and the reordering rules
  without a GPU."""
+import json
 import os
 
 import numpy as np
@@ -120,9 +121,9 @@ def test_parse_errors():
         Circuit.from_text(hdr)
 
 
-def test_parser_corners_pinned_to_the_oracle(oracle, tmp_path):
+def test_parser_corners_pinned_to_the_oracle(oracle, golden_dir, tmp_path):
     """Two corners of quantum_simulator.c's statement loop (VERDICT r01 'missing' 7), checked against the oracle — and
-    against the compiled reference itself where oracle/_ref exists (this container):
+    against the reference's recorded answers (tests/golden/parser_*) and the compiled reference itself where oracle/_ref exists:
       * a second `qubit` statement re-initialises the state (:162-181): earlier gates are void;
       * `qubit` as the LAST statement followed by a newline is an 'Unknown token' error (:147-151,:179-180);
         with no character after it the file is accepted and yields |0...0>."""
@@ -156,6 +157,18 @@ def test_parser_corners_pinned_to_the_oracle(oracle, tmp_path):
     assert (c.num_qubits, len(c)) == (n, gates) == (3, 0)
     assert want[0] == 1 and not want[1:].any()
 
+    # the reference's answers, recorded by tests/golden/make_golden.py from the same three texts
+    with open(os.path.join(golden_dir, "MANIFEST.json")) as f:
+        manifest = json.load(f)
+    for path, name, ok in ((twice, "parser_qubit_twice", True), (last, "parser_qubit_last", True),
+                           (last_nl, "parser_qubit_last_newline", False)):
+        with open(os.path.join(golden_dir, name + ".qasm"), newline="") as f:
+            assert f.read() == path.read_text()
+        assert manifest[name].get("rejected", False) == (not ok)  # the reference returned NULL for the last one
+        if not ok:
+            continue
+        ref = np.load(os.path.join(golden_dir, name + ".npy"), allow_pickle=False)
+        assert oracle.run_qasm(str(path))[1].view(np.float64).tobytes() == ref.tobytes()
     if oracle.have_reference():
         for path, ok in ((twice, True), (last, True), (last_nl, False)):
             if ok:

@@ -7,7 +7,7 @@ out=$PWD/gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 rocprofv3 -L > $out/counters.txt 2>&1 || true
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -s -k "full_size_sharded or largest_sharded" > $out/pytest_sharded.log 2>&1; echo "pytest sharded exit $?" | tee -a $out/pytest_sharded.log
 tail -3 $out/pytest_sharded.log
-python3 bench.py --steps 5 --warmup 1 --wisdom $out/wisdom.txt --no-cpu-baseline --no-precision32 --no-one-shot --sizes= > $out/bench_n30.json 2> $out/bench_n30.err; echo "bench $?"
+python3 bench.py --full --steps 5 --warmup 1 --wisdom $out/wisdom.txt --no-cpu-baseline --no-precision32 --no-one-shot --sizes= > $out/bench_n30.json 2> $out/bench_n30.err; echo "bench $?"
 tail -c 600 $out/bench_n30.json
 for n in 28 30 32; do
   timeout -k 10 400 python3 tools/phase_split.py $n > $out/phase_split_n$n.log 2>&1; echo "phase_split $n: $?"; tail -1 $out/phase_split_n$n.log
