@@ -14,8 +14,6 @@ QSIM_OK, ERR_ARG, ERR_ALLOC, ERR_DEVICE, ERR_OPEN, ERR_PARSE = range(6)
 GATE_U1, GATE_CX, GATE_U2, GATE_U3 = 1, 2, 3, 4
 OPT_FUSE, OPT_PROFILE, OPT_TILE_BITS, OPT_TILE_LOW_BITS, OPT_MAX_PENDING, OPT_TILE_MAX_OPS, OPT_GRID_CAP, OPT_TILE_THREADS = range(1, 9)
 OPT_TILE_PAD_FROM = 9
-OPT_DEBUG_SKIP_OPS = 10
-OPT_DEBUG_SKIP_MEM = 11
 OPT_DEBUG_TILE_ORDER = 12
 OPT_PLAN_CACHE = 13
 OPT_PINGPONG = 14

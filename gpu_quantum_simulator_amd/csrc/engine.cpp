@@ -122,7 +122,7 @@ struct qsim_state {
     int pingpong = 1; // 0 never, 1 when the state is large enough to gain (kPingPongMinBytes), 2 whenever a second buffer can be had
     size_t amp_bytes() const { return f32 ? 8 : 16; }
     // options
-    int fuse = 3, profile = 0, tile_bits = 12, tile_low_bits = 3, tile_max_ops = 32, grid_cap = 0, tile_threads = 0, tile_pad_from = 10, debug_skip_ops = 0, debug_skip_mem = 0, debug_tile_order = 0;
+    int fuse = 3, profile = 0, tile_bits = 12, tile_low_bits = 3, tile_max_ops = 32, grid_cap = 0, tile_threads = 0, tile_pad_from = 10, debug_tile_order = 0;
     uint64_t tile_passes = 0; // launched so far (seeds the probe permutations of QSIM_OPT_DEBUG_TILE_ORDER)
     long max_pending = 1L << 16;
     // queue
@@ -285,7 +285,7 @@ extern "C" int qsim_set_option(qsim_state *s, int option, long value) {
         break;
     case QSIM_OPT_PROFILE: s->profile = value < 0 ? 0 : value > 2 ? 2 : (int)value; break;
     case QSIM_OPT_TILE_BITS:
-        if (value < 8 || value > (s->f32 ? 14 : 13)) return fail(QSIM_ERR_ARG, "tile_bits %ld not in 8..%d", value, s->f32 ? 14 : 13);
+        if (value < 8 || value > 13) return fail(QSIM_ERR_ARG, "tile_bits %ld not in 8..13", value);
         s->tile_bits = (int)value;
         break;
     case QSIM_OPT_TILE_LOW_BITS:
@@ -306,12 +306,6 @@ extern "C" int qsim_set_option(qsim_state *s, int option, long value) {
         break;
     case QSIM_OPT_TILE_PAD_FROM:
         s->tile_pad_from = (int)value;
-        break;
-    case QSIM_OPT_DEBUG_SKIP_OPS:
-        s->debug_skip_ops = value != 0;
-        break;
-    case QSIM_OPT_DEBUG_SKIP_MEM:
-        s->debug_skip_mem = value != 0;
         break;
     case QSIM_OPT_DEBUG_TILE_ORDER:
         s->debug_tile_order = (int)value;
@@ -353,8 +347,6 @@ extern "C" long qsim_get_option(const qsim_state *s, int option) {
     case QSIM_OPT_GRID_CAP: return s->grid_cap;
     case QSIM_OPT_TILE_THREADS: return s->tile_threads;
     case QSIM_OPT_TILE_PAD_FROM: return s->tile_pad_from;
-    case QSIM_OPT_DEBUG_SKIP_OPS: return s->debug_skip_ops;
-    case QSIM_OPT_DEBUG_SKIP_MEM: return s->debug_skip_mem;
     case QSIM_OPT_DEBUG_TILE_ORDER: return s->debug_tile_order;
     case QSIM_OPT_PLAN_CACHE: return s->plan_cache;
     case QSIM_OPT_PINGPONG: return s->pingpong;
@@ -818,7 +810,7 @@ static bool to_tile_op(const TileGeom &g, const TileBlock &blk, TileOp &t, bool 
 // by tile-local bit and are translated through local_bit(), so the order is invisible to them); with 2^L <= 8 amplitudes
 // per run and 512 threads, high[0..2] are walked by the lanes of a wave (the 8 runs one load instruction touches),
 // high[3..5] by the waves of the workgroup, high[6..8] by the 8 registers of a lane.  The memory-only time of a pass
-// depends on this order as much as on the set itself (n = 30, tools/geom_probe4.py: one set 6.56 ... 9.05 ms over 48
+// depends on this order as much as on the set itself (n = 30, profiles/r02/geom_probe4_fixed_sets.log: one set 6.56 ... 9.05 ms over 48
 // random orders, ascending 7.67; another 8.40 ... 14.05, ascending 14.06) and no simple rule predicts it (a boosted-tree
 // model on 3000 samples explains a third of the variance), so it is MEASURED: qsim_tune_circuit times candidate
 // orders for every pass of a circuit's schedule and keeps the best in a process-wide table keyed by (register size,
@@ -902,23 +894,15 @@ static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileO
                                 PackJob *job = nullptr) {
     LaunchCfg cfg{s->stream, s->grid_cap};
     const int threads = s->tile_threads; // 0: default for the tile size
-    void *out = oop ? s->spare : s->amps;
-    hipError_t e;
     if (job) {
         void *dst = job->out ? job->out : (s->spare && s->spare != s->amps ? s->spare : nullptr);
         if (!dst || dst == s->amps) return fail(QSIM_ERR_ARG, "internal: no buffer for the re-layout");
-        e = launch_tile(cfg, s->amps, dst, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, false, zero_mask, &job->map);
+        const hipError_t e = launch_tile(cfg, s->amps, dst, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, &job->map);
         if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
         job->packed_at = dst;
         return QSIM_OK;
     }
-    if (s->debug_skip_ops) {
-        TileGeom bare = geom;
-        bare.n_scale = 0;
-        e = launch_tile(cfg, s->amps, out, s->f32, bare, d, 0, threads, from_zero_ket, s->zero_ket_amp, false, zero_mask);
-    } else {
-        e = launch_tile(cfg, s->amps, out, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, s->debug_skip_mem != 0, zero_mask);
-    }
+    const hipError_t e = launch_tile(cfg, s->amps, oop ? s->spare : s->amps, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask);
     if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     if (oop) std::swap(s->amps, s->spare);
     return QSIM_OK;
@@ -1106,7 +1090,7 @@ static bool have_sched_hints() {
 // support_before: where the state can be non-zero when the pass starts (current_support() once every earlier pass has been launched).
 static bool pass_can_pack(const qsim_state *s, const Pass &p, const TileGeom &geom, const PackJob *job, uint64_t support_before) {
     static const bool trace = getenv("QSIM_TRACE_PACK") != nullptr; // says on stderr why a re-layout got its own sweep
-    if (p.kclass != QSIM_K_TILE || s->debug_skip_ops || s->debug_skip_mem || !launch_tile_can_pack(s->f32, geom, s->tile_threads)) {
+    if (p.kclass != QSIM_K_TILE || !launch_tile_can_pack(s->f32, geom, s->tile_threads)) {
         if (trace) fprintf(stderr, "qsim: re-layout not fused: last pass is %s\n", p.kclass != QSIM_K_TILE ? "no tile pass" : "a tile pass without the packing variant");
         return false;
     }
@@ -2091,8 +2075,6 @@ extern "C" int qsim_tune_circuit_support(qsim_state *s, const qsim_circuit *c, i
     HIP_TRY(hipEventCreate(&e1));
     const auto t_begin = std::chrono::steady_clock::now();
     auto elapsed_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-    const int saved_skip_mem = s->debug_skip_mem;
-    s->debug_skip_mem = 0;
     void *const home = s->amps;
     const bool tune_oop = !todo.empty() && spare_buffer(s) != nullptr;
     auto timed = [&](const Pass &p, const TileGeom &g, float &ms) -> int {
@@ -2144,7 +2126,6 @@ extern "C" int qsim_tune_circuit_support(qsim_state *s, const qsim_circuit *c, i
         g_wisdom[key] = best;
         g_wisdom_epoch++;
     }
-    s->debug_skip_mem = saved_skip_mem;
     (void)hipStreamSynchronize(s->stream);
     if (s->amps != home) std::swap(s->amps, s->spare); // contents are scratch here (reset below); the buffers keep their roles
     (void)hipEventDestroy(e0);

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(TPB) void k_gate2_hh(amp_t *__restrict__ v, uint64_
 // Geometry as the kernel sees it: the high tile bits as a mask (no runtime-indexed arrays in device code).
 struct TileDev {
     int32_t tile_bits, low_bits, n_high, n;
-    int32_t from_zero_ket, nomem; // nomem: measurement aid (QSIM_OPT_DEBUG_SKIP_MEM): no global loads or stores, blocks only.  from_zero_ket 1: the state is a basis state that has not been written yet: generate it, do not load it
+    int32_t from_zero_ket; // 1: the state is a basis state that has not been written yet: generate it, do not load it
     double amp0;                // its amplitude at index 0 (1 for |0...0>, 0 for a shard that does not hold index 0)
     uint64_t high_mask; // global bit positions of tile-local bits L..B-1 (as a set)
     uint64_t zero_mask; // index bits the state is known to be |0> in (qsim_state::support): amplitudes with such a bit set are
@@ -298,7 +298,7 @@ __device__ __forceinline__ uint32_t sw_byte(uint32_t byte) { return byte ^ (sw_f
 // `extern __shared__` symbol instead costs one v_add_u32 (of a link-time zero) per access.
 typedef __attribute__((address_space(3))) amp_t lds_amp_t;
 __device__ __forceinline__ amp_t lds_load(uint32_t byte) { return *(lds_amp_t *)(uintptr_t)byte; }
-__device__ __forceinline__ void lds_store(uint32_t byte, amp_t v) { *(lds_amp_t *)(uintptr_t)byte = v; }
+__device__ __forceinline__ void lds_put(uint32_t byte, amp_t v) { *(lds_amp_t *)(uintptr_t)byte = v; }
 
 // Index of the k-th work item with a zero inserted at bit b (b wave-uniform): x + (x & ~((1<<b)-1)).
 // Op coefficients are stored in the state's precision (the engine rounds once and packs them the way the kernels read them,
@@ -332,19 +332,6 @@ __device__ __forceinline__ amp_t cfma(amp_t a, coef_t c, amp_t acc) { return cfm
 
 __device__ __forceinline__ uint32_t ins0(uint32_t x, uint32_t himask) { return x + (x & himask); }
 
-// Measurement builds (tools/ab_build.sh tag "-DQSIM_EXP_..."): one ingredient of the block phase taken out at a time — the
-// results are WRONG, only the time of the blocks-only run (QSIM_OPT_DEBUG_SKIP_MEM) matters.  Never defined in the product build.
-#if defined(QSIM_EXP_NOBAR)
-#define QSIM_BLOCK_BARRIER() ((void)0)
-#else
-#define QSIM_BLOCK_BARRIER() __syncthreads()
-#endif
-#if defined(QSIM_EXP_NOLDSW)
-#define QSIM_LDS_STORE(addr_, val_) asm volatile("" ::"v"((val_).x), "v"((val_).y), "v"(addr_))
-#else
-#define QSIM_LDS_STORE(addr_, val_) lds_store((addr_), (val_))
-#endif
-
 // First 16 bytes of a TileOp as four dwords through one scalar load (layout: qsim_internal.h).
 typedef uint32_t OpHeader __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ OpHeader op_header(ConstOps ops, int oi) {
@@ -367,46 +354,18 @@ __device__ __forceinline__ int op_bank(const OpHeader h, uint64_t tile_base) {
 // follows a batch names the loaded registers as in/out operands, so nothing that uses them can move in front of it.  The
 // compiler's own s_waitcnt bookkeeping does not see these loads; that only makes its LDS waits conservative (LDS reads return in
 // order, and an outstanding scalar load can only keep the counter higher), and every batch is drained with lgkmcnt(0) here.
-#if defined(QSIM_EXP_NOWAIT) /* measurement build: the scalar loads are issued but never waited for (garbage coefficients) */
-#define QSIM_SMEM_WAIT "; no wait"
-#else
-#define QSIM_SMEM_WAIT "s_waitcnt lgkmcnt(0)"
-#endif
-#if defined(QSIM_EXP_STAMP)
-// Measurement build (tools/stamp_split.py, with QSIM_OPT_DEBUG_SKIP_MEM so that nothing else writes the state buffer): wave 0 of
-// every workgroup stamps the shader clock at fixed points of every block and lane 0 stores the stamps INTO THE STATE BUFFER
-// (32 slots per block, 32 blocks per workgroup), where the host reads them back as amplitudes.  The stamps serialise what the
-// real kernel overlaps: read their shares, not their sum.
-#define QSIM_STAMP(slot_) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                               if (tid == 0 && qsim_stamp_at) qsim_stamp_at[(slot_)] = t_; } while (0)
-#define QSIM_STAMP_ARG , unsigned long long *qsim_stamp_at
-#define QSIM_STAMP_PASS , qsim_stamp_at
-#else
-#define QSIM_STAMP(slot_) ((void)0)
-#define QSIM_STAMP_ARG
-#define QSIM_STAMP_PASS
-#endif
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 template <int BYTE>
 __device__ __forceinline__ u32x16 sload16(ConstRec rec) {
     u32x16 v;
-#if defined(QSIM_EXP_NOSMEM) /* measurement build: no scalar loads — coefficients in [0.5, 1) made from the pointer's low bits */
-    const uint32_t w = 0x3FE00000u | ((uint32_t)(uintptr_t)rec & 0xFFFFFu);
-    for (int k = 0; k < 16; k++) v[k] = (k & 1) ? w + (uint32_t)(BYTE + k) : 0u;
-#else
     asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(v) : "s"(rec), "n"(BYTE));
-#endif
     return v;
 }
 template <int BYTE>
 __device__ __forceinline__ u32x8 sload8(ConstRec rec) {
     u32x8 v;
-#if defined(QSIM_EXP_NOSMEM) /* ... and slot offsets 0, 16, 32, ... */
-    for (int k = 0; k < 8; k++) v[k] = (uint32_t)k << kAmpShift;
-#else
     asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(rec), "n"(BYTE));
-#endif
     return v;
 }
 // entry j of a coefficient row held in SGPRs: dwords 4j .. 4j+3 (fp64: re, im; fp32: the pairs (ur, ui), (-ui, ur))
@@ -478,7 +437,7 @@ __device__ __forceinline__ PartPlan<B, THREADS> part_prepare(uint32_t lds_base, 
 }
 
 template <int B, int THREADS, int T, bool SKIPS>
-__device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uint32_t tid, bool mid_barrier QSIM_STAMP_ARG) {
+__device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uint32_t tid, bool mid_barrier) {
     constexpr uint32_t E = 1u << B;
     constexpr uint32_t ITEMS = E / kPartRows;
     constexpr int IPT = ITEMS >= (uint32_t)THREADS ? ITEMS / THREADS : 1;
@@ -499,35 +458,26 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
 #pragma unroll
     for (int i = 0; i < IPT; i++) {
         const bool live = FULL || tid + i * THREADS < ITEMS;
-        if (i == 0) QSIM_STAMP(1); // block prepared
         off[i] = sload8<0>(rec[i]);
         if constexpr (IPT == 1) rowoff1 = sload8<32>(rec[i]);
         if constexpr (IPT == 1) {
             c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]);
             if constexpr (T != 1) { c2 = sload16<kRecCoefByte + 128>(rec[i]); c3 = sload16<kRecCoefByte + 192>(rec[i]); }
-            if constexpr (T == 1) asm volatile(QSIM_SMEM_WAIT : "+s"(off[i]), "+s"(rowoff1), "+s"(c0), "+s"(c1));
-            else asm volatile(QSIM_SMEM_WAIT : "+s"(off[i]), "+s"(rowoff1), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+            if constexpr (T == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(off[i]), "+s"(rowoff1), "+s"(c0), "+s"(c1));
+            else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(off[i]), "+s"(rowoff1), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
         } else {
-            asm volatile(QSIM_SMEM_WAIT : "+s"(off[i]));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(off[i]));
         }
-        if (i == 0) QSIM_STAMP(2); // first scalar batch arrived
 #pragma unroll
         for (int c = 0; c < NC; c++) {
             if (SKIPS && off[i][c * T] == kSkipClass) continue; // every row of the class is an identity row (wave-uniform)
             if (live) {
 #pragma unroll
-#if defined(QSIM_EXP_NOLDSR) /* measurement build: operands out of thin air */
-                for (int j = 0; j < T; j++) x[i][c * T + j] = amp_t{(real_t)(base[i] ^ off[i][c * T + j]), (real_t)1};
-#else
                 for (int j = 0; j < T; j++) x[i][c * T + j] = lds_load(base[i] ^ off[i][c * T + j]); // the class's T operands, read once
-#endif
             }
         }
     }
-#if !defined(QSIM_EXP_NOMID)
-    if (mid_barrier) QSIM_BLOCK_BARRIER(); // lanes of other waves write slots this one reads: every lane has its operands
-#endif
-    QSIM_STAMP(3); // operands arrived, through the barrier between reads and writes
+    if (mid_barrier) __syncthreads(); // lanes of other waves write slots this one reads: every lane has its operands
     // Phase 2 per item: multiply-adds (T = 4: class 0, the second coefficient batch into the same registers, class 1), then
     // the item's 8 writes.
 #pragma unroll
@@ -538,14 +488,10 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
         auto row = [&](int p, const coef_t *cf) { // y[p] = sum_j cf[j] * x[class of p][j]
             if (live) {
                 const int q0 = (p / T) * T;
-#if defined(QSIM_EXP_NOFMA) /* measurement build: no arithmetic */
-                y[p] = x[i][q0 + p % T]; // (the scalar loads are volatile asm statements: they stay)
-#else
                 amp_t acc = cmul(x[i][q0], cf[0]);
 #pragma unroll
                 for (int j = 1; j < T; j++) acc = cfma(x[i][q0 + j], cf[j], acc);
                 y[p] = acc;
-#endif
             }
         };
         if constexpr (T == 4) {
@@ -556,7 +502,7 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
                 rowoff = sload8<32>(rec[i]);
                 c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]);
                 c2 = sload16<kRecCoefByte + 128>(rec[i]); c3 = sload16<kRecCoefByte + 192>(rec[i]);
-                asm volatile(QSIM_SMEM_WAIT : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
             } else {
                 rowoff = rowoff1;
             }
@@ -568,7 +514,6 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
                 row(0, r0); row(1, r1); row(2, r2); row(3, r3);
                 if (live) asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3])); // class 0 is done before its registers are loaded over
             }
-            if (i == 0) QSIM_STAMP(4); // class 0 multiplied
             const bool second = !(SKIPS && off[i][4] == kSkipClass);
             if (second) {
                 c0 = sload16<kRecCoefByte + 256>(rec[i]); c1 = sload16<kRecCoefByte + 320>(rec[i]);
@@ -576,10 +521,9 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
             }
             if (!(SKIPS && off[i][0] == kSkipClass) && live) { // class 0 leaves while class 1's coefficients arrive
 #pragma unroll
-                for (int p = 0; p < 4; p++) QSIM_LDS_STORE(base[i] ^ rowoff[p], y[p]);
+                for (int p = 0; p < 4; p++) lds_put(base[i] ^ rowoff[p], y[p]);
             }
-            asm volatile(QSIM_SMEM_WAIT : "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
-            if (i == 0) QSIM_STAMP(5); // second scalar batch arrived
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
             if (second) {
                 const coef_t r0[4] = {sgpr_coef(c0, 0), sgpr_coef(c0, 1), sgpr_coef(c0, 2), sgpr_coef(c0, 3)};
                 const coef_t r1[4] = {sgpr_coef(c1, 0), sgpr_coef(c1, 1), sgpr_coef(c1, 2), sgpr_coef(c1, 3)};
@@ -588,17 +532,16 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
                 row(4, r0); row(5, r1); row(6, r2); row(7, r3);
                 if (live) {
 #pragma unroll
-                    for (int p = 4; p < 8; p++) QSIM_LDS_STORE(base[i] ^ rowoff[p], y[p]);
+                    for (int p = 4; p < 8; p++) lds_put(base[i] ^ rowoff[p], y[p]);
                 }
             }
-            if (i == 0) QSIM_STAMP(6); // class 1 multiplied
             continue; // (written above)
         } else if constexpr (T == 2) {
             if constexpr (IPT != 1) {
                 rowoff = sload8<32>(rec[i]);
                 c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]);
                 c2 = sload16<kRecCoefByte + 128>(rec[i]); c3 = sload16<kRecCoefByte + 192>(rec[i]); // two rows of two entries each
-                asm volatile(QSIM_SMEM_WAIT : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
             } else {
                 rowoff = rowoff1;
             }
@@ -609,13 +552,13 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
                 const coef_t ra[2] = {sgpr_coef(*cs[c], 0), sgpr_coef(*cs[c], 1)}, rb[2] = {sgpr_coef(*cs[c], 2), sgpr_coef(*cs[c], 3)};
                 row(2 * c, ra);
                 row(2 * c + 1, rb);
-                if (live) { QSIM_LDS_STORE(base[i] ^ rowoff[2 * c], y[2 * c]); QSIM_LDS_STORE(base[i] ^ rowoff[2 * c + 1], y[2 * c + 1]); }
+                if (live) { lds_put(base[i] ^ rowoff[2 * c], y[2 * c]); lds_put(base[i] ^ rowoff[2 * c + 1], y[2 * c + 1]); }
             }
         } else {
             if constexpr (IPT != 1) {
                 rowoff = sload8<32>(rec[i]);
                 c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]); // four rows of one entry each
-                asm volatile(QSIM_SMEM_WAIT : "+s"(rowoff), "+s"(c0), "+s"(c1));
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1));
             } else {
                 rowoff = rowoff1;
             }
@@ -624,11 +567,10 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
                 if (SKIPS && off[i][p] == kSkipClass) continue;
                 const coef_t r[1] = {sgpr_coef(p < 4 ? c0 : c1, p & 3)};
                 row(p, r);
-                if (live) QSIM_LDS_STORE(base[i] ^ rowoff[p], y[p]);
+                if (live) lds_put(base[i] ^ rowoff[p], y[p]);
             }
         }
     }
-    QSIM_STAMP(8); // writes issued and (the stamp's own wait) done
 }
 
 // The pair / quad forms (TOP_G1, TOP_DIAG1, TOP_G2) for tiles of fewer than 2^3 amplitudes, where a block cannot be padded to
@@ -680,7 +622,7 @@ __device__ __forceinline__ void tile_op_small(amp_t *lds, ConstOps ops, int oi, 
 // carried across the loop edge cost more scalar registers than the overlap won: 69.5 ms per step against 68.8), and a
 // per-workgroup table in LDS of everything that does not depend on the tile (~40 instructions left: 67.4 against 67.2).
 template <int B, int THREADS>
-__device__ __forceinline__ void tile_apply_ops(amp_t *lds, uint32_t lds_base, ConstOps ops, int n_ops, uint32_t tid, uint64_t tile_base QSIM_STAMP_ARG) {
+__device__ __forceinline__ void tile_apply_ops(amp_t *lds, uint32_t lds_base, ConstOps ops, int n_ops, uint32_t tid, uint64_t tile_base) {
     if constexpr (B < 3) {
         OpHeader hn = op_header(ops, 0);
         for (int oi = 0; oi < n_ops; oi++) {
@@ -690,47 +632,34 @@ __device__ __forceinline__ void tile_apply_ops(amp_t *lds, uint32_t lds_base, Co
             const int bank = op_bank(h, tile_base);
             if ((h[1] >> (16 + bank)) & 1u) continue;
             tile_op_small<B, THREADS>(lds, ops, oi, tid, bank, h);
-            QSIM_BLOCK_BARRIER();
+            __syncthreads();
         }
     } else {
         OpHeader hn = op_header(ops, 0);
         for (int oi = 0; oi < n_ops; oi++) {
-#if defined(QSIM_EXP_STAMP)
-            if (qsim_stamp_at) { if (oi) qsim_stamp_at += 32; if (oi >= 32) qsim_stamp_at = nullptr; }
-            QSIM_STAMP(0); // block start
-#endif
             const OpHeader h = hn;
             hn = op_header(ops, oi + 1 < n_ops ? oi + 1 : oi);
             const PartPlan<B, THREADS> cur = part_prepare<B, THREADS>(lds_base, ops, oi, h, tile_base, tid);
-#if defined(QSIM_EXP_STAMP)
-            if (tid == 0 && qsim_stamp_at) qsim_stamp_at[15] = cur.info;
-#endif
             const uint32_t info = cur.info;
             const bool mid = info & 16u;
             if (!(info & 1u)) continue; // the tile's bank is the identity (a CX whose control bit is 0 here): nothing happens at all
             switch (info & 14u) {
-            case 4: tile_op_part<B, THREADS, 4, false>(cur, tid, mid QSIM_STAMP_PASS); break;
-            case 12: tile_op_part<B, THREADS, 4, true>(cur, tid, mid QSIM_STAMP_PASS); break;
-            case 2: tile_op_part<B, THREADS, 2, false>(cur, tid, mid QSIM_STAMP_PASS); break;
-            case 10: tile_op_part<B, THREADS, 2, true>(cur, tid, mid QSIM_STAMP_PASS); break;
-            case 0: tile_op_part<B, THREADS, 1, false>(cur, tid, mid QSIM_STAMP_PASS); break;
-            default: tile_op_part<B, THREADS, 1, true>(cur, tid, mid QSIM_STAMP_PASS); break;
+            case 4: tile_op_part<B, THREADS, 4, false>(cur, tid, mid); break;
+            case 12: tile_op_part<B, THREADS, 4, true>(cur, tid, mid); break;
+            case 2: tile_op_part<B, THREADS, 2, false>(cur, tid, mid); break;
+            case 10: tile_op_part<B, THREADS, 2, true>(cur, tid, mid); break;
+            case 0: tile_op_part<B, THREADS, 1, false>(cur, tid, mid); break;
+            default: tile_op_part<B, THREADS, 1, true>(cur, tid, mid); break;
             }
-            QSIM_STAMP(10);
-            QSIM_BLOCK_BARRIER();
-            QSIM_STAMP(9); // through the barrier that ends the block
+            __syncthreads();
         }
     }
 }
 
 // B (tile size) and THREADS are compile-time so every per-thread loop has a static trip count: all LDS
 // reads of an op are issued before its arithmetic, all writes after, and there is no loop bookkeeping.
-// NOMEM: the measurement build behind QSIM_OPT_DEBUG_SKIP_MEM (no global loads or stores, blocks on zero tiles).  A
-// template parameter, not a flag in TileDev: a run-time "skip the stores" branch gives the vmcnt bookkeeping below a
-// path on which the prefetch loads are the youngest vector-memory operations, and the compiler then waits for
-// vmcnt(0) before every stage-in — i.e. for the previous tile's stores — in the production kernel too.  It did for most
-// of round 2; with two workgroups per CU the drain turned out to cost only 0.2-0.7 % of the step (same box, alternating
-// runs), but the ISA is back to vmcnt(15..8) in the loop.
+// No run-time branch may skip the stage-out: on such a path the prefetch loads are the youngest vector-memory operations and
+// the compiler waits for vmcnt(0) — the previous tile's stores — before every stage-in (0.2-0.7 % of a step in round 2).
 // PACK: the pass also does the re-layout of the exchange that follows it (qsim_internal.h PackMap): every amplitude is stored
 // at perm(its index) of `vout` instead of at its own index — the separate pack sweep over the shard (k_pack: one more read
 // and write of the state per exchange) disappears.  perm is a permutation of index BITS, so it splits like the index itself
@@ -744,7 +673,7 @@ __device__ __forceinline__ uint64_t pack_perm(const PackMap &pm, uint64_t x) {
     return o;
 }
 
-template <int B, int THREADS, bool NOMEM = false, bool PACK = false>
+template <int B, int THREADS, bool PACK = false>
 __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(amp_t *v, amp_t *vout, TileDev g, const TileOp *__restrict__ ops_g,
                                                   int n_ops, uint64_t ntiles, int tiles_per_wg, int n_scale, PackMap pm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -765,7 +694,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     const uint64_t nmask = g.n >= 64 ? ~0ULL : ((1ULL << g.n) - 1ULL);
     const uint64_t outer_mask = nmask & ~(g.high_mask | (uint64_t)lowmask) & ~g.zero_mask; // the tiles to visit: outer bits that may be 1
 
-    // lds_load / lds_store address the tile by raw LDS byte address: that is only right while this kernel's dynamic
+    // lds_load / lds_put address the tile by raw LDS byte address: that is only right while this kernel's dynamic
     // LDS region starts at 0, i.e. while nobody adds a static __shared__ array to it.  Fail loudly otherwise.
     if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem != 0u) __builtin_trap();
 
@@ -819,11 +748,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     amp_t pf[APT];
     const bool generate = g.from_zero_ket != 0; // wave-uniform
     auto fetch = [&](uint64_t tb) {
-#if defined(QSIM_EXP_NOLOAD) /* measurement build: the pass stores but never loads */
-        if (true) {
-#else
-        if (generate || NOMEM) { // |0...0>: amplitude 1 at global index 0 (tile base 0, slot 0), nothing to read
-#endif
+        if (generate) { // |0...0>: amplitude 1 at global index 0 (tile base 0, slot 0), nothing to read
 #pragma unroll
             for (int k = 0; k < APT; k++) pf[k] = amp_t{(real_t)((tb == 0 && k == 0 && tid == 0) ? g.amp0 : 0.0), (real_t)0};
             return;
@@ -861,46 +786,29 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
         __syncthreads();
         if (prefetch_next) fetch(next_base(base));
 
-#if defined(QSIM_EXP_STAMP)
-        // 32 blocks x 32 stamps per workgroup, inside the (unwritten: NOMEM) state buffer; later tiles of a workgroup overwrite earlier ones
-        // the first 2048 workgroups of a launch; launches are told apart by where their op list sits (64 regions of 16 MiB)
-        const uint64_t qsim_region = ((uint64_t)(uintptr_t)ops_g / sizeof(TileOp)) & 63u;
-        unsigned long long *qsim_stamp_at = NOMEM && blockIdx.x < 2048u && g.n >= 27
-                                                ? reinterpret_cast<unsigned long long *>(v) + (qsim_region << 21) + ((uint64_t)blockIdx.x << 10) : nullptr;
-        if (tid == 0 && qsim_stamp_at) {
-            qsim_stamp_at[1023] = __builtin_amdgcn_s_memrealtime(); qsim_stamp_at[1022] = __builtin_amdgcn_s_memtime();
-            qsim_stamp_at[1021] = 0x51534D5453544D50ULL; qsim_stamp_at[1020] = (unsigned long long)n_ops;
-        }
-#endif
-        tile_apply_ops<B, THREADS>(lds, 0u, ops, n_ops, tid, base QSIM_STAMP_PASS);
+        tile_apply_ops<B, THREADS>(lds, 0u, ops, n_ops, tid, base);
 
         // stage out: every LDS read first (one wait for all of them instead of one per pair of stores), then the stores,
         // whose wave-uniform address part (tile base + register-bit offset + distance to the output buffer) stays scalar
-        if (!NOMEM) {
-            amp_t so[APT];
+        amp_t so[APT];
+#pragma unroll
+        for (int k = 0; k < APT; k++) {
+            const uint32_t e = tid + k * THREADS;
+            if (FULL || e < E) so[k] = lds[stage_slot(k)];
+        }
+        if (PACK) {
+            const uint64_t sbase = (pack_perm(pm, base) | pm.konst) << kAmpShift; // wave-uniform
 #pragma unroll
             for (int k = 0; k < APT; k++) {
                 const uint32_t e = tid + k * THREADS;
-                if (FULL || e < E) so[k] = lds[stage_slot(k)];
+                if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(vout) + lane_out + (sbase + k_out[k])) = so[k];
             }
-            if (PACK) {
-                const uint64_t sbase = (pack_perm(pm, base) | pm.konst) << kAmpShift; // wave-uniform
+        } else {
+            const uint64_t sbase = (base << kAmpShift) + (uint64_t)out_shift; // wave-uniform
 #pragma unroll
-                for (int k = 0; k < APT; k++) {
-                    const uint32_t e = tid + k * THREADS;
-                    if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(vout) + lane_out + (sbase + k_out[k])) = so[k];
-                }
-            } else {
-                const uint64_t sbase = (base << kAmpShift) + (uint64_t)out_shift; // wave-uniform
-#pragma unroll
-                for (int k = 0; k < APT; k++) {
-                    const uint32_t e = tid + k * THREADS;
-#if defined(QSIM_EXP_NOSTORE) /* measurement build: the pass loads but never stores */
-                    if (FULL || e < E) asm volatile("" ::"v"(so[k]), "s"(sbase));
-#else
-                    if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(v) + lane_off + (sbase + k_off[k])) = so[k];
-#endif
-                }
+            for (int k = 0; k < APT; k++) {
+                const uint32_t e = tid + k * THREADS;
+                if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(v) + lane_off + (sbase + k_off[k])) = so[k];
             }
         }
         __syncthreads();
@@ -1151,7 +1059,7 @@ constexpr bool tile_has_pack(int b, int threads) { return kAmpShift == 4 && b ==
 
 template <int B, int THREADS>
 static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops,
-                                bool from_zero_ket, double amp0, bool nomem, uint64_t zero_mask, const PackMap *pack) {
+                                bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
     uint64_t tile_mask = (1ULL << g.low_bits) - 1ULL;
     for (int j = 0; j < g.n_high; j++) tile_mask |= 1ULL << g.high[j];
     const uint64_t nmask = g.n >= 64 ? ~0ULL : ((1ULL << g.n) - 1ULL);
@@ -1159,25 +1067,21 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     const uint64_t ntiles = 1ULL << __builtin_popcountll(nmask & ~tile_mask & ~zero_mask); // tiles whose base index may be non-zero
     const int lds = tile_lds_bytes(g.tile_bits, g.n_high);
     // the opt-in to more than 64 KiB of dynamic LDS is per device (a cluster drives several from one process)
-    static bool attr_set[64][2] = {{false, false}};
+    static bool attr_set[64] = {false};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    constexpr bool kHasNomem = B >= 12; // the measurement variant exists for the production tile sizes only
-    if (nomem && !kHasNomem) return hipErrorNotSupported;
     constexpr bool kHasPack = tile_has_pack(B, THREADS);
     const bool packed = pack != nullptr && pack->k > 0;
-    if (packed && (!kHasPack || nomem)) return hipErrorNotSupported;
-    if (!attr_set[dev][nomem ? 1 : 0]) {
-        const void *fn = reinterpret_cast<const void *>(&k_tile<B, THREADS, false>);
-        if constexpr (kHasNomem) { if (nomem) fn = reinterpret_cast<const void *>(&k_tile<B, THREADS, true>); }
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (packed && !kHasPack) return hipErrorNotSupported;
+    if (!attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile<B, THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
-        attr_set[dev][nomem ? 1 : 0] = true;
+        attr_set[dev] = true;
     }
     static bool pack_attr_set[64] = {false};
     if constexpr (kHasPack) {
         if (packed && !pack_attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile<B, THREADS, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile<B, THREADS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             pack_attr_set[dev] = true;
         }
@@ -1186,7 +1090,6 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     TileDev td;
     td.tile_bits = g.tile_bits; td.low_bits = g.low_bits; td.n_high = g.n_high; td.n = g.n;
     td.from_zero_ket = from_zero_ket ? 1 : 0;
-    td.nomem = nomem ? 1 : 0;
     td.amp0 = amp0;
     td.high_mask = 0;
     td.zero_mask = zero_mask;
@@ -1209,21 +1112,14 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     // d_ops: g.n_scale tile-uniform factors first, then the blocks
     const int n_scale = n_ops > 0 ? g.n_scale : 0;
     PackMap pm{};
-    if constexpr (kHasNomem) {
-        if (nomem) {
-            hipLaunchKernelGGL((k_tile<B, THREADS, true>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops,
-                               n_ops - n_scale, ntiles, tpw, n_scale, pm);
-            return hipGetLastError();
-        }
-    }
     if constexpr (kHasPack) {
         if (packed) {
-            hipLaunchKernelGGL((k_tile<B, THREADS, false, true>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops,
+            hipLaunchKernelGGL((k_tile<B, THREADS, true>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops,
                                n_ops - n_scale, ntiles, tpw, n_scale, *pack);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((k_tile<B, THREADS, false>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, n_ops - n_scale,
+    hipLaunchKernelGGL((k_tile<B, THREADS>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, n_ops - n_scale,
                        ntiles, tpw, n_scale, pm);
     return hipGetLastError();
 }
@@ -1234,33 +1130,37 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
 static bool launch_tile_can_pack(const TileGeom &g, int threads) { return tile_has_pack(g.tile_bits, g.tile_bits == 12 && threads != 256 && threads != 1024 ? 512 : 0); }
 
 hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads,
-                       bool from_zero_ket, double amp0, bool nomem, uint64_t zero_mask, const PackMap *pack) {
+                       bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
+#define QSIM_TILE(B_, T_) launch_tile_t<B_, T_>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, zero_mask, pack)
     switch (g.tile_bits) {
-    case 0: return launch_tile_t<0, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 1: return launch_tile_t<1, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 2: return launch_tile_t<2, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 3: return launch_tile_t<3, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 4: return launch_tile_t<4, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 5: return launch_tile_t<5, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 6: return launch_tile_t<6, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 7: return launch_tile_t<7, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 8: return launch_tile_t<8, 64>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 9: return launch_tile_t<9, 128>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 10: return threads == 512 ? launch_tile_t<10, 512>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack) : launch_tile_t<10, 256>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-    case 11: return threads == 512 ? launch_tile_t<11, 512>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack) : launch_tile_t<11, 256>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
+    case 0: return QSIM_TILE(0, 64);
+    case 1: return QSIM_TILE(1, 64);
+    case 2: return QSIM_TILE(2, 64);
+    case 3: return QSIM_TILE(3, 64);
+    case 4: return QSIM_TILE(4, 64);
+    case 5: return QSIM_TILE(5, 64);
+    case 6: return QSIM_TILE(6, 64);
+    case 7: return QSIM_TILE(7, 64);
+    case 8: return QSIM_TILE(8, 64);
+    case 9: return QSIM_TILE(9, 128);
+    case 10: return threads == 512 ? QSIM_TILE(10, 512) : QSIM_TILE(10, 256);
+    case 11: return threads == 512 ? QSIM_TILE(11, 512) : QSIM_TILE(11, 256);
     case 12:
-        if (threads == 256) return launch_tile_t<12, 256>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-        if (threads == 1024) return launch_tile_t<12, 1024>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-        return launch_tile_t<12, 512>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
+        if (threads == 256) return QSIM_TILE(12, 256);
+        if (threads == 1024) return QSIM_TILE(12, 1024);
+        return QSIM_TILE(12, 512);
     case 13:
         // default: the shape with 64 KiB tiles runs 512 threads and two workgroups per CU (fp32); 128 KiB tiles take 1024
-        if (threads == 512 || (threads == 0 && kAmpShift == 3)) return launch_tile_t<13, 512>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
-        return launch_tile_t<13, 1024>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack);
+        if (threads == 512 || (threads == 0 && kAmpShift == 3)) return QSIM_TILE(13, 512);
+        return QSIM_TILE(13, 1024);
 #if QSIM_AMP_SHIFT == 3
-    case 14: return launch_tile_t<14, 1024>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, nomem, zero_mask, pack); // 128 KiB of fp32 amplitudes
+    // unreachable (QSIM_OPT_TILE_BITS stops at 13: to_tile_op packs only 10 free tile bits), but without this instantiation
+    // the compiler lays out the setup of f32 k_tile<13, 512> differently and the fp32 step is 1.2 % slower (DESIGN §3)
+    case 14: return QSIM_TILE(14, 1024);
 #endif
     default: return hipErrorInvalidValue;
     }
+#undef QSIM_TILE
 }
 
 hipError_t launch_norm2(const LaunchCfg &cfg, const void *v, int n, double *d_out) {

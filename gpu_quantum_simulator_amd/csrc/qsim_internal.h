@@ -114,7 +114,7 @@ hipError_t launch_gate2(const LaunchCfg &cfg, void *v, bool f32, int n, int q_hi
 // vout: where the pass writes the state — v itself (in place) or a second buffer of the same size
 // pack (fp64, the default tile shape only — launch_tile_can_pack): vout is the output buffer of the re-layout, written at perm(index)
 hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, bool f32, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads,
-                       bool from_zero_ket, double amp0, bool nomem = false, uint64_t zero_mask = 0, const PackMap *pack = nullptr);
+                       bool from_zero_ket, double amp0, uint64_t zero_mask = 0, const PackMap *pack = nullptr);
 bool launch_tile_can_pack(bool f32, const TileGeom &g, int threads);
 // zeroes the amplitudes whose index has a bit of zero_mask set (the part of a state the tile passes have not written yet)
 hipError_t launch_zero_outside(const LaunchCfg &cfg, void *v, bool f32, int n, uint64_t zero_mask);

@@ -52,15 +52,14 @@ enum {
      *      done with a full grid)                   [default]                                        */
     QSIM_OPT_FUSE = 1,
     QSIM_OPT_PROFILE = 2,      /* 1: bracket every launch with HIP events on the engine's stream; 2: also record each tile pass's block forms (qsim_launch_log_blocks) */
-    QSIM_OPT_TILE_BITS = 3,    /* log2 amplitudes per LDS tile for level 3 (8..13, default 12 = 64 KiB) */
+    QSIM_OPT_TILE_BITS = 3,    /* log2 amplitudes per LDS tile for level 3 (8..13 in either precision, default 12 = 64 KiB of fp64) */
     QSIM_OPT_TILE_LOW_BITS = 4,/* contiguous low index bits always inside a tile (2..6, default 3 -> 128-B runs, 9 free high-qubit slots) */
     QSIM_OPT_MAX_PENDING = 5,  /* queued gates that force a flush (default 1<<16) */
     QSIM_OPT_TILE_MAX_OPS = 6, /* upper bound on fused blocks per tile pass (default 32) */
     QSIM_OPT_GRID_CAP = 7,     /* 0: one workgroup per work tile; >0: at most that many workgroups (grid-stride loop) */
     QSIM_OPT_TILE_PAD_FROM = 9,/* first index bit used to fill unused high slots of a tile (default 10) */
     QSIM_OPT_TILE_THREADS = 8, /* threads per tile workgroup: 0 auto (256 below 2^12 amplitudes, else 512), 256, 512, 1024 */
-    QSIM_OPT_DEBUG_SKIP_OPS = 10,/* measurement aid, default 0: 1 = tile passes move their tiles HBM -> LDS -> HBM but apply
-                                  * no blocks (amplitudes are then WRONG); splits a pass's memory time from its compute time */
+    /* 10 and 11 were measurement aids; they are retired and rejected like any unknown option */
     QSIM_OPT_PLAN_CACHE = 13,  /* default 1: the plans of the last few flushed gate queues are kept (passes, bit orders, blocks on the
                                 * device); a queue with the same gates is replayed without scheduling or uploads.  0 = plan anew */
     QSIM_OPT_PINGPONG = 14,    /* tile passes out of place: each reads the state from one buffer and writes it to a second one, and the
@@ -77,8 +76,6 @@ enum {
     QSIM_OPT_DEBUG_TILE_ORDER = 12,/* measurement aid, default 0: k > 0 = every tile pass walks its high tile bits in a pseudo-random
                                   * order seeded by k (results are unchanged: the order only decides which bits lanes, waves and
                                   * registers walk) */
-    QSIM_OPT_DEBUG_SKIP_MEM = 11 /* measurement aid, default 0: 1 = tile passes apply their blocks to zero-filled tiles and
-                                  * neither load nor store the state (amplitudes are then WRONG): the block phase alone */
 };
 
 /* Kernel classes reported by qsim_get_stats. */

@@ -45,6 +45,19 @@ def test_precision_flag_and_io_round_trip():
         Simulator(4, precision=16)
 
 
+@pytest.mark.parametrize("precision", [32, 64])
+def test_tile_bits_14_and_retired_options_rejected(precision):
+    from gpu_quantum_simulator_amd import _lib
+    with Simulator(10, precision=precision) as sim:
+        sim.set_option(_lib.OPT_TILE_BITS, 13)
+        with pytest.raises(_lib.QsimError, match="not in 8..13"):
+            sim.set_option(_lib.OPT_TILE_BITS, 14)
+        assert _lib.load().qsim_get_option(sim._h, _lib.OPT_TILE_BITS) == 13
+        for opt in (10, 11):  # retired measurement aids: rejected like any unknown option
+            with pytest.raises(_lib.QsimError, match="unknown option"):
+                sim.set_option(opt, 1)
+
+
 @pytest.mark.parametrize("fuse", [0, 1, 2, 3])
 @pytest.mark.parametrize("name", ["entanglement", "grover_3_18", "rand_n10_all", "rand_n12_all",
                                   "rand_n12_clifford_t_physical"])
