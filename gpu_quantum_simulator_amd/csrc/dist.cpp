@@ -218,7 +218,7 @@ std::vector<size_t> small_tail(const std::vector<LGate> &run, const std::vector<
 // non-diagonal gate has touched (x q; cx q,t; x q leaves q where it was, and the fused cluster shows it).
 // cost_sweeps (optional): += what the step is predicted to take, in sweeps of the shard (pass_time_cost).
 uint64_t scheduled_support(const std::vector<LocalOp> &ops, int m, uint64_t support, double *cost_sweeps = nullptr) {
-    const uint64_t all = m >= 64 ? ~0ULL : ((1ULL << m) - 1ULL);
+    const uint64_t all = qsim::index_mask(m);
     if (ops.empty() || (!cost_sweeps && (support & all) == all)) return support & all;
     qsim::Scheduler sched(qsim::engine_sched_config(m, 3, 12, 3, 32, 10, false, (support & all) == all ? ~0ULL : (support & all)));
     for (const LocalOp &o : ops) {
@@ -230,8 +230,7 @@ uint64_t scheduled_support(const std::vector<LocalOp> &ops, int m, uint64_t supp
     sched.finish([&](qsim::Pass &&ps) {
         if (cost_sweeps) *cost_sweeps += qsim::pass_time_cost(ps, false) / (32.0 * (double)(1ULL << m));
         if (ps.kclass != QSIM_K_TILE) { sup = all; return; } // a single-gate kernel: the engine writes the zeros out first
-        sup |= (1ULL << ps.geom.low_bits) - 1ULL;
-        for (int j = 0; j < ps.geom.n_high; j++) sup |= 1ULL << ps.geom.high[j];
+        sup |= qsim::tile_mask(ps.geom);
     });
     return sup & all;
 }

@@ -260,38 +260,10 @@ __device__ __forceinline__ uint64_t deposit(uint64_t x, uint64_t mask) {
 // loads (s_load_dwordx*): the matrix lives in SGPRs / the scalar cache, not in vector registers.
 typedef const TileOp __attribute__((address_space(4))) *ConstOps;
 
-// LDS layout swizzle of a tile slot index: the 16-byte unit inside a 256-byte bank row (slot bits 0..3) is XORed with a
-// linear image of the HIGHER slot bits.  A block on tile-local bits H ("holes") makes the lanes of a wave walk the
-// lowest non-hole bits; a ds_read_b128 is conflict-free when, inside each of its four 16-lane groups (a 4-dimensional
-// subspace of the five lowest lane bits, MI355X_MICROARCH.md LDS table), the lanes fall on 16 different units.
-// Unswizzled, every hole among bits 0..3 halves the units touched.  Slot bit 4+j is given the column
-//      j mod 5 == 0: 1111,   1: 0001,   2: 0010,   3: 0100,   4: 1000
-// so that ANY five consecutive slot bits map to e0,e1,e2,e3,1111 — the largest set in GF(2)^4 of which every four
-// are independent, and whose one dependency (all five) lies outside the lane groups' subspaces.  With holes the five
-// lowest non-hole bits are not consecutive and some patterns still collide, but far fewer than with the first version
-// of this swizzle (bit 4 only): modelled LDS cycles of the bench schedule's blocks 1.29x -> 1.17x the conflict-free
-// count, and the same on other circuits (the blocks on 4 and 5 tile qubits punch many holes into the low bits).
-// The map is linear over XOR: sw(a | b) = sw(a) ^ sw(b) for disjoint a, b, so per-thread bases are swizzled once and
-// the wave-uniform operand offsets arrive pre-swizzled from the host (TileOp::off / rowoff, engine.cpp slot_off) —
-// no extra instruction per access.
-// fp32 amplitudes (8-byte slots): a ds_read_b64 serves 32 lanes per LDS cycle out of a 256-byte row = 32 units, so the unit is slot
-// bits 0..4 and the columns live in GF(2)^5: slot bit 5+i (i < 5) gets e_i ^ e_(i+1 mod 5), slot bit 10+i the three ones 00111 << i —
-// eight different vectors, none of them a unit vector, so that a block's free bits almost always contain five with independent images
-// for the engine to hand to the five low lane bits (engine.cpp to_tile_op).  (Until late in round 4: slot bit 4 only, which left every
-// higher bit without any image — 48 % of the fp32 kernel's LDS-active cycles were bank conflicts.)
-constexpr int kSwLow = kAmpShift == 3 ? 5 : 4; // slot bits below this are the unit inside a bank row
-__device__ __host__ __forceinline__ uint32_t sw_fold(uint32_t hi) { // hi = slot >> kSwLow (at most 10 bits)
-    if (kAmpShift == 3) {
-        const uint32_t a = hi & 31u, b = (hi >> 5) & 7u;
-        const uint32_t fa = a ^ (((a << 1) | (a >> 4)) & 31u);
-        const uint32_t fb = ((0u - (b & 1u)) & 7u) ^ ((0u - ((b >> 1) & 1u)) & 14u) ^ ((0u - ((b >> 2) & 1u)) & 28u);
-        return fa ^ fb;
-    }
-    const uint32_t f = (hi ^ (hi >> 5) ^ (hi >> 10)) & 31u;
-    return ((f >> 1) & 15u) ^ ((0u - (f & 1u)) & 15u);
-}
-__device__ __forceinline__ uint32_t sw_slot(uint32_t slot) { return slot ^ sw_fold(slot >> kSwLow); }
-__device__ __forceinline__ uint32_t sw_byte(uint32_t byte) { return byte ^ (sw_fold(byte >> (kSwLow + kAmpShift)) << kAmpShift); }
+// LDS layout swizzle of a tile slot index (qsim_internal.h lds_sw_fold: one definition for the kernels and the encoder)
+constexpr int kSwLow = kLdsSwLow<kAmpShift>; // slot bits below this are the unit inside a bank row
+__device__ __forceinline__ uint32_t sw_slot(uint32_t slot) { return slot ^ lds_sw_fold<kAmpShift>(slot >> kSwLow); }
+__device__ __forceinline__ uint32_t sw_byte(uint32_t byte) { return byte ^ (lds_sw_fold<kAmpShift>(byte >> (kSwLow + kAmpShift)) << kAmpShift); }
 
 // LDS access by raw byte address.  k_tile has no static __shared__, so its dynamic LDS region starts at address 0
 // (AMDGPU ABI: dynamic LDS follows the static part) and a tile byte offset IS the LDS address; going through the
@@ -302,7 +274,7 @@ __device__ __forceinline__ void lds_put(uint32_t byte, amp_t v) { *(lds_amp_t *)
 
 // Index of the k-th work item with a zero inserted at bit b (b wave-uniform): x + (x & ~((1<<b)-1)).
 // Op coefficients are stored in the state's precision (the engine rounds once and packs them the way the kernels read them,
-// engine.cpp to_tile_op), and they arrive through scalar loads either way.
+// tile_op.cpp), and they arrive through scalar loads either way.
 typedef const __attribute__((address_space(4))) real_t *ConstCoef;
 typedef const PartRec __attribute__((address_space(4))) *ConstRec;
 
@@ -413,7 +385,7 @@ __device__ __forceinline__ void part_geometry(uint32_t lds_base, const OpHeader 
         part[i] = p < nparts ? p : 0; // waves beyond the last item (tiles smaller than 8 * THREADS) stay in bounds
         // Which tile-local bit each bit of the group index lands on is the engine's choice (nibble a of dwords 2-3 of the header, 15
         // for the item bits that select the part): ANY assignment of the block's free bits to the lanes enumerates the groups, and
-        // the engine picks one under which the lanes of a ds_read_b128 / ds_write_b128 group fall on different banks (to_tile_op).
+        // the engine picks one under which the lanes of a ds_read_b128 / ds_write_b128 group fall on different banks (tile_op.cpp).
         uint32_t x = 0;
 #pragma unroll
         for (int a = 0; a < (B > 3 ? B - 3 : 0); a++) {
@@ -686,10 +658,10 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     ConstOps scales = (ConstOps)(uintptr_t)ops_g; // n_scale tile-uniform factors, then the n_ops blocks
     ConstOps ops = scales + n_scale;
     const uint32_t tid = threadIdx.x;
-    // slot tid + k*THREADS swizzles to (sw(tid) ^ sw_fold(k*THREADS >> 4)) + k*THREADS: the swizzle is linear and the two
+    // slot tid + k*THREADS swizzles to (sw(tid) ^ lds_sw_fold(k*THREADS >> kSwLow)) + k*THREADS: the swizzle is linear and the two
     // parts share no bit (tid < THREADS, a power of two >= 64)
     const uint32_t tid_sw = sw_slot(tid);
-    auto stage_slot = [&](int k) { return (tid_sw ^ sw_fold((uint32_t)(k * THREADS) >> kSwLow)) + (uint32_t)(k * THREADS); };
+    auto stage_slot = [&](int k) { return (tid_sw ^ lds_sw_fold<kAmpShift>((uint32_t)(k * THREADS) >> kSwLow)) + (uint32_t)(k * THREADS); };
     const uint32_t lowmask = (1u << L) - 1u;
     const uint64_t nmask = g.n >= 64 ? ~0ULL : ((1ULL << g.n) - 1ULL);
     const uint64_t outer_mask = nmask & ~(g.high_mask | (uint64_t)lowmask) & ~g.zero_mask; // the tiles to visit: outer bits that may be 1
@@ -1154,7 +1126,7 @@ hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, const TileGeom
         if (threads == 512 || (threads == 0 && kAmpShift == 3)) return QSIM_TILE(13, 512);
         return QSIM_TILE(13, 1024);
 #if QSIM_AMP_SHIFT == 3
-    // unreachable (QSIM_OPT_TILE_BITS stops at 13: to_tile_op packs only 10 free tile bits), but without this instantiation
+    // unreachable (QSIM_OPT_TILE_BITS stops at 13: the op header packs only kLaneNibbles free tile bits), but without this instantiation
     // the compiler lays out the setup of f32 k_tile<13, 512> differently and the fp32 step is 1.2 % slower (DESIGN §3)
     case 14: return QSIM_TILE(14, 1024);
 #endif

@@ -63,14 +63,55 @@ struct TileOp {
     uint8_t selbit[2];    // dword 1: their global index bits, most significant bank bit first
     uint8_t ident;        //   bit v: bank v is the identity
     uint8_t flags;        //   kOpFlagSkips: some class is skipped; kOpFlagClosed: no barrier between reads and writes
-    uint8_t b[8];         // dwords 2-3.  TOP_PART: nibble a of b[0..4] = the free tile-local bit that bit a of a lane's group index walks (15: none; engine.cpp to_tile_op picks bank-conflict-free ones), b[7] = log2 T << 1 | skips << 3 | barrier << 4.  Pair / quad forms: b[0], b[1] = the block's tile-local bits, ascending
+    uint8_t b[8];         // dwords 2-3.  TOP_PART: nibble a of b[0..4] = the free tile-local bit that bit a of a lane's group index walks (kLaneNone: none; tile_op.cpp picks bank-conflict-free ones), b[7] = the kInfo* bits.  Pair / quad forms: b[0], b[1] = the block's tile-local bits, ascending
     uint32_t pad0[4];
     double scale[kMaxBanks][2]; // TOP_SCALE: the factor per bank as (re, im); fp32 states: two floats in the first 8 bytes
     uint32_t pad1[8];
     PartRec rec[kMaxBanks][kMaxParts];
 };
+// TOP_PART header packing (tile_op.cpp writes it, kernels_impl.inc part_geometry / part_prepare read it): kLaneNibbles lane
+// nibbles in b[0..4], kLaneNone for a group-index bit that walks no tile bit, and in b[7] the bits of PartPlan::info the engine
+// decides — log2 T at kInfoLog2TShift, kInfoSkips, kInfoBarrier (a workgroup barrier between the reads and the writes).
+constexpr int kLaneNibbles = 10;
+constexpr uint32_t kLaneNone = 15u;
+constexpr int kInfoLog2TShift = 1;
+constexpr uint32_t kInfoSkips = 8u, kInfoBarrier = 16u;
 static_assert(sizeof(PartRec) == 64 + 512 && offsetof(TileOp, scale) == 32 && offsetof(TileOp, rec) == 128 &&
               sizeof(TileOp) == 128 + kMaxBanks * kMaxParts * sizeof(PartRec), "TileOp layout is shared with the device");
+
+// LDS layout swizzle of a tile slot index: the 16-byte unit inside a 256-byte bank row (slot bits 0..3) is XORed with a
+// linear image of the HIGHER slot bits.  A block on tile-local bits H ("holes") makes the lanes of a wave walk the
+// lowest non-hole bits; a ds_read_b128 is conflict-free when, inside each of its four 16-lane groups (a 4-dimensional
+// subspace of the five lowest lane bits, MI355X_MICROARCH.md LDS table), the lanes fall on 16 different units.
+// Unswizzled, every hole among bits 0..3 halves the units touched.  Slot bit 4+j is given the column
+//      j mod 5 == 0: 1111,   1: 0001,   2: 0010,   3: 0100,   4: 1000
+// so that ANY five consecutive slot bits map to e0,e1,e2,e3,1111 — the largest set in GF(2)^4 of which every four
+// are independent, and whose one dependency (all five) lies outside the lane groups' subspaces.  With holes the five
+// lowest non-hole bits are not consecutive and some patterns still collide, but far fewer than with the first version
+// of this swizzle (bit 4 only): modelled LDS cycles of the bench schedule's blocks 1.29x -> 1.17x the conflict-free
+// count, and the same on other circuits (the blocks on 4 and 5 tile qubits punch many holes into the low bits).
+// The map is linear over XOR: sw(a | b) = sw(a) ^ sw(b) for disjoint a, b, so per-thread bases are swizzled once and
+// the wave-uniform operand offsets arrive pre-swizzled from the host (TileOp::off / rowoff, tile_op.cpp) —
+// no extra instruction per access.
+// fp32 amplitudes (8-byte slots): a ds_read_b64 serves 32 lanes per LDS cycle out of a 256-byte row = 32 units, so the unit is slot
+// bits 0..4 and the columns live in GF(2)^5: slot bit 5+i (i < 5) gets e_i ^ e_(i+1 mod 5), slot bit 10+i the three ones 00111 << i —
+// eight different vectors, none of them a unit vector, so that a block's free bits almost always contain five with independent images
+// for the engine to hand to the five low lane bits (tile_op.cpp).  (Until late in round 4: slot bit 4 only, which left every
+// higher bit without any image — 48 % of the fp32 kernel's LDS-active cycles were bank conflicts.)
+// AMP_SHIFT = log2 of the slot size: 4 (fp64) or 3 (fp32).  The kernels (sw_slot, sw_byte, stage_slot) and the encoder call
+// lds_sw_fold<AMP_SHIFT> directly: a forwarding wrapper in between changes the kernels' instruction schedule.
+template <int AMP_SHIFT> constexpr int kLdsSwLow = AMP_SHIFT == 3 ? 5 : 4; // slot bits below this are the unit inside a bank row
+template <int AMP_SHIFT>
+__host__ __device__ __forceinline__ uint32_t lds_sw_fold(uint32_t hi) { // hi = slot >> kLdsSwLow (at most 10 bits)
+    if (AMP_SHIFT == 3) {
+        const uint32_t a = hi & 31u, b = (hi >> 5) & 7u;
+        const uint32_t fa = a ^ (((a << 1) | (a >> 4)) & 31u);
+        const uint32_t fb = ((0u - (b & 1u)) & 7u) ^ ((0u - ((b >> 1) & 1u)) & 14u) ^ ((0u - ((b >> 2) & 1u)) & 28u);
+        return fa ^ fb;
+    }
+    const uint32_t f = (hi ^ (hi >> 5) ^ (hi >> 10)) & 31u;
+    return ((f >> 1) & 15u) ^ ((0u - (f & 1u)) & 15u);
+}
 
 constexpr int kMaxTileHigh = 10; // high (non-contiguous) qubits per tile
 struct TileGeom {
@@ -81,6 +122,15 @@ struct TileGeom {
     int32_t high[kMaxTileHigh]; // global bit of tile-local bit L+j; any order (the scheduler emits ascending, the engine may reorder)
     int32_t n_scale;            // leading entries of the pass's op list that are TOP_SCALE factors, not blocks
 };
+
+// index bits [0, n) of a register of n qubits
+inline uint64_t index_mask(int n) { return n >= 64 ? ~0ULL : ((1ULL << n) - 1ULL); }
+// the global index bits a tile of geometry g holds
+inline uint64_t tile_mask(const TileGeom &g) {
+    uint64_t m = (1ULL << g.low_bits) - 1ULL;
+    for (int j = 0; j < g.n_high; j++) m |= 1ULL << g.high[j];
+    return m;
+}
 
 // Output permutation of a tile pass that also does the re-layout of an exchange (the pack): the amplitude read at index x is
 // written at index  perm(x) = sum_i ((x & seg[i]) >> i)  |  sum_j (bit sel[j] of x) << to[j]  |  konst  of the OUTPUT buffer.

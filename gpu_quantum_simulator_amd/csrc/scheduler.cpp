@@ -593,7 +593,7 @@ uint64_t Scheduler::tile_pass(const std::vector<FusedOp> &ops, uint64_t hset, co
     const uint64_t tmask = lowmask | high;
     if (p.blocks.empty()) return 0; // every block was the identity: nothing is launched, nothing changes
     if (prefer != ~0ULL) { // the state's support is known: the pass visits the tiles inside support | tile
-        const uint64_t all = cfg_.n >= 64 ? ~0ULL : ((1ULL << cfg_.n) - 1ULL);
+        const uint64_t all = index_mask(cfg_.n);
         p.visited = 1.0 / (double)(1ULL << (cfg_.n - __builtin_popcountll((prefer | tmask) & all)));
     }
     sink(std::move(p));
@@ -614,7 +614,7 @@ void Scheduler::build_passes(const PassSink &sink) {
     const int L = std::min(cfg_.tile_low_bits, B);
     const int kmax = std::min(B - L, (int)kMaxTileHigh);
     const uint64_t lowmask = (1ULL << L) - 1ULL;
-    const uint64_t all = cfg_.n >= 64 ? ~0ULL : ((1ULL << cfg_.n) - 1ULL);
+    const uint64_t all = index_mask(cfg_.n);
     const size_t m = closed_.size();
     std::vector<uint64_t> qm(m), must(m); // all qubits of a block (ordering); the ones that have to be tile qubits
     for (size_t i = 0; i < m; i++) {

@@ -94,6 +94,11 @@ struct TileBlock {
     bool classes_feasible() const; // the same answer as classes() without building the layout (no heap: merge_blocks asks often)
 };
 
+// tile_op.cpp: the block as the TileOp k_tile reads under geometry g.  false when a qubit is on the wrong side of the tile or the
+// block cannot be expressed (Scheduler::merge_blocks never produces such a block).  f32: the state holds fp32 amplitudes — 8-byte
+// LDS slots, coefficients rounded once, here, and stored as the float pairs the fp32 kernels consume (kernels_impl.inc coef_t).
+bool to_tile_op(const TileGeom &g, const TileBlock &blk, TileOp &t, bool f32 = false);
+
 struct Pass {
     int kclass = 0;           // QSIM_K_*
     std::vector<FusedOp> ops;      // the one op of a single-op pass; empty for QSIM_K_TILE
