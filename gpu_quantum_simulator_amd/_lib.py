@@ -85,6 +85,10 @@ SIGNATURES = {
     "qsim_read": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
     "qsim_write": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
     "qsim_norm2": (c_int, [c_void_p, _DP]),
+    "qsim_expect_paulis": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_long, _DP]),
+    "qsim_pauli_sweeps": (c_int, [POINTER(c_uint64), c_long, POINTER(c_long)]),
+    "qsim_pauli_terms_per_sweep": (c_int, []),
+    "qsim_cluster_expect_paulis": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_long, _DP]),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

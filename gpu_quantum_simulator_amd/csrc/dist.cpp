@@ -1111,6 +1111,57 @@ extern "C" int qsim_cluster_norm2(qsim_cluster *c, double *out) {
     return QSIM_OK;
 }
 
+// <psi|P_t|psi> on the sharded state.  Masks arrive in logical qubits; mapped through `pos` they split into local index bits
+// (< m) and shard-id bits.  Z on shard-id bits is a sign per shard.  X on shard-id bits (x_rank) pairs shard r with shard
+// r ^ x_rank: over the whole register the sum runs over the indices with the highest bit of x clear, and that bit is then a
+// shard-id bit — so the shard of each pair that has it clear sweeps ALL its local indices against its partner's buffer, and
+// the other one does nothing.  With x_rank == 0 every shard sweeps its own half (highest LOCAL bit of x clear).  Either way
+// every amplitude is read once.  A partner buffer is only readable in place when both shards are on one device.
+extern "C" int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out) {
+    if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
+    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: negative term count");
+    if (num_terms == 0) return QSIM_OK;
+    if (!x_masks || !z_masks || !out) return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: NULL argument");
+    const uint64_t nmask = qsim::index_mask(c->n);
+    std::vector<uint64_t> X((size_t)num_terms), Z((size_t)num_terms);
+    for (long t = 0; t < num_terms; t++) {
+        if ((x_masks[t] | z_masks[t]) & ~nmask)
+            return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: term %ld names a qubit outside the %d-qubit register", t, c->n);
+        X[(size_t)t] = physical_index(c, x_masks[t]);
+        Z[(size_t)t] = physical_index(c, z_masks[t]);
+        if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)
+            return cfail(QSIM_ERR_ARG,
+                         "qsim_cluster_expect_paulis: term %ld has X or Y on a qubit that currently selects the shard, and the shards are on "
+                         "different devices: reading a partner shard across devices is not implemented",
+                         t);
+    }
+    // a shard's buffer is about to be read from another shard's stream: everything queued must have run, lazily held states
+    // must have been written
+    for (qsim_state *s : c->shard)
+        if (!qsim_device_ptr(s) || qsim_sync(s) != QSIM_OK) return cfail(QSIM_ERR_DEVICE, "%s", qsim_last_error());
+    // terms by x_rank, in order of first appearance
+    std::vector<uint64_t> ranks_x;
+    for (long t = 0; t < num_terms; t++)
+        if (std::find(ranks_x.begin(), ranks_x.end(), X[(size_t)t] >> c->m) == ranks_x.end()) ranks_x.push_back(X[(size_t)t] >> c->m);
+    for (long t = 0; t < num_terms; t++) out[t] = 0.0;
+    std::vector<uint64_t> gx, gz;
+    std::vector<long> gt;
+    std::vector<double> part;
+    for (int r = 0; r < c->P; r++)
+        for (const uint64_t xr : ranks_x) {
+            if (xr != 0 && (((uint64_t)r >> (63 - __builtin_clzll(xr))) & 1ULL)) continue; // its partner counts the pair
+            gx.clear(), gz.clear(), gt.clear();
+            for (long t = 0; t < num_terms; t++)
+                if ((X[(size_t)t] >> c->m) == xr) gx.push_back(X[(size_t)t]), gz.push_back(Z[(size_t)t]), gt.push_back(t);
+            part.assign(gt.size(), 0.0);
+            const void *partner = xr ? qsim_state_buffer(c->shard[(size_t)((uint64_t)r ^ xr)]) : nullptr;
+            const int rc = qsim::expect_paulis_shard(c->shard[(size_t)r], partner, (uint64_t)r, gx.data(), gz.data(), (long)gt.size(), part.data());
+            if (rc) return cfail(rc, "shard %d: %s", r, qsim_last_error());
+            for (size_t i = 0; i < gt.size(); i++) out[gt[i]] += part[i];
+        }
+    return QSIM_OK;
+}
+
 extern "C" int qsim_cluster_exchange_stats(const qsim_cluster *c, uint64_t *exchanges, double *bytes_per_shard) {
     if (!c) return QSIM_ERR_ARG;
     if (exchanges) *exchanges = c->exchanges;

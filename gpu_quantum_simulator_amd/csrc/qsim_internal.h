@@ -183,5 +183,29 @@ hipError_t launch_gather_masked(const LaunchCfg &cfg, const void *v, bool f32, u
 hipError_t launch_pack(const LaunchCfg &cfg, const void *in, void *out, void *const *blocks, bool f32, int n, const int *bits, int p, uint32_t skip_blocks = 0,
                        uint64_t zero_mask = 0);
 
+// ---- expect.hip: Pauli-string expectation sweeps (read-only; DESIGN "Expectation values") ----------------------------------
+constexpr int kMaxTermsPerSweep = 32; // slots of the largest k_expect instantiation; qsim_pauli_terms_per_sweep() is what a call uses
+constexpr int kExpectGrid = 1024;     // workgroups of a sweep at most = rows of partial sums (4 per CU)
+constexpr size_t kExpectPartialDoubles = (size_t)kExpectGrid * kMaxTermsPerSweep;
+// One sweep: `count` strings that share x.  `full`: every index j of the buffer counts (a shard whose partner buffer is another
+// shard's: the pair's highest x bit is a rank bit); otherwise, for x != 0, only the j with the highest bit of x clear.
+struct ExpectSweep {
+    uint64_t x;
+    bool full;
+    int count;
+    uint64_t z[kMaxTermsPerSweep];
+    uint32_t im_mask; // bit k: term k takes Im(conj(psi_j^x) psi_j) instead of Re
+};
+int expect_slots(int count); // term slots of the instantiation a sweep of `count` terms runs in (1, 8, 16, 32)
+// d_out[k] = sum_j s_k(j) |a_j|^2 (x == 0 and not full) or sum_j s_k(j) Re/Im(conj(b_(j^x)) a_j), for k < expect_slots(count);
+// d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.
+hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, bool f32, int n, const ExpectSweep &sw, double *d_partial,
+                         double *d_out);
+// engine.cpp: <P_t> restricted to one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s)
+// bits of the masks; every term has the same x above them (x_rank).  x_rank != 0: `partner` is the buffer of shard
+// rank ^ x_rank (quiescent, materialised) and every local index is swept; NULL: the state itself.  Adds nothing up across shards.
+int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms,
+                        double *out);
+
 } // namespace qsim
 #endif

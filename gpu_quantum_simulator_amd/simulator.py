@@ -149,6 +149,30 @@ class Circuit:
             pass
 
 
+
+def _pauli_term_masks(paulis, num_q: int):
+    """Distinct strings of `paulis` as mask arrays, and for every entry the position of its string among them."""
+    from ctypes import c_uint64
+    from .pauli import pauli_masks
+    index, where = {}, []
+    for text in paulis:
+        where.append(index.setdefault(pauli_masks(text, num_q), len(index)))
+    xs = np.array([m[0] for m in index], dtype=np.uint64)
+    zs = np.array([m[1] for m in index], dtype=np.uint64)
+    up = ctypes.POINTER(c_uint64)
+    return xs, zs, xs.ctypes.data_as(up), zs.ctypes.data_as(up), np.array(where, dtype=np.intp)
+
+
+def _weighted_sum(terms, evaluate):
+    """sum_t c_t <P_t> for (coefficient, string) pairs: a float when every coefficient is real, else a complex."""
+    terms = list(terms)
+    coeffs = [c for c, _ in terms]
+    values = evaluate([p for _, p in terms])
+    if all(isinstance(c, (int, float, np.integer, np.floating)) for c in coeffs):
+        return float(np.dot(np.asarray(coeffs, dtype=np.float64), values))
+    return complex(np.dot(np.asarray(coeffs, dtype=np.complex128), values))
+
+
 class Simulator:
     """One state vector resident on one GPU."""
 
@@ -332,6 +356,19 @@ class Simulator:
         check(_lib.load().qsim_norm2(self._h, byref(v)))
         return v.value
 
+    def expectation_terms(self, paulis) -> np.ndarray:
+        """<psi|P|psi> for every Pauli string of `paulis` ("X0 Z3 Y17", see pauli_masks), computed on the device
+        (qsim_expect_paulis): one float64 per string, in the caller's order.  Equal strings are evaluated once."""
+        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
+        out = np.empty(xs.size, dtype=np.float64)
+        check(_lib.load().qsim_expect_paulis(self._h, xp, zp, xs.size, _dp(out)))
+        return out[where]
+
+    def expectation(self, terms):
+        """sum_t c_t <P_t> for an iterable of (coefficient, Pauli string): <psi|H|psi> of H = sum_t c_t P_t.  A float when
+        every coefficient is real, else a complex."""
+        return _weighted_sum(terms, self.expectation_terms)
+
     @property
     def device_ptr(self) -> int:
         return int(_lib.load().qsim_device_ptr(self._h) or 0)
@@ -427,6 +464,17 @@ class Cluster:
         v = c_double()
         self._check(_lib.load().qsim_cluster_norm2(self._h, byref(v)))
         return v.value
+
+    def expectation_terms(self, paulis) -> np.ndarray:
+        """Simulator.expectation_terms on the sharded state (qsim_cluster_expect_paulis); strings name LOGICAL qubits."""
+        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
+        out = np.empty(xs.size, dtype=np.float64)
+        self._check(_lib.load().qsim_cluster_expect_paulis(self._h, xp, zp, xs.size, _dp(out)))
+        return out[where]
+
+    def expectation(self, terms):
+        """Simulator.expectation on the sharded state."""
+        return _weighted_sum(terms, self.expectation_terms)
 
     def sample(self, randoms) -> np.ndarray:
         """measurement() (quantum_simulator.c:270-283) on the sharded state, indices in logical order."""

@@ -152,6 +152,19 @@ int qsim_sync(qsim_state *s);  /* flush, then wait for the stream */
 int qsim_read(qsim_state *s, uint64_t first, uint64_t count, double *out_re_im);
 int qsim_write(qsim_state *s, uint64_t first, uint64_t count, const double *in_re_im);
 int qsim_norm2(qsim_state *s, double *out); /* sum |a|^2 computed on the device */
+/* ---- expectation values of Pauli strings, computed on the device (new: the reference has no observables) ----
+ * A string on the register is two masks: bit q of x_mask set where it has X or Y on qubit q, bit q of z_mask where it has Z or Y
+ * (both: Y).  out[t] = <psi|P_t|psi>, a real number, for num_terms strings; coefficients of a Hamiltonian are the caller's.
+ * Launches queued gates first; does not modify the state.  Terms are grouped by x_mask: all strings with one x_mask share the
+ * loads and the pair products, so each group costs ceil(size / K) read-only sweeps of the state, K = qsim_pauli_terms_per_sweep().
+ * The sums are fp64 in both precisions and are formed in a fixed order: equal calls return equal bits.  One device-to-host
+ * copy and one stream synchronise per 128 sweeps.  The identity (x = z = 0) is legal and gives the squared norm;
+ * num_terms == 0 succeeds and writes nothing.  QSIM_ERR_ARG: NULL arguments with num_terms > 0, a mask bit at or above the
+ * register's qubit count, a negative num_terms. */
+int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out);
+/* Host only, no device: how many sweeps the call above makes for these terms. */
+int qsim_pauli_sweeps(const uint64_t *x_masks, long num_terms, long *sweeps);
+int qsim_pauli_terms_per_sweep(void); /* K: 32 ("Expectation values": the measured choice among 8, 16, 32) */
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
@@ -301,6 +314,12 @@ int qsim_cluster_sync(qsim_cluster *c);
 int qsim_cluster_plan(qsim_cluster *c, const qsim_circuit *circuit, int max_candidates, double budget_ms);
 int qsim_cluster_read(qsim_cluster *c, uint64_t logical_first, uint64_t count, double *out_re_im);
 int qsim_cluster_norm2(qsim_cluster *c, double *out);
+/* qsim_expect_paulis on a sharded state; masks are in LOGICAL qubits and are mapped through the cluster's qubit map.  Z on a
+ * qubit that is a shard-id bit is a sign per shard; X or Y there pairs shard r with shard r ^ x_rank, whose buffer is read in
+ * place.  That needs every shard on ONE device (virtual shards): with shards on different devices such a term is refused with
+ * QSIM_ERR_ARG — a path that reads a peer's buffer or copies it over is missing — and terms whose X and Y sit on local qubits
+ * work on any placement.  Every shard is flushed and its stream waited for first; per-shard results are added in shard order. */
+int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out);
 /* qsim_sample for a sharded state: basis indices in LOGICAL order for random numbers in [0,1] (measurement(),
  * quantum_simulator.c:270-283), whatever qubit map the exchanges left behind.  Every shard forms the |a|^2 sums of the
  * logical 2^12-amplitude blocks it holds a part of on its own device (qsim_block_prob_masked); the host adds the P
