@@ -1,16 +1,22 @@
 """fp32 state (qsim_create_f32): the precision of the reference's CUDA variants (cuFloatComplex, naive.cu:38).
 
 NOT the parity configuration (that is fp64 within 1e-10, tests/test_gpu_parity.py).  The same kernels are instantiated for
-float amplitudes; these tests hold them to the fp64 oracle within fp32 rounding.  Tolerance: each gate adds at most a few
-ulp(fp32) = 6e-8 relative per amplitude; over a few hundred gates on unit-norm states 2e-5 abs is a loose bound and far
-below any indexing error (which shows up at the 1e-2..1 level).
+float amplitudes; these tests hold them to the fp64 truth with the criterion of tests/fp32_ref.py: the relative 2-norm error
+may be at most C = 8 times that of a gate-by-gate complex64 replay of the same gates (floor 2^-24).  That tells fp32
+arithmetic from anything coarser: coefficients rounded to half precision sit thousands of times above it.
+
+TOL32 = 2e-5 abs is kept as a second, much weaker check.  It catches indexing errors (1e-2..1) but NOT precision loss: at
+n = 20..22 the RMS amplitude is 5e-4..1e-3, so 2e-5 abs admits 2-4 % error per amplitude, and an engine with half-precision
+coefficients would pass it at those sizes.  Run with -s to see each case's rel_err(got), rel_err(ref32) and their ratio.
 """
 import os
 
 import numpy as np
 import pytest
 
-from gpu_quantum_simulator_amd import Simulator, circuits, run_qasm
+import fp32_ref
+from fp32_ref import check_fp32, gate_list, replay, report
+from gpu_quantum_simulator_amd import Circuit, Simulator, circuits, run_qasm
 from helpers import random_unitary
 
 pytestmark = pytest.mark.gpu
@@ -63,23 +69,32 @@ def test_tile_bits_14_and_retired_options_rejected(precision):
                                   "rand_n12_clifford_t_physical"])
 def test_golden_fixtures_fp32(golden_dir, name, fuse):
     want = np.load(os.path.join(golden_dir, name + ".npy"), allow_pickle=False).view(np.complex128).reshape(-1)
-    got = run_qasm(os.path.join(golden_dir, name + ".qasm"), fuse=fuse, precision=32)
+    path = os.path.join(golden_dir, name + ".qasm")
+    got = run_qasm(path, fuse=fuse, precision=32)
+    c = Circuit.from_file(path)
+    report(f"golden {name} fuse={fuse}", check_fp32(got, want, replay(c.num_qubits, [c.gate(i) for i in range(len(c))])))
     assert np.max(np.abs(got - want)) < TOL32
 
 
 def test_every_target_bit_and_pair_fp32(oracle):
-    """Per-gate kernels (fuse=0): dense/diagonal 1q on every bit, cx on every ordered pair, against the oracle."""
+    """Per-gate kernels (fuse=0): dense/diagonal 1q on every bit, cx on every ordered pair, against the oracle.  Compared from
+    the start the state holds after the write (rounded to fp32); cx only moves data and is bit-exact."""
     n = 13
     rng = np.random.default_rng(5)
     with Simulator(n, fuse=0, precision=32) as sim:
         for q in range(n):
-            for U in (random_unitary(2, rng), np.diag(np.exp(1j * rng.uniform(0, 6.28, 2)))):
+            for kind, U in (("dense", random_unitary(2, rng)), ("diag", np.diag(np.exp(1j * rng.uniform(0, 6.28, 2))))):
                 s = _rand_state(n, 300 + q)
+                s32 = s.astype(np.complex64)
                 sim.write(s)
                 sim.apply_1q(U, q)
+                got = sim.read()
                 want = s.copy()
                 oracle.apply_1q(want, n, U.T, q)
-                assert np.max(np.abs(sim.read() - want)) < TOL32, q
+                assert np.max(np.abs(got - want)) < TOL32, q
+                want32 = s32.astype(np.complex128)
+                oracle.apply_1q(want32, n, U.T, q)
+                report(f"1q {kind} q={q}", check_fp32(got, want32, replay(n, [("u1", q, U)], start=s32)))
         for c in range(n):
             for t in range(n):
                 if c == t:
@@ -87,52 +102,50 @@ def test_every_target_bit_and_pair_fp32(oracle):
                 s = _rand_state(n, 400 + c * n + t)
                 sim.write(s)
                 sim.apply_cx(c, t)
+                got = sim.read()
                 want = s.copy()
                 oracle.apply_cx(want, n, c, t)
-                assert np.max(np.abs(sim.read() - want)) < TOL32, (c, t)
+                assert np.max(np.abs(got - want)) < TOL32, (c, t)
+                want32 = s.astype(np.complex64).astype(np.complex128)
+                oracle.apply_cx(want32, n, c, t)
+                assert np.array_equal(got, want32), (c, t)
 
 
-@pytest.mark.parametrize("n,depth,seed,vocab,opts", [
-    (14, 400, 31, "all", {}),
-    (16, 500, 32, "clifford_t", {}),
-    (18, 400, 33, "all", {"tile_bits": 13, "tile_low_bits": 6}),
-    (20, 300, 34, "all", {"tile_bits": 11, "tile_low_bits": 5, "tile_max_ops": 3}),
-    (19, 300, 35, "all", {"tile_bits": 9, "tile_low_bits": 2}),
-    (20, 300, 36, "all", {"grid_cap": 64}),
-    (22, 400, 37, "all", {}),
-])
+@pytest.mark.parametrize("n,depth,seed,vocab,opts", [(*spec, opts) for spec, opts in fp32_ref.RANDOM_CIRCUITS])
 def test_random_circuits_fp32(oracle, tmp_path, n, depth, seed, vocab, opts):
+    spec = (n, depth, seed, vocab)
     path = circuits.random_circuit_file(str(tmp_path / "c.qasm"), n, depth, seed, vocab)
     _, want, _, _ = oracle.run_qasm(path)
     got = run_qasm(path, fuse=3, precision=32, **opts)
+    report(f"random {spec} {opts}", check_fp32(got, want, replay(n, gate_list(*spec))))
     assert np.max(np.abs(got - want)) < TOL32
 
 
 @pytest.mark.parametrize("order_seed", [1, 2])
 def test_tile_bit_order_fp32(oracle, tmp_path, order_seed):
     """Shuffled tile-bit orders (QSIM_OPT_DEBUG_TILE_ORDER) through the fp32 instantiation of the tile kernel."""
-    n = 17
-    path = circuits.random_circuit_file(str(tmp_path / "c.qasm"), n, 500, 91, "all")
+    spec = fp32_ref.TILE_ORDER_CIRCUIT
+    path = circuits.random_circuit_file(str(tmp_path / "c.qasm"), *spec)
     _, want, _, _ = oracle.run_qasm(path)
     got = run_qasm(path, fuse=3, precision=32, debug_tile_order=order_seed)
+    report(f"tile order {order_seed} {spec}", check_fp32(got, want, replay(spec[0], gate_list(*spec))))
     assert np.max(np.abs(got - want)) < TOL32
 
 
 def test_randomised_geometry_sweep_fp32(oracle, tmp_path):
-    rng = np.random.default_rng(77)
-    for case in range(30):
-        n = int(rng.integers(2, 20))
-        depth = int(rng.integers(20, 300))
-        tile_bits = int(rng.integers(8, 14))
-        tile_low = int(rng.integers(max(2, tile_bits - 10), min(6, tile_bits - 2) + 1))
-        opts = {"tile_bits": tile_bits, "tile_low_bits": tile_low, "tile_max_ops": int(rng.integers(1, 40)),
-                "tile_pad_from": int(rng.integers(-1, 20))}
-        fuse = int(rng.choice([0, 1, 2, 3, 3, 3]))
-        path = circuits.random_circuit_file(str(tmp_path / f"g{case}.qasm"), n, depth, 7000 + case, "all")
+    """Seeded sweep over register sizes and every engine option (fp32_ref.geometry_sweep_cases: tile size, low bits, ops per
+    pass, padding start, threads, grid cap), each case against the oracle."""
+    for case, spec, fuse, opts in fp32_ref.geometry_sweep_cases():
+        n, depth, seed, vocab = spec
+        path = circuits.random_circuit_file(str(tmp_path / f"g{case}.qasm"), n, depth, seed, vocab)
         _, want, _, _ = oracle.run_qasm(path)
         got = run_qasm(path, fuse=fuse, precision=32, **opts)
         err = float(np.max(np.abs(got - want)))
         assert err < TOL32, (case, n, depth, fuse, opts, err)
+        try:
+            report(f"sweep {case} {spec} fuse={fuse} {opts}", check_fp32(got, want, replay(n, gate_list(*spec))))
+        except AssertionError as e:
+            raise AssertionError(f"case {case}: {spec} fuse={fuse} {opts}: {e}") from None
 
 
 def test_dense_2q_and_sparse_blocks_fp32():
@@ -143,10 +156,14 @@ def test_dense_2q_and_sparse_blocks_fp32():
         for hi, lo in [(13, 0), (5, 2), (12, 7), (1, 0), (9, 3)]:
             U = random_unitary(4, rng)
             s = _rand_state(n, 500 + hi)
+            s32 = s.astype(np.complex64)
             sim.write(s)
             sim.apply_2q(U, hi, lo)
+            got = sim.read()
             want = np_apply_2q(s.copy(), n, U, hi, lo)
-            assert np.max(np.abs(sim.read() - want)) < TOL32, (hi, lo)
+            assert np.max(np.abs(got - want)) < TOL32, (hi, lo)
+            want32 = np_apply_2q(s32.astype(np.complex128), n, U, hi, lo)
+            report(f"2q ({hi}, {lo})", check_fp32(got, want32, replay(n, [("u2", hi, lo, U)], start=s32)))
 
 
 def test_sampling_and_pack_fp32():
