@@ -201,7 +201,7 @@ int expect_slots(int count); // term slots of the instantiation a sweep of `coun
 // d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.
 hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, bool f32, int n, const ExpectSweep &sw, double *d_partial,
                          double *d_out);
-// engine.cpp: <P_t> restricted to one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s)
+// readout.cpp: <P_t> restricted to one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s)
 // bits of the masks; every term has the same x above them (x_rank).  x_rank != 0: `partner` is the buffer of shard
 // rank ^ x_rank (quiescent, materialised) and every local index is swept; NULL: the state itself.  Adds nothing up across shards.
 int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms,
