@@ -458,7 +458,8 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
     LaunchCfg cfg{s->stream, s->grid_cap};
     const FusedOp &op = p.ops[0];
     hipError_t e = hipSuccess;
-    double visited = 1.0; // fraction of the tiles a tile pass works on
+    double visited = 1.0;    // fraction of the tiles a tile pass works on = the share of the register it writes
+    double read_share = 1.0; // the share of the register it reads
     switch (p.kclass) {
     case QSIM_K_GATE1:
     case QSIM_K_GATE1_LO: {
@@ -491,18 +492,21 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
     }
     case QSIM_K_TILE: {
         TileGeom geom = cached_geom ? *cached_geom : p.geom;
-        if (!cached_geom) order_tile_bits(s, geom);
-        if (geom_out) *geom_out = geom;
-        uint64_t hm = 0, oc = 0;
-        for (int j = 0; j < geom.n_high; j++) { hm |= 1ULL << geom.high[j]; oc |= (uint64_t)geom.high[j] << (5 * j); }
         // the part of the register this pass has to visit (qsim_state::support)
         const uint64_t nmask = index_mask(s->n);
         const uint64_t tmask = tile_mask(geom);
         uint64_t zero_mask = 0;
         if (s->sparse_start && from_zero_ket) zero_mask = nmask;
         else if (s->partial) zero_mask = nmask & ~s->support;
+        // (a cached plan was recorded on the same support: its order has the new bits where this one puts them)
+        if (!cached_geom) order_tile_bits(s, geom, from_zero_ket ? 0 : zero_mask);
+        if (geom_out) *geom_out = geom;
+        uint64_t hm = 0, oc = 0;
+        for (int j = 0; j < geom.n_high; j++) { hm |= 1ULL << geom.high[j]; oc |= (uint64_t)geom.high[j] << (5 * j); }
         visited = 1.0 / (double)(1ULL << __builtin_popcountll(zero_mask & ~tmask));
-        LaunchScope scope(s, p.kclass, (int)p.blocks.size(), hm, oc, visited);
+        // of a visited tile only the slots inside the support are read (k_tile SPARSE); a generating pass reads nothing
+        read_share = from_zero_ket ? 0.0 : visited / (double)(1ULL << __builtin_popcountll(zero_mask & tmask));
+        LaunchScope scope(s, p.kclass, (int)p.blocks.size(), hm, oc, visited, read_share);
         if (scope.on && s->profile >= 2) // what the blocks look like, for the pass-time model's data (tools/pass_model_data.py); host work per launch: only on request
             for (size_t k = (size_t)geom.n_scale; k < p.blocks.size(); k++) {
                 const TileBlock &b = p.blocks[k];
@@ -530,7 +534,7 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
     }
     if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     const double scale = s->f32 ? 0.5 : 1.0; // the scheduler prices passes for 16-byte amplitudes
-    account(s, p.kclass, scale * visited * (from_zero_ket ? p.bytes / 2 : p.bytes)); // a generating pass only writes
+    account(s, p.kclass, scale * p.bytes / 2 * (visited + read_share)); // half of a pass's bytes are reads, half writes
     return QSIM_OK;
 }
 

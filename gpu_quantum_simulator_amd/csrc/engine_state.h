@@ -38,9 +38,10 @@ struct ProfEvent {
     uint64_t high_mask;
     uint64_t order_code; // tile passes: the high tile bits in tile-local order, 5 bits each, lowest first
     double visited;      // tile passes: fraction of the register's tiles the pass works on (the state's support)
+    double read_share;   // tile passes: fraction of the register the pass reads (the slots of those tiles inside the support before it)
     std::vector<uint8_t> forms; // tile passes: one byte per block (qsim_launch_log_blocks)
 };
-struct LaunchRec { int kclass, n_ops; uint64_t high_mask; double ms; uint64_t order_code; double visited; std::vector<uint8_t> forms; };
+struct LaunchRec { int kclass, n_ops; uint64_t high_mask; double ms; uint64_t order_code; double visited, read_share; std::vector<uint8_t> forms; };
 
 // Everything a schedule depends on: the options that shape it, the state's support, the QSIM_SCHED_* overrides and the
 // gates themselves.  A cached plan is only replayed for a queue whose identity EQUALS the one it was built from, field by
@@ -180,7 +181,10 @@ bool trace_pack(); // QSIM_TRACE_PACK is set: stderr says why a re-layout got a 
 
 // ---- planning.cpp ----------------------------------------------------------------------------------------------------------
 // Counts the tile pass and gives its high bits the measured order, if there is one (or the probe order of QSIM_OPT_DEBUG_TILE_ORDER).
-void order_tile_bits(qsim_state *s, TileGeom &g);
+// zero_mask: the index bits the state is zero in when the pass starts (0: a full or a generating pass) — the high bits among
+// them end up topmost (place_new_bits), where the kernel drops their loads.
+void order_tile_bits(qsim_state *s, TileGeom &g, uint64_t zero_mask = 0);
+void place_new_bits(TileGeom &g, uint64_t zero_mask);
 uint64_t wisdom_epoch(); // changes whenever a measured order or schedule choice does: cached plans carry the one they were built under
 bool have_sched_hints();
 void apply_sched_hint(uint64_t key, SchedConfig &cfg); // the schedule choice remembered under this key, if any
@@ -194,9 +198,10 @@ struct LaunchScope { // records a start/stop pair around one launch when profili
     qsim_state *s;
     ProfEvent pe{};
     bool on;
-    LaunchScope(qsim_state *st, int kclass, int n_ops = 1, uint64_t high_mask = 0, uint64_t order_code = 0, double visited = 1.0) : s(st), on(st->profile != 0) {
+    LaunchScope(qsim_state *st, int kclass, int n_ops = 1, uint64_t high_mask = 0, uint64_t order_code = 0, double visited = 1.0, double read_share = 1.0) : s(st), on(st->profile != 0) {
         if (on) {
             pe.visited = visited;
+            pe.read_share = read_share;
             pe.kclass = kclass;
             pe.n_ops = n_ops;
             pe.high_mask = high_mask;

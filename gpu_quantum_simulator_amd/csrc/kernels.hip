@@ -16,6 +16,7 @@
 //                                                    quantum_simulator_preproces_constant.cu:169-178 — rebuilt
 //                                                    as a full-grid, LDS-tiled pass instead of one block
 // Index arithmetic is 64-bit throughout (the reference's `int th_id` stops at n = 31, naive.cu:74).
+#include <type_traits>
 #include "qsim_internal.h"
 
 namespace qsim {

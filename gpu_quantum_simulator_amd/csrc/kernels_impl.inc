@@ -239,7 +239,9 @@ struct TileDev {
     uint64_t high_mask; // global bit positions of tile-local bits L..B-1 (as a set)
     uint64_t zero_mask; // index bits the state is known to be |0> in (qsim_state::support): amplitudes with such a bit set are
                         // zero BY DEFINITION — their memory has never been written — so tiles with one in their base index are
-                        // not visited at all and, inside the visited tiles, such slots are staged in as zero
+                        // not visited at all and, inside the visited tiles, such slots are staged in as zero WITHOUT being loaded
+    int32_t live_regs;  // k_tile<SPARSE>: registers 0 .. live_regs-1 of a lane hold slots inside the support; the others sit on tile bits
+                        // in zero_mask that the engine placed in the topmost register role (place_new_bits) and are never loaded
     int8_t high[16];    // ... and in order: tile-local bit L+j is global bit high[j].  ANY order: which tile bits the lanes of a
                         // wave, the waves of a workgroup and the registers of a lane walk is the engine's choice
 };
@@ -645,7 +647,15 @@ __device__ __forceinline__ uint64_t pack_perm(const PackMap &pm, uint64_t x) {
     return o;
 }
 
-template <int B, int THREADS, bool PACK = false>
+// SPARSE: the variant for a pass over a partially written state (TileDev::zero_mask != 0, not generating).  Slots of a visited
+// tile whose index has a zero_mask bit are zero by definition, and their loads are never issued: the engine puts the tile bits
+// that are new to the support into the topmost register role, so the live slots of every lane are its first live_regs
+// registers and the fetch is ONE wave-uniform choice between straight-line batches of APT, APT/2, APT/4 ... loads (a
+// per-element "load or zero" select would make the compiler branch around each load and wait for vmcnt(0) per element, the
+// previous tile's stores included).  New bits that are not there (more than the register role holds, a shuffled order, the low
+// bits, tiles with tail guards) mask whole lanes off for the batch, or are loaded and zeroed as before: right, not fast, and only
+// the sub-millisecond passes come that way.  Full sweeps run the SPARSE = false instantiation, which carries none of this.
+template <int B, int THREADS, bool PACK = false, bool SPARSE = false>
 __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(amp_t *v, amp_t *vout, TileDev g, const TileOp *__restrict__ ops_g,
                                                   int n_ops, uint64_t ntiles, int tiles_per_wg, int n_scale, PackMap pm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -719,10 +729,28 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     }
     amp_t pf[APT];
     const bool generate = g.from_zero_ket != 0; // wave-uniform
+    // SPARSE: the lane's own index bits (lane and wave role, low bits) lie inside the support
+    const bool sparse_lane_ok = !SPARSE || ((lane_off >> kAmpShift) & g.zero_mask) == 0;
     auto fetch = [&](uint64_t tb) {
         if (generate) { // |0...0>: amplitude 1 at global index 0 (tile base 0, slot 0), nothing to read
 #pragma unroll
             for (int k = 0; k < APT; k++) pf[k] = amp_t{(real_t)((tb == 0 && k == 0 && tid == 0) ? g.amp0 : 0.0), (real_t)0};
+            return;
+        }
+        if constexpr (SPARSE && FULL) {
+            // exclusive branches, each a straight-line batch that writes every register exactly once (a register that one branch
+            // loads and another one zeroes afterwards would have to wait for the load: vmcnt(0))
+            auto batch = [&](auto live_c) {
+                constexpr int LIVE = decltype(live_c)::value;
+#pragma unroll
+                for (int k = 0; k < APT; k++) pf[k] = k < LIVE ? *elem_ptr(tb, k) : amp_t{(real_t)0, (real_t)0};
+            };
+            const int live = g.live_regs; // wave-uniform
+            if (!sparse_lane_ok) batch(std::integral_constant<int, 0>{}); // masked lanes generate no requests
+            else if (APT >= 2 && live == APT / 2) batch(std::integral_constant<int, (APT >= 2 ? APT / 2 : APT)>{});
+            else if (APT >= 4 && live == APT / 4) batch(std::integral_constant<int, (APT >= 4 ? APT / 4 : APT)>{});
+            else if (APT >= 8 && live == APT / 8) batch(std::integral_constant<int, (APT >= 8 ? APT / 8 : APT)>{});
+            else batch(std::integral_constant<int, APT>{});
             return;
         }
 #pragma unroll
@@ -744,11 +772,11 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
 #pragma unroll
             for (int k = 0; k < APT; k++) pf[k] = cmul(pf[k], make_coef(fr, fi));
         }
-        if (g.zero_mask != 0 && !generate) { // wave-uniform: slots outside the state's support hold unwritten memory, i.e. zero
-            const bool lane_ok = ((lane_off >> kAmpShift) & g.zero_mask) == 0;
+        if (SPARSE && !generate) { // slots outside the state's support are zero (not loaded, or unwritten memory the fallback loaded);
+                                   // after the tile-uniform factors, so that they are +0 whatever the factors are
 #pragma unroll
             for (int k = 0; k < APT; k++)
-                if (!(lane_ok && ((k_off[k] >> kAmpShift) & g.zero_mask) == 0)) pf[k] = amp_t{(real_t)0, (real_t)0};
+                if (!(sparse_lane_ok && ((k_off[k] >> kAmpShift) & g.zero_mask) == 0)) pf[k] = amp_t{(real_t)0, (real_t)0};
         }
 #pragma unroll
         for (int k = 0; k < APT; k++) {
@@ -1029,6 +1057,16 @@ static int tile_lds_bytes(int tile_bits, int n_high) { return ((int)sizeof(amp_t
 
 constexpr bool tile_has_pack(int b, int threads) { return kAmpShift == 4 && b == 12 && threads == 512; } // the production shape of fp64 shards
 
+// How many registers of a lane hold slots inside the support (TileDev::live_regs): all of them, halved for every high bit in
+// zero_mask counted from the top of the order down, as far as the register role reaches.  Tiles with tail guards: all.
+static int tile_live_regs(const TileGeom &g, int threads, uint64_t zero_mask) {
+    const int slots = 1 << g.tile_bits;
+    if (slots / 4 < threads || (slots / 4) % threads != 0) return (slots + threads - 1) / threads; // not FULL: the guarded path loads every slot
+    int live = slots / threads;
+    for (int j = g.n_high - 1; j >= 0 && live > 1 && ((zero_mask >> g.high[j]) & 1ULL); j--) live >>= 1;
+    return live;
+}
+
 template <int B, int THREADS>
 static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops,
                                 bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
@@ -1039,24 +1077,29 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     const uint64_t ntiles = 1ULL << __builtin_popcountll(nmask & ~tile_mask & ~zero_mask); // tiles whose base index may be non-zero
     const int lds = tile_lds_bytes(g.tile_bits, g.n_high);
     // the opt-in to more than 64 KiB of dynamic LDS is per device (a cluster drives several from one process)
-    static bool attr_set[64] = {false};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     constexpr bool kHasPack = tile_has_pack(B, THREADS);
     const bool packed = pack != nullptr && pack->k > 0;
     if (packed && !kHasPack) return hipErrorNotSupported;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile<B, THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    static bool pack_attr_set[64] = {false};
-    if constexpr (kHasPack) {
-        if (packed && !pack_attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tile<B, THREADS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            pack_attr_set[dev] = true;
+    // four instantiations at most (PACK x SPARSE), each opted in once per device
+    const bool sparse = zero_mask != 0 && !from_zero_ket; // a pass over a partially written state: k_tile<SPARSE>
+    static bool attr_set[4][64] = {{false}};
+    auto opt_in = [&](const void *fn, int which) -> hipError_t {
+        if (attr_set[which][dev]) return hipSuccess;
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) attr_set[which][dev] = true;
+        return e;
+    };
+    {
+        hipError_t e = opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, false, false>), 0);
+        // (the warm-up call opts in both plain instantiations: a run from a reset needs the SPARSE one a pass or two later)
+        if (e == hipSuccess && ((sparse && !packed) || cfg.warm_only)) e = opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, false, true>), 1);
+        if constexpr (kHasPack) {
+            if (e == hipSuccess && packed)
+                e = sparse ? opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, true, true>), 3) : opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, true, false>), 2);
         }
+        if (e != hipSuccess) return e;
     }
     if (cfg.warm_only) return hipSuccess;
     TileDev td;
@@ -1067,6 +1110,9 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     td.zero_mask = zero_mask;
     for (int j = 0; j < 16; j++) td.high[j] = 0;
     for (int j = 0; j < g.n_high; j++) { td.high_mask |= 1ULL << g.high[j]; td.high[j] = (int8_t)g.high[j]; }
+    // the registers of a lane walk the topmost high bits (tile slot bits log2(THREADS) .. B-1): each of them, from the top, that
+    // the state is zero in halves the registers that hold anything
+    td.live_regs = tile_live_regs(g, THREADS, sparse ? zero_mask : 0);
     // tiles per workgroup: enough to amortise the exposed first load — 64 where that still leaves four rounds of workgroups
     // (2048), down to 8 otherwise.  Round 4, late: 64 instead of 8 takes 1 % off a step at every size (tools/tpw_sweep.py: n = 30
     // 66.0 -> 65.4 ms, 128 tiles 66.3, 256 68.3, one round of 512 workgroups 69.6; n = 28 17.14 -> 16.9 with 32; n = 32 260.7 -> 258.8) ...
@@ -1084,15 +1130,19 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     // d_ops: g.n_scale tile-uniform factors first, then the blocks
     const int n_scale = n_ops > 0 ? g.n_scale : 0;
     PackMap pm{};
+#define QSIM_TILE_GO(PACK_, SPARSE_, PM_)                                                                                                          \
+    hipLaunchKernelGGL((k_tile<B, THREADS, PACK_, SPARSE_>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, \
+                       n_ops - n_scale, ntiles, tpw, n_scale, PM_)
     if constexpr (kHasPack) {
         if (packed) {
-            hipLaunchKernelGGL((k_tile<B, THREADS, true>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops,
-                               n_ops - n_scale, ntiles, tpw, n_scale, *pack);
+            if (sparse) QSIM_TILE_GO(true, true, *pack);
+            else QSIM_TILE_GO(true, false, *pack);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((k_tile<B, THREADS>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, n_ops - n_scale,
-                       ntiles, tpw, n_scale, pm);
+    if (sparse) QSIM_TILE_GO(false, true, pm);
+    else QSIM_TILE_GO(false, false, pm);
+#undef QSIM_TILE_GO
     return hipGetLastError();
 }
 

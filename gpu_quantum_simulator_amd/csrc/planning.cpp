@@ -33,8 +33,10 @@ using namespace qsim;
 struct GeomKey {
     int n, f32, tile_bits, low_bits;
     uint64_t high_mask;
+    uint64_t new_mask; // the high bits outside the state's support when the pass starts (0: a pass over a full support).  Such a pass
+                       // reads a fraction of what it writes and runs with those bits topmost: another pass than the full one of the same set
     bool operator<(const GeomKey &o) const {
-        return std::tie(n, f32, tile_bits, low_bits, high_mask) < std::tie(o.n, o.f32, o.tile_bits, o.low_bits, o.high_mask);
+        return std::tie(n, f32, tile_bits, low_bits, high_mask, new_mask) < std::tie(o.n, o.f32, o.tile_bits, o.low_bits, o.high_mask, o.new_mask);
     }
 };
 struct GeomOrder { int8_t high[kMaxTileHigh]; float ms, ms_ascending; };
@@ -42,9 +44,10 @@ static std::mutex g_wisdom_mu;
 static std::map<GeomKey, GeomOrder> g_wisdom;
 static std::atomic<uint64_t> g_wisdom_epoch{1}; // bumped whenever the table changes: cached plans carry the orders they were built with
 
-static GeomKey geom_key(const qsim_state *s, const TileGeom &g) {
-    GeomKey k{g.n, s->f32 ? 1 : 0, g.tile_bits, g.low_bits, 0};
+static GeomKey geom_key(const qsim_state *s, const TileGeom &g, uint64_t new_mask = 0) {
+    GeomKey k{g.n, s->f32 ? 1 : 0, g.tile_bits, g.low_bits, 0, 0};
     for (int j = 0; j < g.n_high; j++) k.high_mask |= 1ULL << g.high[j];
+    k.new_mask = new_mask & k.high_mask;
     return k;
 }
 
@@ -59,17 +62,28 @@ static void shuffle_high(TileGeom &g, uint64_t seed) {
 
 uint64_t qsim::wisdom_epoch() { return g_wisdom_epoch.load(); }
 
-void qsim::order_tile_bits(qsim_state *s, TileGeom &g) {
+// The high bits the state is still zero in (new to the support with this pass) go to the top of the order, the others keep
+// theirs: the topmost bits are walked by the registers of a lane, and k_tile<SPARSE> then loads only the registers that hold
+// something (kernels_impl.inc tile_live_regs).  Stable, so placing twice changes nothing.
+void qsim::place_new_bits(TileGeom &g, uint64_t zero_mask) {
+    std::stable_partition(g.high, g.high + g.n_high, [&](int b) { return !((zero_mask >> b) & 1ULL); });
+}
+
+void qsim::order_tile_bits(qsim_state *s, TileGeom &g, uint64_t zero_mask) {
     s->tile_passes++;
     if (g.n_high < 2) return;
-    if (s->debug_tile_order > 0) {
+    if (s->debug_tile_order > 0) { // any order at all, the new bits wherever they fall: the kernel's other ways of not loading them
         shuffle_high(g, 0x9E3779B97F4A7C15ULL * (uint64_t)(s->debug_tile_order + 1) + 0xD1B54A32D192ED03ULL * s->tile_passes);
         return;
     }
-    std::lock_guard<std::mutex> lock(g_wisdom_mu);
-    auto it = g_wisdom.find(geom_key(s, g));
-    if (it != g_wisdom.end())
-        for (int j = 0; j < g.n_high; j++) g.high[j] = it->second.high[j];
+    const uint64_t new_mask = zero_mask & geom_key(s, g).high_mask;
+    {
+        std::lock_guard<std::mutex> lock(g_wisdom_mu);
+        auto it = g_wisdom.find(geom_key(s, g, new_mask));
+        if (it != g_wisdom.end())
+            for (int j = 0; j < g.n_high; j++) g.high[j] = it->second.high[j];
+    }
+    place_new_bits(g, new_mask); // (a measured order of this key has them there already)
 }
 
 // Scheduler variant per circuit, decided by the planning step (qsim_tune_circuit): key -> SchedConfig::commute.  Circuits
@@ -385,17 +399,27 @@ static int keep_fastest_schedule(qsim_state *s, const qsim_circuit *c, const Sch
 
 // Times every tile pass of `passes` whose geometry is not in the table yet under candidate orders of its high bits and enters
 // the fastest (qsim_tune_circuit's comment).  The state's contents are scratch here; the buffers keep their roles.
-static int measure_tile_orders(qsim_state *s, const std::vector<Pass> &passes, int max_candidates, double budget_ms, qsim_tune_report &r) {
-    std::vector<const Pass *> todo;
+// support: where the state can be non-zero when the first pass starts (0: a reset, ~0: dense).  A pass over a partial support is
+// timed as it will run — on that support, its new bits topmost in every candidate — and entered under a key of its own.
+static int measure_tile_orders(qsim_state *s, const std::vector<Pass> &passes, uint64_t support, int max_candidates, double budget_ms, qsim_tune_report &r) {
+    struct Todo { const Pass *p; uint64_t zero_mask, new_mask; };
+    std::vector<Todo> todo;
+    const uint64_t nmask = index_mask(s->n);
     for (const Pass &p : passes) {
-        if (p.kclass != QSIM_K_TILE) continue;
+        if (p.kclass != QSIM_K_TILE) { support = ~0ULL; continue; } // any other kernel works on a materialised state
+        uint64_t zero_mask = 0;
+        if ((support & nmask) != nmask) {
+            if ((support & nmask) != 0) zero_mask = nmask & ~support; // (the generating pass reads nothing: its order is the full pass's)
+            support |= tile_mask(p.geom);
+        }
         r.tile_passes++;
         if (p.geom.n_high < 2) continue;
+        const GeomKey key = geom_key(s, p.geom, zero_mask);
         std::lock_guard<std::mutex> lock(g_wisdom_mu);
-        if (g_wisdom.count(geom_key(s, p.geom))) { r.already_known++; continue; }
+        if (g_wisdom.count(key)) { r.already_known++; continue; }
         bool dup = false;
-        for (const Pass *q : todo) dup = dup || (geom_key(s, q->geom).high_mask == geom_key(s, p.geom).high_mask);
-        if (!dup) todo.push_back(&p);
+        for (const Todo &q : todo) dup = dup || (geom_key(s, q.p->geom).high_mask == key.high_mask && q.new_mask == key.new_mask);
+        if (!dup) todo.push_back({&p, zero_mask, key.new_mask});
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(hipEventCreate(&e0));
@@ -404,9 +428,10 @@ static int measure_tile_orders(qsim_state *s, const std::vector<Pass> &passes, i
     auto elapsed_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     void *const home = s->amps;
     const bool tune_oop = !todo.empty() && spare_buffer(s) != nullptr;
+    uint64_t zero_mask = 0;
     auto timed = [&](const Pass &p, const TileGeom &g, float &ms) -> int {
         (void)hipEventRecord(e0, s->stream);
-        const int rc2 = launch_tile_pass(s, p, g, false, nullptr, tune_oop); // timed the way most passes of a run go
+        const int rc2 = launch_tile_pass(s, p, g, false, nullptr, tune_oop, zero_mask); // timed the way most passes of a run go
         if (rc2) return rc2;
         (void)hipEventRecord(e1, s->stream);
         if (hipEventSynchronize(e1) != hipSuccess) return fail(QSIM_ERR_DEVICE, "tuning: event sync failed");
@@ -415,10 +440,12 @@ static int measure_tile_orders(qsim_state *s, const std::vector<Pass> &passes, i
     };
     int rc = QSIM_OK;
     for (size_t i = 0; i < todo.size() && rc == QSIM_OK; i++) {
-        const Pass &p = *todo[i];
+        const Pass &p = *todo[i].p;
+        zero_mask = todo[i].zero_mask;
         const double share_end = budget_ms > 0 ? budget_ms * (double)(i + 1) / (double)todo.size() : 1e300;
         TileGeom asc = p.geom;
         std::sort(asc.high, asc.high + asc.n_high);
+        place_new_bits(asc, todo[i].new_mask); // "ascending" for a partial pass: what it runs with when nothing is measured
         float ms = 0.f;
         rc = timed(p, asc, ms); // warm: first touch of the op buffer and of this geometry's code path
         if (rc == QSIM_OK) rc = timed(p, asc, ms);
@@ -426,11 +453,13 @@ static int measure_tile_orders(qsim_state *s, const std::vector<Pass> &passes, i
         GeomOrder best{};
         for (int j = 0; j < asc.n_high; j++) best.high[j] = (int8_t)asc.high[j];
         best.ms = best.ms_ascending = ms;
-        const GeomKey key = geom_key(s, asc);
+        const GeomKey key = geom_key(s, asc, todo[i].new_mask);
         for (int cand = 1; cand < max_candidates; cand++) {
             if (cand >= 4 && elapsed_ms() > share_end) break;
             TileGeom g = asc;
+            std::sort(g.high, g.high + g.n_high);
             shuffle_high(g, key.high_mask * 0x9E3779B97F4A7C15ULL + (uint64_t)cand * 0xD1B54A32D192ED03ULL);
+            place_new_bits(g, key.new_mask);
             rc = timed(p, g, ms);
             if (rc) break;
             r.candidates_timed++;
@@ -477,7 +506,7 @@ extern "C" int qsim_tune_circuit_support(qsim_state *s, const qsim_circuit *c, i
     if (max_candidates > 1 && s->fuse >= 3 && ranked.size() > 1)
         QSIM_TRY(keep_fastest_schedule(s, c, scfg, support, sched_key, ranked, passes));
     qsim_tune_report r{};
-    const int rc = measure_tile_orders(s, passes, max_candidates, budget_ms, r);
+    const int rc = measure_tile_orders(s, passes, support, max_candidates, budget_ms, r);
     if (rep) *rep = r;
     const int rc_reset = qsim_reset(s);
     return rc ? rc : rc_reset;
@@ -488,7 +517,7 @@ extern "C" long qsim_tune_table_size(void) {
     return (long)g_wisdom.size();
 }
 
-// The table as text, one geometry per line: n f32 tile_bits low_bits high_mask(hex) ms ms_ascending order...  A table
+// The table as text, one geometry per line: [part new_mask(hex)] n f32 tile_bits low_bits high_mask(hex) ms ms_ascending order...  A table
 // measured once (per machine) can be loaded by later processes: the C host does so when QSIM_WISDOM names a file.
 extern "C" int qsim_tune_table_save(const char *path) {
     if (!path) return fail(QSIM_ERR_ARG, "NULL path");
@@ -503,6 +532,7 @@ extern "C" int qsim_tune_table_save(const char *path) {
     std::lock_guard<std::mutex> lock(g_wisdom_mu);
     for (const auto &kv : g_wisdom) {
         const int nh = __builtin_popcountll(kv.first.high_mask);
+        if (kv.first.new_mask) fprintf(f, "part %llx ", (unsigned long long)kv.first.new_mask); // a pass over a partial support
         fprintf(f, "%d %d %d %d %llx %.4f %.4f", kv.first.n, kv.first.f32, kv.first.tile_bits, kv.first.low_bits,
                 (unsigned long long)kv.first.high_mask, kv.second.ms, kv.second.ms_ascending);
         for (int j = 0; j < nh; j++) fprintf(f, " %d", (int)kv.second.high[j]);
@@ -537,12 +567,17 @@ extern "C" long qsim_tune_table_load(const char *path) {
         }
         GeomKey k{};
         GeomOrder o{};
-        unsigned long long hm = 0;
-        int used = 0;
+        unsigned long long hm = 0, nm = 0;
+        int used = 0, skip = 0;
+        // "part <new_mask>" in front: the order of a pass that admits those bits to the support.  Lines without it (every line of
+        // a file written before such passes were told apart) are orders of full passes and are looked up for those alone.
+        if (strncmp(line, "part ", 5) == 0 && (sscanf(line + 5, "%llx %n", &nm, &skip) < 1 || nm == 0)) continue;
+        if (nm) memmove(line, line + 5 + skip, strlen(line + 5 + skip) + 1);
         if (sscanf(line, "%d %d %d %d %llx %f %f%n", &k.n, &k.f32, &k.tile_bits, &k.low_bits, &hm, &o.ms, &o.ms_ascending, &used) < 7) continue;
         k.high_mask = hm;
+        k.new_mask = nm;
         const int nh = __builtin_popcountll(hm);
-        if (nh < 2 || nh > kMaxTileHigh) continue;
+        if (nh < 2 || nh > kMaxTileHigh || (nm & ~hm)) continue;
         const char *p = line + used;
         uint64_t seen = 0;
         bool ok = true;
@@ -552,6 +587,12 @@ extern "C" long qsim_tune_table_load(const char *path) {
             else { o.high[j] = (int8_t)v; seen |= 1ULL << v; p += adv; }
         }
         if (!ok) continue; // not a permutation of the set: ignore the line
+        for (int j = 0, seen_new = 0; j < nh && ok; j++) { // the new bits topmost, as the engine runs such a pass
+            const bool is_new = (nm >> o.high[j]) & 1ULL;
+            if (seen_new && !is_new) ok = false;
+            seen_new |= is_new;
+        }
+        if (!ok) continue;
         std::lock_guard<std::mutex> lock(g_wisdom_mu);
         g_wisdom[k] = o;
         g_wisdom_epoch++;
@@ -583,9 +624,9 @@ extern "C" int qsim_plan_circuit_from(const qsim_circuit *c, int fuse, int tile_
     const std::vector<Pass> passes = schedule(engine_sched_config(c->num_q, fuse, tile_bits, tile_low_bits, 32, 10, false, initial_support), queue_of(c), &out->gates);
     for (const Pass &p : passes) { // a run from a reset: the first tile passes visit part of the register (Pass::visited)
         out->launches++;
-        out->algorithmic_bytes += p.bytes * p.visited;
+        out->algorithmic_bytes += p.moved();
         out->k_launches[p.kclass]++;
-        out->k_bytes[p.kclass] += p.bytes * p.visited;
+        out->k_bytes[p.kclass] += p.moved();
     }
     return QSIM_OK;
 }
@@ -606,7 +647,7 @@ extern "C" int qsim_plan_passes(const qsim_circuit *c, int fuse, int tile_bits, 
         o.blocks = p.kclass == QSIM_K_TILE ? (int)p.blocks.size() - p.geom.n_scale : 1;
         o.tile_mask = p.kclass == QSIM_K_TILE ? tile_mask(p.geom) : index_mask(c->num_q); // a single-gate kernel: treat every bit as touched
         o.visited = p.visited;
-        o.bytes = p.bytes * p.visited;
+        o.bytes = p.moved();
         o.cost_bytes = pass_time_cost(p, false);
     }
     return QSIM_OK;

@@ -24,7 +24,7 @@ static int resolve_events(qsim_state *s) {
     for (auto &pe : s->events) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, pe.start, pe.stop) == hipSuccess) s->stats.k_ms[pe.kclass] += ms;
-        if (s->launch_log.size() < (1u << 20)) s->launch_log.push_back({pe.kclass, pe.n_ops, pe.high_mask, (double)ms, pe.order_code, pe.visited, std::move(pe.forms)});
+        if (s->launch_log.size() < (1u << 20)) s->launch_log.push_back({pe.kclass, pe.n_ops, pe.high_mask, (double)ms, pe.order_code, pe.visited, pe.read_share, std::move(pe.forms)});
         s->event_pool.push_back(pe.start);
         s->event_pool.push_back(pe.stop);
     }
@@ -69,6 +69,14 @@ extern "C" int qsim_launch_log_visited(qsim_state *s, long index, double *visite
     const LaunchRec *rec = visited ? log_record(s, index, err) : nullptr;
     if (!rec) return err;
     *visited = rec->visited;
+    return QSIM_OK;
+}
+
+extern "C" int qsim_launch_log_read_share(qsim_state *s, long index, double *read_share) {
+    int err = QSIM_ERR_ARG;
+    const LaunchRec *rec = read_share ? log_record(s, index, err) : nullptr;
+    if (!rec) return err;
+    *read_share = rec->read_share;
     return QSIM_OK;
 }
 

@@ -595,6 +595,9 @@ uint64_t Scheduler::tile_pass(const std::vector<FusedOp> &ops, uint64_t hset, co
     if (prefer != ~0ULL) { // the state's support is known: the pass visits the tiles inside support | tile
         const uint64_t all = index_mask(cfg_.n);
         p.visited = 1.0 / (double)(1ULL << (cfg_.n - __builtin_popcountll((prefer | tmask) & all)));
+        // ... and reads the slots of those tiles that are inside the support already; nothing at all while there is no support (the
+        // pass then generates the basis state)
+        p.read_share = (prefer & all) == 0 ? 0.0 : p.visited / (double)(1ULL << __builtin_popcountll(tmask & ~prefer & all));
     }
     sink(std::move(p));
     return tmask;

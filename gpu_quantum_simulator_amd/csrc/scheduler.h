@@ -113,6 +113,9 @@ struct Pass {
     std::vector<uint32_t> src; // SchedConfig::track: the gates folded into this pass, by their order of arrival at the scheduler (0, 1, ...)
     double bytes = 0;         // algorithmic bytes this pass must move when it sweeps the whole register
     double visited = 1.0;     // ... times this: the fraction of the register inside the state's support after the pass (tile passes of a run that starts from a reset, SchedConfig::initial_support)
+    double read_share = 1.0;  // tile passes of such a run: the fraction of the register the pass READS — of a visited tile only the slots inside the
+                              // support before the pass are loaded (visited / 2^(tile qubits new to the support); 0 for the pass that generates the basis state)
+    double moved() const { return bytes / 2 * (visited + read_share); } // algorithmic bytes of the pass as it runs: half of `bytes` are reads, half writes
     bool diag_full = false;   // QSIM_K_PHASE executed over every amplitude (d0 != 1 or q < 2)
 };
 
@@ -124,6 +127,9 @@ struct Pass {
 // same settings; round 4's first fit 0.58, round 3's kernel 0.77); fp32 states (pass_model_n30_f32_last_tree.csv): 3.67 + 0.33 x
 // max(0, blocks - 3), rms 0.24 ms (0.57 per block before the fp32 swizzle).  The planning steps (engine: which schedule; shard planner:
 // which segmentation) rank by the sum of this — fewer sweeps are worth more than leaner ones, but not at any number of blocks.
+// The byte term is the fitted one (bytes x visited), not Pass::moved(): a partial pass reads less than it writes since the
+// kernel stopped loading slots outside the support, but the model was fitted on passes that loaded them, and which schedule a
+// circuit gets hangs on it: it changes only together with a new fit.
 inline double pass_time_cost(const Pass &p, bool f32) {
     if (p.kclass != QSIM_K_TILE) return p.bytes;
     const int nb = (int)p.blocks.size() - p.geom.n_scale;

@@ -410,6 +410,10 @@ int qsim_launch_log_order(qsim_state *s, long index, int *order, int *count);
 /* ... and the fraction of the register's tiles it worked on (1 for a full sweep and for other kernels; less while the state's
  * support is partial, QSIM_OPT_SPARSE_START / qsim_set_support). */
 int qsim_launch_log_visited(qsim_state *s, long index, double *visited);
+/* ... and the fraction of the register it read: of a visited tile only the slots inside the state's support before the pass are
+ * loaded, so this is visited / 2^(tile qubits new to the support); 0 for the pass that generates a basis state, 1 for a full
+ * sweep and for other kernels.  The pass moved (visited + read_share) / 2 of the bytes of a full pass. */
+int qsim_launch_log_read_share(qsim_state *s, long index, double *read_share);
 /* ... and what its blocks looked like, one byte per block in order (tile passes; *count = 0 otherwise; at most `cap` are written):
  * bits 0-1 log2 of the entries per row the block is evaluated with (1, 2 or 4), bits 2-4 its qubits inside the tile, bit 5 set when
  * at least half of its rows are identity rows, bits 6-7 its selector qubits outside the tile.  Recorded under QSIM_OPT_PROFILE = 2
