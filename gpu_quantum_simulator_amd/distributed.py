@@ -16,7 +16,7 @@ gate never forces data to move by itself:
     relabelling idea (quantum_simulator_4x4_permute.cu:377-434) with the objective inverted: hot -> local.
   * the initial |0...0> is symmetric under qubit permutations, so the first placement is free.
 
-The planner is the C++ one inside libqsim (csrc/dist.cpp, shared with the C host's qsim_cluster) and is deterministic:
+The planner is the C++ one inside libqsim (csrc/shard_plan.cpp, shared with the C host's qsim_cluster) and is deterministic:
 every rank builds the same plan (only its own per-rank scalars / X gates differ), so ranks never need to agree on
 anything at run time.  `VirtualCluster` drives P shards inside
 one process (exchange = plain copies) so the whole path is testable on one GPU or, with a CPU shard
@@ -57,7 +57,7 @@ def normalize_gates(gates: Sequence[Sequence], gate_matrix: Callable[[str], np.n
 
 
 class ShardPlan:
-    """Steps for one rank, produced by the C++ planner in libqsim (csrc/dist.cpp, the same one the C host's
+    """Steps for one rank, produced by the C++ planner in libqsim (csrc/shard_plan.cpp, the same one the C host's
     qsim_cluster uses): ('local', [ops]) and ('exchange', rank_bits, local_positions).
 
     ops: ('u1', local_pos, U) | ('cx', cpos, tpos) | ('scale', z).  Every rank sees the same sequence of step kinds and
@@ -275,7 +275,7 @@ class ShardedSimulator:
             self._warm_up_links()
 
     def _attach_native_comm(self):
-        """Every byte of state then travels through ncclSend / ncclRecv issued by libqsim itself (csrc/dist.cpp
+        """Every byte of state then travels through ncclSend / ncclRecv issued by libqsim itself (csrc/rank_comm.cpp
         qsim_rank_comm_exchange); torch.distributed only carries the 128-byte RCCL id.  All ranks must agree on the
         outcome, so a failure anywhere (reduced with MIN) sends every rank to the torch.distributed path."""
         import sys

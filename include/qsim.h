@@ -301,7 +301,9 @@ qsim_state *qsim_cluster_shard(qsim_cluster *c, int shard);
 int qsim_cluster_set_option(qsim_cluster *c, int option, long value);
 int qsim_cluster_reset(qsim_cluster *c); /* |0...0>, identity qubit map */
 /* ONE circuit per reset (compute_state_vector semantics): the plan's free first qubit placement and its sparse exchanges are
- * only right from |0...0>, so a call that does not follow qsim_cluster_reset fails with QSIM_ERR_ARG instead of dropping data. */
+ * only right from |0...0>, so a call that does not follow qsim_cluster_reset fails with QSIM_ERR_ARG instead of dropping data.
+ * What is checked is that no circuit has run since the reset: amplitudes written into a shard through qsim_cluster_shard() after
+ * the reset are not noticed, and the run may drop them. */
 int qsim_cluster_run_circuit(qsim_cluster *c, const qsim_circuit *circuit);
 int qsim_cluster_sync(qsim_cluster *c);
 /* Planning for a circuit the cluster will run (repeatedly): the shard plan is built and kept, and every shard's local steps go

@@ -1,4 +1,4 @@
-"""Pure-Python restatement of the shard planner (csrc/dist.cpp build_plan), kept in tests/ as an independent cross-check:
+"""Pure-Python restatement of the shard planner (csrc/shard_plan.cpp build_plan), kept in tests/ as an independent cross-check:
 the product path uses the C++ planner through distributed.ShardPlan; tests require the two to agree step by step."""
 from typing import List, Tuple
 
@@ -18,7 +18,7 @@ class PyShardPlan:
     ops: ('u1', local_pos, U) | ('cx', cpos, tpos) | ('scale', z).  Every rank sees the same sequence of
     step kinds and the same exchanges."""
 
-    LINK_UNITS, PACK_UNITS = 25600, 256  # csrc/dist.cpp plan_cost: shard/link and pack pass in common integer units
+    LINK_UNITS, PACK_UNITS = 25600, 256  # csrc/shard_plan.cpp plan_cost: shard/link and pack pass in common integer units
 
     def __init__(self, n: int, p: int, gates: List[Tuple], rank: int, lookahead_free_start: bool = True):
         assert 0 <= p <= n - 2 or p == 0, "need at least two local qubits"

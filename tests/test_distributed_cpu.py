@@ -190,7 +190,7 @@ def test_bench_selfcheck_on_two_gloo_ranks(broken):
 @pytest.mark.parametrize("n,depth,seed,vocab", [(8, 300, 11, "all"), (12, 600, 12, "all"), (16, 800, 13, "clifford_t"),
                                                 (30, 1000, 20240147, "all")])
 def test_cpp_planner_equals_python_restatement(world, n, depth, seed, vocab, monkeypatch):
-    """libqsim's planner (csrc/dist.cpp: the product path of both the C host and distributed.py) against the
+    """libqsim's planner (csrc/shard_plan.cpp: the product path of both the C host and distributed.py) against the
     independent pure-Python restatement in tests/py_shard_plan.py: same exchanges, same final qubit map, and the same
     per-rank local ops on every rank.  The restatement covers the planner proper (which gates can run, Belady eviction,
     the two placement policies); the hand-over of a segment's small last pass to the next segment (small_tail, which asks
@@ -220,7 +220,7 @@ def test_cpp_planner_equals_python_restatement(world, n, depth, seed, vocab, mon
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_small_last_pass_waits_for_the_exchange(oracle, tmp_path, world, monkeypatch):
-    """csrc/dist.cpp small_tail: a segment's last pass, when the engine's scheduler would fill it with only a handful of
+    """csrc/shard_plan.cpp small_tail: a segment's last pass, when the engine's scheduler would fill it with only a handful of
     gates, is handed on to the segment after the exchange.  The plan stays a valid execution order (CPU shards equal the
     oracle), no gate is lost or duplicated, and on the bench circuit the shards sweep their part of the register less often."""
     n = 14
@@ -347,16 +347,36 @@ def _pack_np(state, m, Lsel):
     return state[src]
 
 
+def test_plan_for_more_shards_than_an_exchange_has_block_bits_is_refused():
+    """An exchange names its blocks with one mask bit each (csrc/shard_plan.h kMaxRoleBits = 5: groups of at most 32
+    shards), so a plan for 64 shards — on a 10-qubit circuit, where every other check passes — is refused with
+    QSIM_ERR_ARG and a text that names the limit; 32 shards still plan.  Plan creation is host-only."""
+    from gpu_quantum_simulator_amd import _lib
+    from gpu_quantum_simulator_amd.simulator import Circuit, ShardPlanHandle
+    n = 10
+    circ = Circuit.empty(n)
+    for g in normalize_gates(circuits.random_gates(n, 200, 64, "all"), gate_matrix):
+        if g[0] == "cx":
+            circ.append_cx(g[1], g[2])
+        else:
+            circ.append_1q(g[2], g[1])
+    with pytest.raises(_lib.QsimError) as refused:
+        ShardPlanHandle(circ, 64)
+    assert refused.value.code == _lib.ERR_ARG
+    assert "64 shards" in str(refused.value) and "at most 32" in str(refused.value)
+    assert ShardPlanHandle(circ, 32).num_steps >= 1
+
+
 @pytest.mark.parametrize("world", [2, 4, 8, 16, 32])
 @pytest.mark.parametrize("n,depth,seed,vocab", [(7, 120, 21, "all"), (10, 400, 22, "all"), (12, 500, 23, "clifford_t"), (11, 60, 24, "all"),
                                                 (15, 260, 25, "all"), (15, 120, 26, "clifford_t"), (16, 88, 9424, "all")])  # shards of >= 2^12: the hand-over is active
 def test_sparse_exchange_protocol_on_poisoned_memory(oracle, tmp_path, world, n, depth, seed, vocab):
-    if world >= 16 and n < 10:
-        pytest.skip("shards of fewer than 2^5 amplitudes")
-    """What an exchange may leave out (csrc/dist.cpp roles_of; qsim_shard_plan_exchange_roles): shards that hold nothing
+    """What an exchange may leave out (csrc/shard_plan.cpp roles_of; qsim_shard_plan_exchange_roles): shards that hold nothing
     neither pack nor send, blocks that are zero throughout are not received, and a receiver only ever looks inside its
     new support.  Modelled here with numpy shards whose memory is NaN wherever the protocol did not write: if a block that
     matters stayed home, or a support were too small, the NaNs (or wrong amplitudes) reach the gathered state."""
+    if world >= 16 and n < 10:
+        pytest.skip("shards of fewer than 2^5 amplitudes")
     gates = circuits.random_gates(n, depth, seed, vocab)
     want = _oracle_state(oracle, tmp_path, n, gates)
     p = world.bit_length() - 1

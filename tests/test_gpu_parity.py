@@ -570,7 +570,7 @@ def test_masked_block_sums_and_gather():
 
 
 def test_rccl_rank_comm_on_one_gpu():
-    """The native RCCL call sites (csrc/dist.cpp) with the one GPU present: a 1-rank communicator from
+    """The native RCCL call sites (csrc/rank_comm.cpp, csrc/shard_exec.cpp) with the one GPU present: a 1-rank communicator from
     ncclGetUniqueId / ncclCommInitRank, shard data through ncclSend -> ncclRecv on the engine's stream (loopback), and
     the argument checks of the exchange entry point.  Exchanges between ranks need more GPUs than this box has; their
     data path is the same pack + send/recv and is covered by the gloo tests (plan) and the virtual-shard tests (layout)."""
@@ -731,7 +731,7 @@ def test_measurement_post_path(oracle, golden_dir, tmp_path):
 
 @pytest.mark.parametrize("shards,opts", [(2, {}), (4, {}), (8, {}), (16, {}), (4, {"pingpong": 2, "tile_bits": 9})])
 def test_c_host_cluster_virtual_shards(oracle, tmp_path, shards, opts):
-    """qsim_cluster (csrc/dist.cpp): the C host's one-process sharded path, all shards on device 0.  Sixteen shards swap
+    """qsim_cluster (csrc/cluster.cpp): the C host's one-process sharded path, all shards on device 0.  Sixteen shards swap
     up to four qubits at once, more than the one-kernel exchange takes (eight block destinations): those exchanges go
     through the pack + copy form, in the same run as one-kernel ones."""
     from gpu_quantum_simulator_amd import Cluster
@@ -1270,7 +1270,7 @@ def test_support_api_and_zero_shard_semantics(oracle, tmp_path):
 
 @pytest.mark.parametrize("shards", [2, 4, 8])
 def test_cluster_exchanges_leave_out_what_is_zero(oracle, tmp_path, shards):
-    """Support carried through exchanges (csrc/dist.cpp roles_of): the first exchanges of a run move only the blocks that can
+    """Support carried through exchanges (csrc/shard_plan.cpp roles_of): the first exchanges of a run move only the blocks that can
     be non-zero, shards that hold nothing do no work, and the shards keep visiting only their support afterwards — with
     stale amplitudes of an earlier, unrelated run in every buffer (state and exchange scratch).  Same amplitudes as the oracle."""
     from gpu_quantum_simulator_amd import Cluster
