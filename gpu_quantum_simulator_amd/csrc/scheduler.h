@@ -7,9 +7,17 @@
 // clusters are folded eagerly (no separate pending 2x2 per paired qubit), identity tests are EXACT
 // (the reference's 1e-3 tolerance reorders gates), and level 3 groups clusters into
 // cache-blocked passes by a greedy scan over the dependency order.
+//
+// Three files implement it, by concern (scheduler_impl.h holds the few helpers they share; libqsim.so exports none of them):
+//   fusion.cpp        FusedOp predicates, the fusion algebra, the cluster state machine (add_1q / add_cx / add_2q / fold_2q /
+//                     close / finish), the QSIM_SCHED_* knob table and engine_sched_config
+//   tile_block.cpp    TileBlock methods, the row-class components, to_block, merge_blocks
+//   pass_builder.cpp  single_op_pass, tile_pass, and the level-3 pass construction: PendingWalk (the ONE walk over the pending
+//                     clusters) and PassBuilder, whose named steps build_passes calls in a loop
 #ifndef QSIM_SCHEDULER_H
 #define QSIM_SCHEDULER_H
 
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <functional>
@@ -37,7 +45,6 @@ struct FusedOp {
         if (kind != OP_G1) m |= 1ULL << q_lo;
         return m;
     }
-    int max_row_nnz() const; // exact-zero structure
     bool is_diag() const;
     bool is_identity() const;
     uint64_t selector_mask() const; // qubits the matrix is block-diagonal in (exact zeros): it never mixes their 0 and 1 halves
@@ -58,6 +65,7 @@ struct TileBlock {
         int n = 0;
         uint8_t col[kMaxRowNnz];
         cd val[kMaxRowNnz];
+        bool is_identity_row(int r) const { return n == 1 && col[0] == r && val[0] == cd(1.0, 0.0); } // row r of the identity, exactly
     };
     std::vector<Row> store; // banks() x dim() rows, bank-major; sized by shape()
     uint32_t gates = 0;
@@ -91,7 +99,7 @@ struct TileBlock {
     // can be skipped.  false: some component is larger than kMaxRowNnz or the packing leaves a gap (such a block is
     // never built: merge_blocks asks first).
     bool classes(int &T, std::vector<std::vector<int>> &rows, std::vector<std::vector<int>> &cols) const;
-    bool classes_feasible() const; // the same answer as classes() without building the layout (no heap: merge_blocks asks often)
+    bool classes_feasible() const; // the answer of classes() without the layout, from the same components (no heap: merge_blocks asks often)
 };
 
 // tile_op.cpp: the block as the TileOp k_tile reads under geometry g.  false when a qubit is on the wrong side of the tile or the
@@ -170,23 +178,35 @@ struct SchedConfig {
     int track = 0; // 1: every pass lists the gates it absorbed (Pass::src) — the shard planner asks which gates a segment's last pass holds
 };
 
+// The tile as the scheduler's steps see it, derived from the configuration in this one place.
+struct TileShape {
+    int B, L;          // index bits of a tile; the lowest L of them are always bits 0 .. L-1
+    int kmax;          // free slots for high qubits
+    uint64_t lowmask;  // bits 0 .. L-1
+    // merge_blocks: tiles of fewer than 2^11 amplitudes keep to 3 qubits: a block on k > 3 qubits deals the 2^(k-3) parts of a group to
+    // different waves, so a part must be at least one wave: 2^(B-k) >= 64 groups (k_tile's tile_op_part).  2^11 tiles take
+    // 5 qubits, 2^12 and larger 6.
+    int merge_max_q;
+    explicit TileShape(const SchedConfig &c)
+        : B(std::min(c.tile_bits, c.n)), L(std::min(c.tile_low_bits, B)), kmax(std::min(B - L, (int)kMaxTileHigh)), lowmask((1ULL << L) - 1ULL),
+          merge_max_q(B >= 11 ? std::max(3, std::min(std::min(c.merge_qubits, kMaxBlockQ), B - 6)) : 3) {}
+};
+
 // The configuration qsim_flush schedules with for a state of n qubits (options as given by the caller; the search settings
-// follow the size of the state, see the comment in scheduler.cpp).
+// follow the size of the state, see the comment in fusion.cpp).
 SchedConfig engine_sched_config(int n, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, int pad_from = 10, bool f32 = false,
                                 uint64_t initial_support = 0);
 
 // The QSIM_SCHED_* environment variables override the search parameters for experiments (tools/).
 // They are not part of the API and change the pass count, never the result — but they DO shape the schedule, so the
 // engine folds this record into the identity of a cached plan (a plan built under one setting is never replayed under
-// another).  `set` has one bit per variable that is present.
+// another).  `set` has one bit per variable that is present.  fusion.cpp's knob table is the ONE list of the variables: reading,
+// applying and comparing all go over it.
 struct SchedEnv {
     uint32_t set = 0;
     int lookahead = 0, rollout = 0, window = 0, local_iters = 0, objective = 0, merge = 0, merge_qubits = 0, cap = 0, seed = 0;
     double cheap_margin = 0;
-    bool operator==(const SchedEnv &o) const {
-        return set == o.set && lookahead == o.lookahead && rollout == o.rollout && window == o.window && local_iters == o.local_iters &&
-               objective == o.objective && merge == o.merge && merge_qubits == o.merge_qubits && cap == o.cap && seed == o.seed && cheap_margin == o.cheap_margin;
-    }
+    __attribute__((visibility("hidden"))) bool operator==(const SchedEnv &o) const;
 };
 SchedEnv read_sched_env();                      // the environment as it is now
 void apply_sched_env(const SchedEnv &e, SchedConfig &cfg);
@@ -213,6 +233,7 @@ class Scheduler {
 
   private:
     SchedConfig cfg_;
+    TileShape tile_;
     uint64_t gates_ = 0;
     std::vector<FusedOp> pool_;   // open clusters
     std::vector<int> open_;       // per qubit: index into pool_, or -1
@@ -220,7 +241,11 @@ class Scheduler {
     std::vector<std::vector<uint32_t>> pool_src_, closed_src_; // SchedConfig::track: the gates behind pool_[i] / closed_[i]
     mutable std::vector<uint32_t> cur_src_;                     // ... and behind the pass being emitted
 
+    class PassBuilder; // pass_builder.cpp: the state and the steps of build_passes
     void close(int idx);
+    // the ONE way a cluster comes to be: opened on its qubits, or appended closed; `src`: the gates behind it (kept under SchedConfig::track)
+    __attribute__((visibility("hidden"))) void open_cluster(const FusedOp &op, std::vector<uint32_t> src);
+    __attribute__((visibility("hidden"))) void append_closed(const FusedOp &op, uint32_t gate_index);
     void fold_2q(const cd U[16], int q_hi, int q_lo, uint32_t gates, uint32_t gate_index);
     void build_passes(const PassSink &sink);
     void single_op_pass(const FusedOp &op, const PassSink &sink) const;

@@ -6,7 +6,7 @@ the project's fp32 bound).  Further down: which role the new bits really play in
 qsim_flush_pack ending on a partial state, and measured orders with the wisdom file's round trip.
 
 Which circuits can be compared bit for bit.  With sparse start off the scheduler does not know the support, and it then
-builds OTHER passes out of the same gates (scheduler.cpp): (1) build_passes tries a pass that stays inside the support
+builds OTHER passes out of the same gates (pass_builder.cpp): (1) build_passes tries a pass that stays inside the support
 first (cheap_margin), and (2) tile_pass takes qubits a block is merely block-diagonal in into the tile only when they are
 inside the support, which changes what merge_blocks multiplies together on the host.  Other products of the same
 matrices round differently, so two such runs of a general circuit agree to ~1e-17 and not in the last bit — with or

@@ -347,3 +347,69 @@ def test_tokenizer_formatting_fuzz_against_the_oracle(oracle, tmp_path):
             else:
                 oracle.apply_1q(s, on, g[2].T, g[1])
         assert s.tobytes() == amps.tobytes(), (case, text)
+
+
+# One fixed small circuit under every QSIM_SCHED_* variable, each set alone to a value other than its default.  On the commit
+# before the knob table (scheduler.cpp read, applied and compared the variables in three hand-written lists) eight of the
+# eleven changed this circuit's plan, each in its own way (KNOBS_LIVE), and three left it as it is at this size
+# (KNOBS_WITHOUT_EFFECT_HERE; on the 1000-gate circuits of tools/sched_digest.py all eleven are live).
+KNOB_CIRCUIT = dict(n=14, depth=300, seed=5, tile_bits=11, tile_low_bits=3, tile_max_ops=8)
+KNOBS_LIVE = {"LOOKAHEAD": "2", "WINDOW": "16", "OBJ": "1", "MERGE": "0", "MERGEQ": "4", "CAP": "4", "NOCOMMUTE": "1", "SEED": "7"}
+KNOBS_WITHOUT_EFFECT_HERE = {"ROLLOUT": "2", "LOCAL": "2", "CHEAP": "0.25"}
+_KNOB_CHILD = """
+import hashlib, json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from gpu_quantum_simulator_amd import Circuit, circuits, gate_matrix
+from helpers import np_apply_1q, np_apply_cx, replay_schedule
+k = json.loads(sys.argv[2])
+gates = circuits.random_gates(k["n"], k["depth"], k["seed"], "all")
+c = Circuit.from_gates(k["n"], gates)
+sched = c.schedule(3, k["tile_bits"], k["tile_low_bits"], k["tile_max_ops"])
+h = hashlib.sha256()
+for s in sched:
+    h.update(repr(s[:4] + (s[5],)).encode())
+    h.update(b"" if s[4] is None else s[4].tobytes())
+for p in c.passes(3, k["tile_bits"], k["tile_low_bits"], 0):
+    h.update(repr(sorted(p.items())).encode())
+want = np.zeros(1 << k["n"], dtype=np.complex128)
+want[0] = 1
+for g in gates:
+    if g[0] == "cx":
+        want = np_apply_cx(want, k["n"], g[1], g[2])
+    elif g[0] == "rz":
+        want = np_apply_1q(want, k["n"], gate_matrix(f"rz({g[1]!r})"), g[2])
+    else:
+        want = np_apply_1q(want, k["n"], gate_matrix(g[0]), g[1])
+print(json.dumps({"plan": h.hexdigest(), "err": float(np.max(np.abs(replay_schedule(k["n"], sched) - want)))}))
+"""
+
+
+def test_every_sched_variable_is_read_applied_and_kept_apart():
+    """Guards the knob table (fusion.cpp) against a variable that aliases another or is dropped: the library reads the
+    environment per Scheduler, so every setting runs in a child process of its own."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    base = {k: v for k, v in os.environ.items() if not k.startswith("QSIM_SCHED_")}
+    base["PYTHONPATH"] = os.pathsep.join([os.path.dirname(here), here, base.get("PYTHONPATH", "")])
+    base["QSIM_NO_TORCH_PRELOAD"] = "1"  # host only
+    settings = {"default": None, **KNOBS_LIVE, **KNOBS_WITHOUT_EFFECT_HERE}
+    assert len(settings) == 12  # the eleven variables of scheduler.h SchedEnv
+    procs = {}
+    for name, value in settings.items():
+        env = dict(base)
+        if value is not None:
+            env["QSIM_SCHED_" + name] = value
+        procs[name] = subprocess.Popen([sys.executable, "-c", _KNOB_CHILD, here, json.dumps(KNOB_CIRCUIT)], env=env,
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    got = {}
+    for name, p in procs.items():
+        out, err = p.communicate()
+        assert p.returncode == 0, (name, err)
+        got[name] = json.loads(out.strip().splitlines()[-1])
+        assert got[name]["err"] < TOL, (name, got[name]["err"])  # whatever the knobs do to the plan, never to the result
+    for name in KNOBS_WITHOUT_EFFECT_HERE:
+        assert got[name]["plan"] == got["default"]["plan"], name
+    live = [got[name]["plan"] for name in KNOBS_LIVE] + [got["default"]["plan"]]
+    assert len(set(live)) == len(live), {name: got[name]["plan"][:12] for name in got}
