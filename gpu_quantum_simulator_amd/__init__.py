@@ -6,9 +6,9 @@ C host `bin/qsim`.  This Python package is the host-side mirror of that ABI used
 importing it never loads anything from oracle/.
 """
 from . import circuits  # noqa: F401  (pure Python, no native code)
-from .pauli import pauli_masks  # noqa: F401  (pure Python too)
+from .pauli import pauli_masks, trotter_rotations  # noqa: F401  (pure Python too)
 
-__all__ = ["circuits", "pauli_masks", "Simulator", "Circuit", "Cluster", "run_qasm", "gate_matrix", "ShardPlanHandle", "RankComm"]
+__all__ = ["circuits", "pauli_masks", "trotter_rotations", "Simulator", "Circuit", "Cluster", "run_qasm", "gate_matrix", "ShardPlanHandle", "RankComm"]
 
 
 def __getattr__(name):  # lazy: `import gpu_quantum_simulator_amd.circuits` must work before the library is built

@@ -2,6 +2,7 @@
 // may appear several times: "virtual shards", used to validate the sharded path where fewer than P GPUs exist).  The plan
 // it runs and the helpers it shares with the one-process-per-GPU driver are shard_plan.h's.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "qsim_internal.h"
@@ -591,6 +592,76 @@ extern "C" int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_mas
             if (rc) return cfail(rc, "shard %d: %s", r, qsim_last_error());
             for (size_t i = 0; i < gt.size(); i++) out[gt[i]] += part[i];
         }
+    return QSIM_OK;
+}
+
+// exp(-i theta/2 P_t) on the sharded state, t = 0 first (DESIGN "Pauli rotations").  Masks arrive in logical qubits and are mapped
+// through `pos`, as in qsim_cluster_expect_paulis.  Z on shard-id bits is a sign per shard.  A run whose x has shard-id bits
+// (x_rank) pairs shard r with shard r ^ x_rank: the member with the highest bit of x_rank clear sweeps all its local indices
+// against its partner's buffer and writes both; the other member does nothing.  For that every shard has been settled and its
+// stream waited for, and afterwards the partner's stream waits for the sweep that wrote its buffer.
+extern "C" int qsim_cluster_apply_pauli_rotations(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms) {
+    if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
+    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: negative term count");
+    if (num_terms == 0) return QSIM_OK;
+    if (!x_masks || !z_masks || !thetas) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: NULL argument");
+    const uint64_t nmask = qsim::index_mask(c->n), mmask = qsim::index_mask(c->m);
+    std::vector<uint64_t> X((size_t)num_terms), Z((size_t)num_terms);
+    for (long t = 0; t < num_terms; t++) {
+        if ((x_masks[t] | z_masks[t]) & ~nmask)
+            return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: term %ld names a qubit outside the %d-qubit register", t, c->n);
+        if (!std::isfinite(thetas[t])) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: term %ld has a non-finite angle", t);
+        X[(size_t)t] = physical_index(c, x_masks[t]);
+        Z[(size_t)t] = physical_index(c, z_masks[t]);
+        if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)
+            return cfail(QSIM_ERR_ARG,
+                         "qsim_cluster_apply_pauli_rotations: term %ld has X or Y on a qubit that currently selects the shard, and the shards are on "
+                         "different devices: reading a partner shard across devices is not implemented",
+                         t);
+    }
+    c->fresh = false; // the state is no longer |0...0>: a circuit needs a reset first
+    uint64_t paired_by = 0; // the x_rank all shards are settled and waited for (0: not)
+    for (const qsim::RotRoute &rt : qsim::route_rotations(X.data(), Z.data(), num_terms, mmask)) {
+        const uint64_t x = X[(size_t)rt.first], xr = x >> c->m;
+        if (rt.gate) {
+            double U[8];
+            qsim::pauli_rot_1q((Z[(size_t)rt.first] & x) != 0, thetas[rt.first], U);
+            for (qsim_state *s : c->shard)
+                if (const int rc = qsim_apply_1q(s, U, __builtin_ctzll(x))) return cfail(rc, "%s", qsim_last_error());
+            paired_by = 0;
+            continue;
+        }
+        if (xr == 0) {
+            for (int r = 0; r < c->P; r++) {
+                const int rc = qsim::pauli_rot_run(c->shard[(size_t)r], nullptr, (uint64_t)r, x, Z.data() + rt.first, thetas + rt.first, rt.count);
+                if (rc) return cfail(rc, "shard %d: %s", r, qsim_last_error());
+            }
+            paired_by = 0;
+            continue;
+        }
+        // a shard's buffer is about to be read and written from another shard's stream: everything queued must have run.  A pair
+        // of which one member holds nothing gets that member's zeros written; a pair that holds nothing at all stays untouched.
+        if (paired_by != xr)
+            for (int r = 0; r < c->P; r++) {
+                qsim_state *s = c->shard[(size_t)r];
+                if (qsim_holds_nothing(s) && qsim_holds_nothing(c->shard[(size_t)((uint64_t)r ^ xr)])) continue;
+                if (qsim_sync(s) != QSIM_OK) return cfail(QSIM_ERR_DEVICE, "shard %d: %s", r, qsim_last_error());
+            }
+        paired_by = xr;
+        for (int r = 0; r < c->P; r++) {
+            if (((uint64_t)r >> (63 - __builtin_clzll(xr))) & 1ULL) continue; // its partner sweeps the pair
+            qsim_state *s = c->shard[(size_t)r], *other = c->shard[(size_t)((uint64_t)r ^ xr)];
+            if (qsim_holds_nothing(s) && qsim_holds_nothing(other)) continue;
+            void *partner = qsim_state_buffer(other);
+            if (!partner) return cfail(QSIM_ERR_DEVICE, "shard %d: %s", (int)((uint64_t)r ^ xr), qsim_last_error());
+            const int rc = qsim::pauli_rot_run(s, partner, (uint64_t)r, x, Z.data() + rt.first, thetas + rt.first, rt.count);
+            if (rc) return cfail(rc, "shard %d: %s", r, qsim_last_error());
+            // the partner's stream must not run ahead of the sweep that wrote its buffer
+            hipError_t e = hipEventRecord(c->packed[(size_t)r], (hipStream_t)qsim_stream(s));
+            if (e == hipSuccess) e = hipStreamWaitEvent((hipStream_t)qsim_stream(other), c->packed[(size_t)r], 0);
+            if (e != hipSuccess) return cfail(QSIM_ERR_DEVICE, "shard %d: ordering the partner's stream failed: %s", r, hipGetErrorString(e));
+        }
+    }
     return QSIM_OK;
 }
 

@@ -1,10 +1,11 @@
-"""Pauli strings as the two masks qsim_expect_paulis takes.  Pure Python: usable without the library.
+"""Pauli strings as the two masks qsim_expect_paulis and qsim_apply_pauli_rotations take, and the rotation list of a product
+formula.  Pure Python: usable without the library.
 
 A string is written sparsely in the project's qubit numbering (qubit q = bit q of the amplitude index): "X0 Z3 Y17" —
 whitespace-separated, letters XYZ in either case, "I5" allowed and ignored, "" = the identity."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Iterable, List, Tuple
 
 
 def pauli_masks(text: str, num_q: int) -> Tuple[int, int]:
@@ -26,3 +27,26 @@ def pauli_masks(text: str, num_q: int) -> Tuple[int, int]:
         if letter in "ZY":
             z |= 1 << q
     return x, z
+
+
+def trotter_rotations(terms: Iterable, time: float, steps: int = 1, order: int = 1) -> List[Tuple[float, str]]:
+    """The rotations [(theta, string), ...] of a product formula for exp(-i H time), H = sum_k c_k P_k given as (c_k, string)
+    pairs with real c_k, first rotation first; exp(-i c dt P) is the rotation by theta = 2 c dt.
+    order 1: `steps` times the terms in order with dt = time / steps.  order 2: `steps` times the symmetric formula, the terms
+    forward and then in reverse, each by dt / 2.  ValueError for a complex coefficient, an order other than 1 or 2, steps < 1."""
+    if order not in (1, 2):
+        raise ValueError(f"product formula of order {order!r}: only 1 and 2 are built")
+    if int(steps) != steps or steps < 1:
+        raise ValueError(f"steps must be a positive integer, not {steps!r}")
+    pairs = []
+    for coeff, text in terms:
+        if isinstance(coeff, complex) or (hasattr(coeff, "dtype") and coeff.dtype.kind == "c"):
+            raise ValueError(f"coefficient {coeff!r} of {text!r} is complex: a Hamiltonian's coefficients are real")
+        pairs.append((float(coeff), text))
+    dt = float(time) / int(steps)
+    if order == 1:
+        one_step = [(2.0 * c * dt, text) for c, text in pairs]
+    else:
+        half = [(c * dt, text) for c, text in pairs]
+        one_step = half + half[::-1]
+    return one_step * int(steps)

@@ -163,6 +163,19 @@ def _pauli_term_masks(paulis, num_q: int):
     return xs, zs, xs.ctypes.data_as(up), zs.ctypes.data_as(up), np.array(where, dtype=np.intp)
 
 
+def _rotation_arrays(rotations, num_q: int):
+    """(theta, string) pairs as the arrays qsim_apply_pauli_rotations takes, in order: xs, zs, thetas and their pointers."""
+    from ctypes import c_uint64
+    from .pauli import pauli_masks
+    rotations = list(rotations)
+    masks = [pauli_masks(text, num_q) for _, text in rotations]
+    xs = np.array([m[0] for m in masks], dtype=np.uint64)
+    zs = np.array([m[1] for m in masks], dtype=np.uint64)
+    thetas = np.array([float(theta) for theta, _ in rotations], dtype=np.float64)
+    up = ctypes.POINTER(c_uint64)
+    return xs, zs, thetas, xs.ctypes.data_as(up), zs.ctypes.data_as(up), _dp(thetas)
+
+
 def _weighted_sum(terms, evaluate):
     """sum_t c_t <P_t> for (coefficient, string) pairs: a float when every coefficient is real, else a complex."""
     terms = list(terms)
@@ -369,6 +382,23 @@ class Simulator:
         every coefficient is real, else a complex."""
         return _weighted_sum(terms, self.expectation_terms)
 
+    # -- Pauli rotations
+    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
+        """state <- exp(-i theta/2 P) state for the Pauli string P ("X0 Y3 Z17", see pauli_masks)."""
+        self.apply_pauli_rotations([(theta, pauli)])
+
+    def apply_pauli_rotations(self, rotations) -> None:
+        """exp(-i theta/2 P) for every (theta, string) of `rotations`, the first one first, as ONE qsim_apply_pauli_rotations call:
+        consecutive strings with X/Y on the same qubits share a sweep of the state.  Returns without waiting."""
+        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
+        check(_lib.load().qsim_apply_pauli_rotations(self._h, xp, zp, tp, xs.size))
+
+    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
+        """A product formula for exp(-i H time) with H = sum_k c_k P_k given as (c_k, string) pairs, real c_k
+        (pauli.trotter_rotations builds the list: order 1 or 2, `steps` steps), applied as one call."""
+        from .pauli import trotter_rotations
+        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
+
     @property
     def device_ptr(self) -> int:
         return int(_lib.load().qsim_device_ptr(self._h) or 0)
@@ -475,6 +505,20 @@ class Cluster:
     def expectation(self, terms):
         """Simulator.expectation on the sharded state."""
         return _weighted_sum(terms, self.expectation_terms)
+
+    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
+        """Simulator.apply_pauli_rotation on the sharded state; the string names LOGICAL qubits."""
+        self.apply_pauli_rotations([(theta, pauli)])
+
+    def apply_pauli_rotations(self, rotations) -> None:
+        """Simulator.apply_pauli_rotations on the sharded state (qsim_cluster_apply_pauli_rotations)."""
+        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
+        self._check(_lib.load().qsim_cluster_apply_pauli_rotations(self._h, xp, zp, tp, xs.size))
+
+    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
+        """Simulator.evolve on the sharded state."""
+        from .pauli import trotter_rotations
+        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
 
     def sample(self, randoms) -> np.ndarray:
         """measurement() (quantum_simulator.c:270-283) on the sharded state, indices in logical order."""

@@ -165,6 +165,27 @@ int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const uint64_t *z
 /* Host only, no device: how many sweeps the call above makes for these terms. */
 int qsim_pauli_sweeps(const uint64_t *x_masks, long num_terms, long *sweeps);
 int qsim_pauli_terms_per_sweep(void); /* K: 32 ("Expectation values": the measured choice among 8, 16, 32) */
+/* ---- Pauli-string rotations exp(-i theta/2 P), applied on the device (new: the reference has neither observables nor rotations) ----
+ * The other half of qsim_expect_paulis: strings are the same two masks.  state <- prod_t exp(-i thetas[t]/2 P_t) state, t = 0
+ * first, in the caller's order (nothing is reordered, whether or not terms commute).  Convention: exp(-i theta/2 Z_q) =
+ * diag(e^(-i theta/2), e^(+i theta/2)) on qubit q, which is e^(-i theta/2) times the gate table's rz(theta) = diag(1, e^(i theta))
+ * (qsim_gate_matrix; quantum_simulator.c:184-211): the table drops the global phase, a rotation keeps it.  The identity string
+ * (x = z = 0) is that global phase e^(-i theta/2) alone.
+ * Routing: a term that is X or Y on ONE qubit is queued as its 2x2 (qsim_apply_1q: it fuses with neighbouring gates, no sweep).
+ * Every other term — single-qubit Z terms included — goes to an in-place sweep of the state (one read, one write, for a string of
+ * any weight), launched after the queued gates; a maximal run of consecutive sweep terms with equal x_mask shares sweeps, K =
+ * qsim_pauli_rotations_per_sweep() terms each, applied in registers in order (all-Z terms, x_mask = 0, are one such run).
+ * cos and sin of theta/2 are formed on the host in fp64 and rounded once to the state's precision, as gate matrices are.
+ * Returns without waiting: the sweeps are on qsim_stream(); no device allocation, no host synchronisation.  A sweep's grid is as
+ * many workgroups as are resident at once, each walking a grid-stride loop; QSIM_OPT_GRID_CAP > 0 caps it instead, as for every kernel.  Every amplitude is
+ * written by one thread: equal calls give equal bits.  Sweeps are NOT counted in the qsim_stats record: they have no QSIM_K_* class of their own, the
+ * struct keeps its layout; the queued 2x2s are, as gates.  A shard that holds nothing (qsim_holds_nothing) stays untouched.
+ * num_terms == 0 succeeds and does nothing.  QSIM_ERR_ARG, with the state unchanged: a NULL state, NULL arrays with num_terms > 0,
+ * a negative num_terms, a mask bit at or above the register's qubit count, a non-finite theta. */
+int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms);
+/* Host only, no device: what the call above does with these terms — sweeps launched and terms queued as 2x2 gates. */
+int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, long *sweeps, long *queued_as_gates);
+int qsim_pauli_rotations_per_sweep(void); /* K: 32, the one-bit-per-term masks' limit; an unmeasured default ("Pauli rotations") */
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
@@ -322,6 +343,15 @@ int qsim_cluster_norm2(qsim_cluster *c, double *out);
  * QSIM_ERR_ARG — a path that reads a peer's buffer or copies it over is missing — and terms whose X and Y sit on local qubits
  * work on any placement.  Every shard is flushed and its stream waited for first; per-shard results are added in shard order. */
 int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out);
+/* qsim_apply_pauli_rotations on a sharded state (fp64, as clusters are); masks are in LOGICAL qubits and are mapped through the
+ * cluster's qubit map.  Z on a qubit that is a shard-id bit is a sign per shard (it flips the sign of sin(theta/2) there).  X or Y
+ * there pairs shard r with shard r ^ x_rank: the member with the lower id sweeps all its local indices against the partner's buffer
+ * and writes both.  That needs every shard on ONE device (virtual shards): with shards on different devices such a term is refused
+ * with QSIM_ERR_ARG, the restriction of qsim_cluster_expect_paulis, and terms whose X and Y sit on local qubits work on any
+ * placement.  Before a cross-shard sweep every shard is flushed and its stream waited for; afterwards the partner's stream waits
+ * for the sweep.  A single X or Y on a LOCAL qubit is queued on every shard as its 2x2.  The cluster no longer counts as holding
+ * |0...0>: qsim_cluster_run_circuit needs a qsim_cluster_reset first. */
+int qsim_cluster_apply_pauli_rotations(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms);
 /* qsim_sample for a sharded state: basis indices in LOGICAL order for random numbers in [0,1] (measurement(),
  * quantum_simulator.c:270-283), whatever qubit map the exchanges left behind.  Every shard forms the |a|^2 sums of the
  * logical 2^12-amplitude blocks it holds a part of on its own device (qsim_block_prob_masked); the host adds the P
@@ -401,6 +431,10 @@ int qsim_rank_comm_loopback(qsim_rank_comm *c, uint64_t count);
 
 int qsim_get_stats(qsim_state *s, qsim_stats *out); /* waits for outstanding profile events */
 int qsim_reset_stats(qsim_state *s);
+/* Test and measurement aid, not part of what the rotation call promises: rotation sweeps (qsim_apply_pauli_rotations and the
+ * cluster's) launched by this process so far.  One process-wide counter for all states and shards together, which qsim_stats
+ * does not have and qsim_reset_stats does not clear: take differences, and only where one thread applies rotations. */
+uint64_t qsim_pauli_rotation_sweeps_launched(void);
 /* Per-launch record (QSIM_OPT_PROFILE=1) since the last qsim_reset_stats: returns the number of records and,
  * for 0 <= index < count, fills the kernel class, the fused blocks in that launch, the tile's high-qubit
  * mask and the HIP-event time. */
