@@ -544,6 +544,32 @@ extern "C" int qsim_cluster_norm2(qsim_cluster *c, double *out) {
     return QSIM_OK;
 }
 
+// What the two Pauli entry points open with: the argument checks (`third`: the results or the angles; `thetas`: the angles, where
+// there are any), every mask mapped from logical qubits through `pos` into X and Z, and the refusal to pair shards across devices.
+static int physical_terms(qsim_cluster *c, const char *who, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *thetas,
+                          long num_terms, std::vector<uint64_t> &X, std::vector<uint64_t> &Z) {
+    if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
+    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "%s: negative term count", who);
+    if (num_terms == 0) return QSIM_OK;
+    if (!x_masks || !z_masks || !third) return cfail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    const uint64_t nmask = qsim::index_mask(c->n);
+    X.resize((size_t)num_terms), Z.resize((size_t)num_terms);
+    for (long t = 0; t < num_terms; t++) {
+        if ((x_masks[t] | z_masks[t]) & ~nmask) return cfail(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, c->n);
+        if (thetas && !std::isfinite(thetas[t])) return cfail(QSIM_ERR_ARG, "%s: term %ld has a non-finite angle", who, t);
+        X[(size_t)t] = physical_index(c, x_masks[t]);
+        Z[(size_t)t] = physical_index(c, z_masks[t]);
+        if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)
+            return cfail(QSIM_ERR_ARG,
+                         "%s: term %ld has X or Y on a qubit that currently selects the shard, and the shards are on "
+                         "different devices: reading a partner shard across devices is not implemented",
+                         who, t);
+    }
+    return QSIM_OK;
+}
+// x_rank pairs shard r with shard r ^ xr: the member with the highest bit of xr clear does the pair's work, the other one nothing
+static bool sweeps_pair(int r, uint64_t xr) { return (((uint64_t)r >> (63 - __builtin_clzll(xr))) & 1ULL) == 0; }
+
 // <psi|P_t|psi> on the sharded state.  Masks arrive in logical qubits; mapped through `pos` they split into local index bits
 // (< m) and shard-id bits.  Z on shard-id bits is a sign per shard.  X on shard-id bits (x_rank) pairs shard r with shard
 // r ^ x_rank: over the whole register the sum runs over the indices with the highest bit of x clear, and that bit is then a
@@ -551,23 +577,9 @@ extern "C" int qsim_cluster_norm2(qsim_cluster *c, double *out) {
 // the other one does nothing.  With x_rank == 0 every shard sweeps its own half (highest LOCAL bit of x clear).  Either way
 // every amplitude is read once.  A partner buffer is only readable in place when both shards are on one device.
 extern "C" int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out) {
-    if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
-    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: negative term count");
+    std::vector<uint64_t> X, Z;
+    if (const int rc = physical_terms(c, "qsim_cluster_expect_paulis", x_masks, z_masks, out, nullptr, num_terms, X, Z)) return rc;
     if (num_terms == 0) return QSIM_OK;
-    if (!x_masks || !z_masks || !out) return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: NULL argument");
-    const uint64_t nmask = qsim::index_mask(c->n);
-    std::vector<uint64_t> X((size_t)num_terms), Z((size_t)num_terms);
-    for (long t = 0; t < num_terms; t++) {
-        if ((x_masks[t] | z_masks[t]) & ~nmask)
-            return cfail(QSIM_ERR_ARG, "qsim_cluster_expect_paulis: term %ld names a qubit outside the %d-qubit register", t, c->n);
-        X[(size_t)t] = physical_index(c, x_masks[t]);
-        Z[(size_t)t] = physical_index(c, z_masks[t]);
-        if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)
-            return cfail(QSIM_ERR_ARG,
-                         "qsim_cluster_expect_paulis: term %ld has X or Y on a qubit that currently selects the shard, and the shards are on "
-                         "different devices: reading a partner shard across devices is not implemented",
-                         t);
-    }
     // a shard's buffer is about to be read from another shard's stream: everything queued must have run, lazily held states
     // must have been written
     for (qsim_state *s : c->shard)
@@ -582,7 +594,7 @@ extern "C" int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_mas
     std::vector<double> part;
     for (int r = 0; r < c->P; r++)
         for (const uint64_t xr : ranks_x) {
-            if (xr != 0 && (((uint64_t)r >> (63 - __builtin_clzll(xr))) & 1ULL)) continue; // its partner counts the pair
+            if (xr != 0 && !sweeps_pair(r, xr)) continue; // its partner counts the pair
             gx.clear(), gz.clear(), gt.clear();
             for (long t = 0; t < num_terms; t++)
                 if ((X[(size_t)t] >> c->m) == xr) gx.push_back(X[(size_t)t]), gz.push_back(Z[(size_t)t]), gt.push_back(t);
@@ -601,24 +613,10 @@ extern "C" int qsim_cluster_expect_paulis(qsim_cluster *c, const uint64_t *x_mas
 // against its partner's buffer and writes both; the other member does nothing.  For that every shard has been settled and its
 // stream waited for, and afterwards the partner's stream waits for the sweep that wrote its buffer.
 extern "C" int qsim_cluster_apply_pauli_rotations(qsim_cluster *c, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms) {
-    if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
-    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: negative term count");
+    std::vector<uint64_t> X, Z;
+    if (const int rc = physical_terms(c, "qsim_cluster_apply_pauli_rotations", x_masks, z_masks, thetas, thetas, num_terms, X, Z)) return rc;
     if (num_terms == 0) return QSIM_OK;
-    if (!x_masks || !z_masks || !thetas) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: NULL argument");
-    const uint64_t nmask = qsim::index_mask(c->n), mmask = qsim::index_mask(c->m);
-    std::vector<uint64_t> X((size_t)num_terms), Z((size_t)num_terms);
-    for (long t = 0; t < num_terms; t++) {
-        if ((x_masks[t] | z_masks[t]) & ~nmask)
-            return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: term %ld names a qubit outside the %d-qubit register", t, c->n);
-        if (!std::isfinite(thetas[t])) return cfail(QSIM_ERR_ARG, "qsim_cluster_apply_pauli_rotations: term %ld has a non-finite angle", t);
-        X[(size_t)t] = physical_index(c, x_masks[t]);
-        Z[(size_t)t] = physical_index(c, z_masks[t]);
-        if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)
-            return cfail(QSIM_ERR_ARG,
-                         "qsim_cluster_apply_pauli_rotations: term %ld has X or Y on a qubit that currently selects the shard, and the shards are on "
-                         "different devices: reading a partner shard across devices is not implemented",
-                         t);
-    }
+    const uint64_t mmask = qsim::index_mask(c->m);
     c->fresh = false; // the state is no longer |0...0>: a circuit needs a reset first
     uint64_t paired_by = 0; // the x_rank all shards are settled and waited for (0: not)
     for (const qsim::RotRoute &rt : qsim::route_rotations(X.data(), Z.data(), num_terms, mmask)) {
@@ -649,7 +647,7 @@ extern "C" int qsim_cluster_apply_pauli_rotations(qsim_cluster *c, const uint64_
             }
         paired_by = xr;
         for (int r = 0; r < c->P; r++) {
-            if (((uint64_t)r >> (63 - __builtin_clzll(xr))) & 1ULL) continue; // its partner sweeps the pair
+            if (!sweeps_pair(r, xr)) continue; // its partner sweeps the pair
             qsim_state *s = c->shard[(size_t)r], *other = c->shard[(size_t)((uint64_t)r ^ xr)];
             if (qsim_holds_nothing(s) && qsim_holds_nothing(other)) continue;
             void *partner = qsim_state_buffer(other);

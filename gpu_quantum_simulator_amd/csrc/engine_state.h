@@ -3,8 +3,9 @@
 // qsim_internal.h, never this.  Who defines what:
 //   engine.cpp    errors, create / destroy, options, reset / support, the gate queue, launch_pass, the plan cache, the flush
 //   planning.cpp  the measured tile-bit orders and schedule choices (process-wide tables, private to it) and the planning API
-//   readout.cpp   reads, writes, norms, expectation values, sampling        pack.cpp  re-layouts and buffer hand-overs
-//   profile.cpp   profiling events, statistics, the launch log              evolve.cpp  Pauli-string rotations (the host side of evolve.hip)
+//   readout.cpp   reads, writes, norms, sampling                             pack.cpp  re-layouts and buffer hand-overs
+//   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values and rotations
+//                                                                           (the host side of expect.hip and evolve.hip; pauli_sweep.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 

@@ -1,0 +1,219 @@
+// pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values") and
+// rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations").  pauli_sweep.h has what the
+// two kinds of sweep share.  Every entry point opens with settle() and then only touches qsim_state's buffer, stream and
+// d_expect; expectation values read the buffer, rotations write it.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdlib>
+
+#include "engine_state.h"
+#include "pauli_sweep.h"
+
+using namespace qsim;
+
+// ---- what both kinds share ----------------------------------------------------------------------------------------------------
+// i^k is real (k even) or imaginary (k odd); its non-zero component: 1, 1, -1, -1 for k = 0, 1, 2, 3 mod 4
+static double pauli_phase(int k) { return (k & 2) ? -1.0 : 1.0; }
+// <P> = i^ny (c + (-1)^ny conj c) summed over the pairs = 2 i^ny Re c (ny even) or 2 i^(ny+1) Im c (odd): 2 Re c, -2 Im c, -2 Re c,
+// 2 Im c for ny = 0, 1, 2, 3 mod 4; x == 0: the plain signed norm
+static double expect_factor(uint64_t x, int ny) { return x == 0 ? 1.0 : 2.0 * pauli_phase(ny + (ny & 1)); }
+// w = -i sin(theta/2) i^ny = i^(ny+3) sin(theta/2): -i sn, sn, i sn, -sn for ny = 0, 1, 2, 3 mod 4; v is its non-zero component
+static double rotation_v(int ny, double sn) { return pauli_phase(ny + 3) * sn; }
+// Z on rank qubits (mask bits from m up): a sign per shard
+static double rank_sign(uint64_t rank, uint64_t z, int m) { return (__builtin_popcountll(rank & (z >> m)) & 1) ? -1.0 : 1.0; }
+
+// The argument checks of the two single-state entry points; `third` is the array that goes with the masks (results or angles),
+// `thetas` the angles where there are any.
+static int check_terms(const char *who, const qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *thetas,
+                       long num_terms) {
+    if (!s) return fail(QSIM_ERR_ARG, "NULL state");
+    if (num_terms < 0) return fail(QSIM_ERR_ARG, "%s: negative term count", who);
+    if (num_terms > 0 && (!x_masks || !z_masks || !third)) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    const uint64_t nmask = index_mask(s->n);
+    for (long t = 0; t < num_terms; t++) {
+        if ((x_masks[t] | z_masks[t]) & ~nmask) return fail(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, s->n);
+        if (thetas && !std::isfinite(thetas[t])) return fail(QSIM_ERR_ARG, "%s: term %ld has a non-finite angle", who, t);
+    }
+    return QSIM_OK;
+}
+
+// ---- expectation values ---------------------------------------------------------------------------------------------------------
+// Terms per sweep: kPauliTermsPerSweep by measurement (DESIGN); QSIM_PAULI_TERMS_PER_SWEEP = 8 | 16 | 32 in the environment
+// overrides it for tools/expect_bench.py, which times the candidates against each other.
+static constexpr int kPauliTermsPerSweep = 32;
+static int pauli_terms_per_sweep() {
+    static const int k = [] {
+        const char *e = getenv("QSIM_PAULI_TERMS_PER_SWEEP");
+        const int v = e ? atoi(e) : 0;
+        return v == 8 || v == 16 || v == 32 ? v : kPauliTermsPerSweep;
+    }();
+    return k;
+}
+extern "C" int qsim_pauli_terms_per_sweep(void) { return pauli_terms_per_sweep(); }
+
+// The sweeps of a term list: terms in order of x (equal x: caller's order), every run of equal x cut into pieces of K.
+struct PauliSweeps {
+    std::vector<long> order;                     // term indices, grouped
+    std::vector<std::pair<long, int>> sweeps;    // (first position in `order`, terms)
+};
+static PauliSweeps pauli_sweeps(const uint64_t *x, uint64_t x_keep, long num) {
+    PauliSweeps p;
+    p.order.resize((size_t)num);
+    for (long t = 0; t < num; t++) p.order[(size_t)t] = t;
+    std::stable_sort(p.order.begin(), p.order.end(), [&](long a, long b) { return (x[a] & x_keep) < (x[b] & x_keep); });
+    const int K = pauli_terms_per_sweep();
+    for (long i = 0; i < num;) {
+        long e = i + 1;
+        while (e < num && (x[p.order[(size_t)e]] & x_keep) == (x[p.order[(size_t)i]] & x_keep)) e++;
+        for (; i < e; i += K) p.sweeps.emplace_back(i, (int)std::min<long>(K, e - i));
+        i = e;
+    }
+    return p;
+}
+
+extern "C" int qsim_pauli_sweeps(const uint64_t *x_masks, long num_terms, long *sweeps) {
+    if (!sweeps || num_terms < 0 || (num_terms > 0 && !x_masks)) return fail(QSIM_ERR_ARG, "qsim_pauli_sweeps: bad argument");
+    *sweeps = (long)pauli_sweeps(x_masks, ~0ULL, num_terms).sweeps.size();
+    return QSIM_OK;
+}
+
+int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *X, const uint64_t *Z, long num, double *out) {
+    if (!s || num < 0 || (num > 0 && (!X || !Z || !out))) return fail(QSIM_ERR_ARG, "expectation: NULL argument or negative term count");
+    if (num == 0) return QSIM_OK;
+    const int m = s->n;
+    const uint64_t mmask = index_mask(m), x_rank = X[0] >> m;
+    for (long t = 0; t < num; t++)
+        if ((X[t] >> m) != x_rank) return fail(QSIM_ERR_ARG, "expectation: terms of one shard call must pair the same shards");
+    if ((x_rank != 0) != (partner != nullptr)) return fail(QSIM_ERR_ARG, "expectation: a partner buffer goes with x on rank qubits, and only with it");
+    QSIM_TRY(settle(s));
+    constexpr int kBatch = 128; // sweeps whose results travel in one copy
+    constexpr int kSlots = kMaxPauliTermsPerSweep;
+    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kBatch * kSlots) * sizeof(double)));
+    double *d_results = s->d_expect + kExpectPartialDoubles;
+    const PauliSweeps plan = pauli_sweeps(X, mmask, num);
+    std::vector<double> host((size_t)kBatch * kSlots);
+    LaunchCfg cfg{s->stream, s->grid_cap};
+    for (size_t first = 0; first < plan.sweeps.size(); first += kBatch) {
+        const size_t last = std::min(plan.sweeps.size(), first + (size_t)kBatch);
+        for (size_t w = first; w < last; w++) {
+            ExpectSweep sw{};
+            sw.x = X[plan.order[(size_t)plan.sweeps[w].first]] & mmask;
+            sw.full = x_rank != 0;
+            sw.count = plan.sweeps[w].second;
+            for (int k = 0; k < sw.count; k++) {
+                const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
+                sw.z[k] = Z[t] & mmask;
+                if (__builtin_popcountll(X[t] & Z[t]) & 1) sw.im_mask |= 1u << k;
+            }
+            HIP_TRY(launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, s->d_expect, d_results + (w - first) * kSlots));
+        }
+        HIP_TRY(hipMemcpyAsync(host.data(), d_results, (last - first) * kSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (size_t w = first; w < last; w++)
+            for (int k = 0; k < plan.sweeps[w].second; k++) {
+                const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
+                const double f = expect_factor(X[t], __builtin_popcountll(X[t] & Z[t])) * rank_sign(rank, Z[t], m);
+                out[t] = f * host[(w - first) * kSlots + (size_t)k];
+            }
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out) {
+    QSIM_TRY(check_terms("qsim_expect_paulis", s, x_masks, z_masks, out, nullptr, num_terms));
+    return expect_paulis_shard(s, nullptr, 0, x_masks, z_masks, num_terms, out);
+}
+
+// ---- rotations ------------------------------------------------------------------------------------------------------------------
+// A term that is X or Y on a single qubit is a 2x2 for the gate queue; every other term goes to an in-place sweep, and consecutive
+// sweep terms with one x mask share a sweep.
+// Terms per sweep: 32, the record count of k_pauli_rot; not backed by a measurement yet (DESIGN "Pauli rotations").
+static constexpr int kPauliRotationsPerSweep = kMaxPauliTermsPerSweep;
+extern "C" int qsim_pauli_rotations_per_sweep(void) { return kPauliRotationsPerSweep; }
+
+static std::atomic<uint64_t> g_sweeps_launched{0};
+extern "C" uint64_t qsim_pauli_rotation_sweeps_launched(void) { return g_sweeps_launched.load(); }
+
+long qsim::rotation_sweeps(long run_length) { return (run_length + kPauliRotationsPerSweep - 1) / kPauliRotationsPerSweep; }
+
+static bool is_gate(uint64_t x, uint64_t z, uint64_t local_mask) {
+    return __builtin_popcountll(x) == 1 && (z & ~x) == 0 && (x & local_mask) != 0;
+}
+
+std::vector<RotRoute> qsim::route_rotations(const uint64_t *X, const uint64_t *Z, long num, uint64_t local_mask) {
+    std::vector<RotRoute> out;
+    for (long t = 0; t < num;) {
+        if (is_gate(X[t], Z[t], local_mask)) {
+            out.push_back({t, 1, true});
+            t++;
+            continue;
+        }
+        long e = t + 1;
+        while (e < num && X[e] == X[t] && !is_gate(X[e], Z[e], local_mask)) e++;
+        out.push_back({t, e - t, false});
+        t = e;
+    }
+    return out;
+}
+
+void qsim::pauli_rot_1q(bool y, double theta, double *U) {
+    const double c = std::cos(0.5 * theta), sn = std::sin(0.5 * theta);
+    const double ux[8] = {c, 0, 0, -sn, 0, -sn, c, 0}, uy[8] = {c, 0, -sn, 0, sn, 0, c, 0};
+    std::copy(y ? uy : ux, (y ? uy : ux) + 8, U);
+}
+
+int qsim::pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x, const uint64_t *Z, const double *thetas, long count) {
+    if (!s || count < 0 || (count > 0 && (!Z || !thetas))) return fail(QSIM_ERR_ARG, "rotation: NULL argument or negative term count");
+    const int m = s->n;
+    const uint64_t mmask = index_mask(m);
+    if (((x >> m) != 0) != (partner != nullptr)) return fail(QSIM_ERR_ARG, "rotation: a partner buffer goes with x on rank qubits, and only with it");
+    if (count == 0 || (!partner && qsim_holds_nothing(s))) return QSIM_OK; // rotations map the zero vector to itself
+    QSIM_TRY(settle(s));
+    HIP_TRY(hipSetDevice(s->device)); // a cluster drives several devices from one thread, and settle() may have had nothing to do
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    for (long first = 0; first < count; first += kPauliRotationsPerSweep) {
+        RotSweep sw{};
+        sw.x = x & mmask;
+        sw.full = partner != nullptr;
+        sw.count = (int)std::min<long>(kPauliRotationsPerSweep, count - first);
+        for (int k = 0; k < sw.count; k++) {
+            const uint64_t z = Z[first + k];
+            const double half = 0.5 * thetas[first + k];
+            const int ny = __builtin_popcountll(x & z);
+            sw.z[k] = z & mmask;
+            sw.c[k] = std::cos(half);
+            sw.v[k] = rotation_v(ny, std::sin(half)) * rank_sign(rank, z, m);
+            if (ny & 1) sw.odd_mask |= 1u << k;
+        }
+        const hipError_t e = launch_pauli_rot(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw);
+        if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "rotation sweep launch failed: %s", hipGetErrorString(e));
+        g_sweeps_launched++;
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, long *sweeps, long *queued_as_gates) {
+    if (num_terms < 0) return fail(QSIM_ERR_ARG, "qsim_pauli_rotation_plan: negative term count");
+    if (!sweeps || !queued_as_gates || (num_terms > 0 && (!x_masks || !z_masks))) return fail(QSIM_ERR_ARG, "qsim_pauli_rotation_plan: NULL argument");
+    *sweeps = *queued_as_gates = 0;
+    for (const RotRoute &r : route_rotations(x_masks, z_masks, num_terms, ~0ULL)) {
+        if (r.gate) ++*queued_as_gates;
+        else *sweeps += rotation_sweeps(r.count);
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms) {
+    QSIM_TRY(check_terms("qsim_apply_pauli_rotations", s, x_masks, z_masks, thetas, thetas, num_terms));
+    for (const RotRoute &r : route_rotations(x_masks, z_masks, num_terms, index_mask(s->n))) {
+        if (r.gate) {
+            double U[8];
+            pauli_rot_1q((z_masks[r.first] & x_masks[r.first]) != 0, thetas[r.first], U);
+            QSIM_TRY(qsim_apply_1q(s, U, __builtin_ctzll(x_masks[r.first])));
+        } else {
+            QSIM_TRY(pauli_rot_run(s, nullptr, 0, x_masks[r.first], z_masks + r.first, thetas + r.first, r.count));
+        }
+    }
+    return QSIM_OK;
+}

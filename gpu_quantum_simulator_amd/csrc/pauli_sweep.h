@@ -1,0 +1,142 @@
+// pauli_sweep.h — how a Pauli sweep walks a state: what expect.hip (<psi|P|psi>, read-only), evolve.hip (exp(-i theta/2 P), in
+// place) and their host side pauli.cpp share.  DESIGN §7b opens with the same account.
+//
+// A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
+// pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets
+// the other one as its partner; x == 0 visits every index and has no partner.  `full`: the pair's highest x bit selects the shard,
+// so every index of buffer a is visited and its partner j ^ x lies in ANOTHER buffer b.  All strings of one sweep share x.
+//
+// Work is dealt in UNITS of 16 bytes per lane (one fp64 amplitude, two fp32 amplitudes), consecutive lanes on consecutive units;
+// the partner unit (j ^ x) permutes the same 128-byte lines, so both streams stay coalesced for any x.  A unit index
+// t = (q << kTidBits) | tid is expanded to an amplitude index by a bit insertion (the zero at bit h), which is linear over OR of
+// disjoint bit sets: popcount(j & z) = popcount(E(q << kTidBits) & z) + popcount(E(tid) & z) (+ z bit 0 for the odd fp32 slot).
+// The first part is uniform over the workgroup (scalar unit), the second is constant per thread.
+// fp32 corners: x odd puts the partner in the other half of its unit (each kernel swaps the halves itself, in one line: as a shared
+// inline function the swap changed the instruction schedule of the fp32 paired k_expect instantiations); x == 1 on one state puts
+// both members of a pair in ONE unit (odd_slot == 0: every unit is visited, its even slot is j); a register of one amplitude is 8
+// bytes long, no unit (k_expect guards its loads, k_pauli_rot takes a single-thread path of its own).
+//
+// Grids.  Every workgroup of a sweep walks the same number of trips, so a second, partly filled round of workgroups would cost a
+// whole round: the default grid is what is resident at once (resident_grid).  The two kernels cap it differently, on purpose:
+// an expectation sweep at kExpectGrid rows whatever LaunchCfg::grid_cap says, because its partial-sum buffer is sized by that; a
+// rotation sweep at grid_cap when one is set (QSIM_OPT_GRID_CAP, as for every other kernel), and at 1024 when the occupancy
+// query fails.
+#ifndef QSIM_PAULI_SWEEP_H
+#define QSIM_PAULI_SWEEP_H
+
+#include "qsim_internal.h"
+
+namespace qsim {
+
+// ---- sweep descriptors: what pauli.cpp hands to the launchers ---------------------------------------------------------------
+constexpr int kMaxPauliTermsPerSweep = 32; // slots of the largest k_expect instantiation and term records of k_pauli_rot;
+                                           // qsim_pauli_terms_per_sweep() / qsim_pauli_rotations_per_sweep() is what a call uses
+struct PauliSweep {
+    uint64_t x;
+    bool full;
+    int count;      // strings, all with this x; a rotation sweep applies them in order
+    uint64_t z[kMaxPauliTermsPerSweep];
+};
+struct ExpectSweep : PauliSweep {
+    uint32_t im_mask; // bit k: term k takes Im(conj(psi_j^x) psi_j) instead of Re
+};
+// Term k: c = cos(theta/2) and the real number v with w = -i sin(theta/2) i^ny = v (ny = popcount(x & z) odd, bit k of odd_mask)
+// or i v (even); a sign per shard is folded into v.  full: a != b; otherwise a == b.
+struct RotSweep : PauliSweep {
+    double c[kMaxPauliTermsPerSweep], v[kMaxPauliTermsPerSweep];
+    uint32_t odd_mask;
+};
+
+constexpr int kExpectGrid = 1024;     // workgroups of an expectation sweep at most = rows of partial sums (4 per CU)
+constexpr size_t kExpectPartialDoubles = (size_t)kExpectGrid * kMaxPauliTermsPerSweep;
+int expect_slots(int count); // term slots of the instantiation a sweep of `count` terms runs in (1, 8, 16, 32)
+// d_out[k] = sum_j s_k(j) |a_j|^2 (x == 0 and not full) or sum_j s_k(j) Re/Im(conj(b_(j^x)) a_j), for k < expect_slots(count);
+// d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.
+hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, bool f32, int n, const ExpectSweep &sw, double *d_partial,
+                         double *d_out);
+// a_j' = c a_j + w (-1)^ny s(j) b_(j^x),  b_(j^x)' = c b_(j^x) + w s(j) a_j, term after term.
+hipError_t launch_pauli_rot(const LaunchCfg &cfg, void *a, void *b, bool f32, int n, const RotSweep &sw);
+
+// the partner index and every z must stay inside the buffer of 2^n amplitudes
+inline bool check_sweep(const PauliSweep &sw, int n) {
+    if (sw.count < 1 || sw.count > kMaxPauliTermsPerSweep || n < 0 || n > 40) return false;
+    const uint64_t N = 1ULL << n;
+    if (sw.x >= N) return false;
+    for (int k = 0; k < sw.count; k++)
+        if (sw.z[k] >= N) return false;
+    return true;
+}
+
+// ---- geometry -----------------------------------------------------------------------------------------------------------------
+constexpr int kTPB = 256;                     // 4 waves; a unit index's low 8 bits are the thread
+constexpr int kTidBits = 8;
+static_assert((1 << kTidBits) == kTPB, "unit index = (q << kTidBits) | tid");
+// units per thread and trip: 8 independent 16-byte loads in flight (a paired sweep loads two units per unit visited)
+constexpr int units_per_trip(bool paired) { return paired ? 4 : 8; }
+
+struct SweepGeom {      // by value: a kernel argument
+    uint64_t units;     // 16-byte units to visit
+    uint64_t low;       // unit-index bits below the inserted zero (all ones: nothing inserted)
+    uint64_t x;         // partner amplitude = amplitude ^ x
+    uint64_t amps;      // amplitudes in the buffer (guards the one-amplitude fp32 register)
+    uint32_t odd_slot;  // fp32: the odd amplitude of a unit is visited too (0 only for x == 1 on one state: both members share the unit)
+};
+
+inline SweepGeom sweep_geom(uint64_t x, bool full, bool f32, int n) {
+    const uint64_t N = 1ULL << n;
+    const int as = f32 ? 1 : 0; // log2 amplitudes per unit
+    SweepGeom g{};
+    g.x = x;
+    g.amps = N;
+    g.odd_slot = 1;
+    g.low = ~0ULL;
+    uint64_t amps_visited = N;
+    if (x != 0 && !full) { // one member of each pair: the index with the highest bit of x clear
+        const int h = 63 - __builtin_clzll(x);
+        amps_visited = N >> 1;
+        if (h >= as) g.low = (1ULL << (h - as)) - 1ULL; // the zero is inserted at unit bit h - as
+        else g.odd_slot = 0;                            // fp32, x == 1: every unit, one pair each
+    }
+    g.units = g.odd_slot ? (amps_visited >> as) : N >> as;
+    if (g.units == 0) g.units = 1; // one fp32 amplitude
+    return g;
+}
+
+// Workgroups of Kernel (kTPB threads, no dynamic LDS) resident at once, 0 when the query fails.  One figure per kernel and
+// process: the devices of a cluster are of one kind.
+template <auto Kernel>
+int resident_grid() {
+    static const int grid = [] {
+        int dev = 0, per_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, kTPB, 0) != hipSuccess || per_cu < 1)
+            return 0;
+        return per_cu * prop.multiProcessorCount;
+    }();
+    return grid;
+}
+
+// ---- device helpers -----------------------------------------------------------------------------------------------------------
+template <typename R> struct Vec16;
+template <> struct Vec16<double> { using type = double2; };
+template <> struct Vec16<float> { using type = float4; };
+
+__device__ __forceinline__ double flip(double v, uint32_t sign_bit31) {
+    return __hiloint2double(__double2hiint(v) ^ (int)sign_bit31, __double2loint(v));
+}
+__device__ __forceinline__ float flip(float v, uint32_t sign_bit31) { return __uint_as_float(__float_as_uint(v) ^ sign_bit31); }
+
+// unit index -> its (even) amplitude index
+template <typename R>
+__device__ __forceinline__ uint64_t expand(const SweepGeom &g, uint64_t t) {
+    return (((t & ~g.low) << 1) | (t & g.low)) << (sizeof(R) == 8 ? 0 : 1);
+}
+// the unit that holds amplitude `amp` (even for fp32)
+template <typename R>
+__device__ __forceinline__ typename Vec16<R>::type load_unit(const R *p, uint64_t amp) {
+    return *reinterpret_cast<const typename Vec16<R>::type *>(p + 2 * amp);
+}
+
+} // namespace qsim
+#endif

@@ -185,54 +185,18 @@ hipError_t launch_gather_masked(const LaunchCfg &cfg, const void *v, bool f32, u
 hipError_t launch_pack(const LaunchCfg &cfg, const void *in, void *out, void *const *blocks, bool f32, int n, const int *bits, int p, uint32_t skip_blocks = 0,
                        uint64_t zero_mask = 0);
 
-// ---- expect.hip: Pauli-string expectation sweeps (read-only; DESIGN "Expectation values") ----------------------------------
-constexpr int kMaxTermsPerSweep = 32; // slots of the largest k_expect instantiation; qsim_pauli_terms_per_sweep() is what a call uses
-constexpr int kExpectGrid = 1024;     // workgroups of a sweep at most = rows of partial sums (4 per CU)
-constexpr size_t kExpectPartialDoubles = (size_t)kExpectGrid * kMaxTermsPerSweep;
-// One sweep: `count` strings that share x.  `full`: every index j of the buffer counts (a shard whose partner buffer is another
-// shard's: the pair's highest x bit is a rank bit); otherwise, for x != 0, only the j with the highest bit of x clear.
-struct ExpectSweep {
-    uint64_t x;
-    bool full;
-    int count;
-    uint64_t z[kMaxTermsPerSweep];
-    uint32_t im_mask; // bit k: term k takes Im(conj(psi_j^x) psi_j) instead of Re
-};
-int expect_slots(int count); // term slots of the instantiation a sweep of `count` terms runs in (1, 8, 16, 32)
-// d_out[k] = sum_j s_k(j) |a_j|^2 (x == 0 and not full) or sum_j s_k(j) Re/Im(conj(b_(j^x)) a_j), for k < expect_slots(count);
-// d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.
-hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, bool f32, int n, const ExpectSweep &sw, double *d_partial,
-                         double *d_out);
-// readout.cpp: <P_t> restricted to one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s)
-// bits of the masks; every term has the same x above them (x_rank).  x_rank != 0: `partner` is the buffer of shard
-// rank ^ x_rank (quiescent, materialised) and every local index is swept; NULL: the state itself.  Adds nothing up across shards.
+// ---- pauli.cpp: Pauli strings on one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s) bits
+// of the masks (pauli_sweep.h has the sweeps themselves).  A partner is the buffer of shard rank ^ x_rank, quiescent, materialised
+// and on the same device; it goes with x on rank qubits (x_rank != 0) and only with it, and then every local index is swept.
+// <P_t> restricted to the shard; every term has the same x_rank.  Adds nothing up across shards.
 int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms,
                         double *out);
-
-// ---- evolve.hip: Pauli-string rotations exp(-i theta/2 P) as in-place sweeps (DESIGN "Pauli rotations") -------------------
-constexpr int kMaxRotTermsPerSweep = 32; // term records of k_pauli_rot; qsim_pauli_rotations_per_sweep() is what a call uses
-// One sweep: `count` consecutive rotations that share x, applied in order.  Term k: c = cos(theta/2) and the real number v with
-// w = -i sin(theta/2) i^ny = v (ny = popcount(x & z) odd, bit k of odd_mask) or i v (even); a sign per shard is folded into v.
-// `full`: every index j of buffer a is paired with index j ^ x of ANOTHER buffer b (a shard and its partner shard: the pair's
-// highest x bit is a rank bit); otherwise a == b and, for x != 0, j runs over the indices with the highest bit of x clear.
-struct RotSweep {
-    uint64_t x;
-    bool full;
-    int count;
-    uint64_t z[kMaxRotTermsPerSweep];
-    double c[kMaxRotTermsPerSweep], v[kMaxRotTermsPerSweep];
-    uint32_t odd_mask;
-};
-// a_j' = c a_j + w (-1)^ny s(j) b_(j^x),  b_(j^x)' = c b_(j^x) + w s(j) a_j  with s(j) = (-1)^popcount(j & z), term after term.
-hipError_t launch_pauli_rot(const LaunchCfg &cfg, void *a, void *b, bool f32, int n, const RotSweep &sw);
-// evolve.cpp: how a list of rotations is carried out, in the caller's order.  A term that is X or Y on ONE qubit inside
+// How a list of rotations exp(-i theta/2 P) is carried out, in the caller's order.  A term that is X or Y on ONE qubit inside
 // local_mask is a gate for the queue; every other term belongs to a run: a maximal stretch of consecutive such terms with equal x.
 struct RotRoute { long first, count; bool gate; };
 std::vector<RotRoute> route_rotations(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, uint64_t local_mask);
 long rotation_sweeps(long run_length); // ceil(run_length / K)
-// One run on one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s) bits of the masks;
-// x carries the run's rank bits too.  partner != NULL (x has rank bits): the buffer of shard rank ^ x_rank, quiescent and
-// materialised, on the same device; every local index is swept.  Launches on the state's stream and returns.
+// One run; x carries the run's rank bits too.  Launches on the state's stream and returns.
 int pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x, const uint64_t *z_masks, const double *thetas, long count);
 // The 2x2 of exp(-i theta/2 X) (y == false) or exp(-i theta/2 Y) as qsim_apply_1q takes it.
 void pauli_rot_1q(bool y, double theta, double *U);

@@ -1,6 +1,6 @@
-// readout.cpp — everything that looks at a state without changing it, plus qsim_write: amplitudes in and out, the norm,
-// expectation values of Pauli strings (the host side of expect.hip's sweeps) and the measurement post-path (sampling, block
-// sums and gathers).  Every entry point opens with settle() or qsim_sync (engine.cpp) and then only reads qsim_state's buffer,
+// readout.cpp — everything that looks at a state's amplitudes without changing it, plus qsim_write: amplitudes in and out, the
+// norm and the measurement post-path (sampling, block sums and gathers); expectation values of Pauli strings are pauli.cpp's.
+// Every entry point opens with settle() or qsim_sync (engine.cpp) and then only reads qsim_state's buffer,
 // stream and scratch; nothing here touches the gate queue, the plans or the planning tables.
 #include <algorithm>
 #include <cstdlib>
@@ -70,101 +70,6 @@ extern "C" int qsim_norm2(qsim_state *s, double *out) {
     HIP_TRY(hipMemcpyAsync(out, s->d_scalar, 8, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return QSIM_OK;
-}
-
-// ---- expectation values of Pauli strings (expect.hip; DESIGN "Expectation values") ----------------------------------------------
-// Terms per sweep: kPauliTermsPerSweep by measurement (DESIGN); QSIM_PAULI_TERMS_PER_SWEEP = 8 | 16 | 32 in the environment
-// overrides it for tools/expect_bench.py, which times the candidates against each other.
-static constexpr int kPauliTermsPerSweep = 32;
-static int pauli_terms_per_sweep() {
-    static const int k = [] {
-        const char *e = getenv("QSIM_PAULI_TERMS_PER_SWEEP");
-        const int v = e ? atoi(e) : 0;
-        return v == 8 || v == 16 || v == 32 ? v : kPauliTermsPerSweep;
-    }();
-    return k;
-}
-extern "C" int qsim_pauli_terms_per_sweep(void) { return pauli_terms_per_sweep(); }
-
-// The sweeps of a term list: terms in order of x (equal x: caller's order), every run of equal x cut into pieces of K.
-struct PauliSweeps {
-    std::vector<long> order;                     // term indices, grouped
-    std::vector<std::pair<long, int>> sweeps;    // (first position in `order`, terms)
-};
-static PauliSweeps pauli_sweeps(const uint64_t *x, uint64_t x_keep, long num) {
-    PauliSweeps p;
-    p.order.resize((size_t)num);
-    for (long t = 0; t < num; t++) p.order[(size_t)t] = t;
-    std::stable_sort(p.order.begin(), p.order.end(), [&](long a, long b) { return (x[a] & x_keep) < (x[b] & x_keep); });
-    const int K = pauli_terms_per_sweep();
-    for (long i = 0; i < num;) {
-        long e = i + 1;
-        while (e < num && (x[p.order[(size_t)e]] & x_keep) == (x[p.order[(size_t)i]] & x_keep)) e++;
-        for (; i < e; i += K) p.sweeps.emplace_back(i, (int)std::min<long>(K, e - i));
-        i = e;
-    }
-    return p;
-}
-
-extern "C" int qsim_pauli_sweeps(const uint64_t *x_masks, long num_terms, long *sweeps) {
-    if (!sweeps || num_terms < 0 || (num_terms > 0 && !x_masks)) return fail(QSIM_ERR_ARG, "qsim_pauli_sweeps: bad argument");
-    *sweeps = (long)pauli_sweeps(x_masks, ~0ULL, num_terms).sweeps.size();
-    return QSIM_OK;
-}
-
-int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *X, const uint64_t *Z, long num, double *out) {
-    if (!s || num < 0 || (num > 0 && (!X || !Z || !out))) return fail(QSIM_ERR_ARG, "expectation: NULL argument or negative term count");
-    if (num == 0) return QSIM_OK;
-    const int m = s->n;
-    const uint64_t mmask = index_mask(m), x_rank = X[0] >> m;
-    for (long t = 0; t < num; t++)
-        if ((X[t] >> m) != x_rank) return fail(QSIM_ERR_ARG, "expectation: terms of one shard call must pair the same shards");
-    if ((x_rank != 0) != (partner != nullptr)) return fail(QSIM_ERR_ARG, "expectation: a partner buffer goes with x on rank qubits, and only with it");
-    QSIM_TRY(settle(s));
-    constexpr int kBatch = 128; // sweeps whose results travel in one copy
-    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kBatch * kMaxTermsPerSweep) * sizeof(double)));
-    double *d_results = s->d_expect + kExpectPartialDoubles;
-    const PauliSweeps plan = pauli_sweeps(X, mmask, num);
-    std::vector<double> host((size_t)kBatch * kMaxTermsPerSweep);
-    LaunchCfg cfg{s->stream, s->grid_cap};
-    for (size_t first = 0; first < plan.sweeps.size(); first += kBatch) {
-        const size_t last = std::min(plan.sweeps.size(), first + (size_t)kBatch);
-        for (size_t w = first; w < last; w++) {
-            ExpectSweep sw{};
-            sw.x = X[plan.order[(size_t)plan.sweeps[w].first]] & mmask;
-            sw.full = x_rank != 0;
-            sw.count = plan.sweeps[w].second;
-            for (int k = 0; k < sw.count; k++) {
-                const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
-                sw.z[k] = Z[t] & mmask;
-                if (__builtin_popcountll(X[t] & Z[t]) & 1) sw.im_mask |= 1u << k;
-            }
-            HIP_TRY(launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, s->d_expect, d_results + (w - first) * kMaxTermsPerSweep));
-        }
-        HIP_TRY(hipMemcpyAsync(host.data(), d_results, (last - first) * kMaxTermsPerSweep * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t w = first; w < last; w++)
-            for (int k = 0; k < plan.sweeps[w].second; k++) {
-                const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
-                const int ny = __builtin_popcountll(X[t] & Z[t]);
-                // i^ny (c + (-1)^ny conj c): 2 Re c, -2 Im c, -2 Re c, 2 Im c for ny = 0, 1, 2, 3 mod 4; x == 0: the plain signed norm
-                double f = X[t] == 0 ? 1.0 : ((ny & 3) == 0 || (ny & 3) == 3 ? 2.0 : -2.0);
-                if (__builtin_popcountll(rank & (Z[t] >> m)) & 1) f = -f; // Z on rank qubits: a sign per shard
-                out[t] = f * host[(w - first) * kMaxTermsPerSweep + (size_t)k];
-            }
-    }
-    return QSIM_OK;
-}
-
-extern "C" int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out) {
-    if (!s) return fail(QSIM_ERR_ARG, "NULL state");
-    if (num_terms < 0) return fail(QSIM_ERR_ARG, "qsim_expect_paulis: negative term count");
-    if (num_terms > 0 && (!x_masks || !z_masks || !out)) return fail(QSIM_ERR_ARG, "qsim_expect_paulis: NULL argument");
-    const uint64_t nmask = index_mask(s->n);
-    for (long t = 0; t < num_terms; t++)
-        if ((x_masks[t] | z_masks[t]) & ~nmask)
-            return fail(QSIM_ERR_ARG, "qsim_expect_paulis: term %ld names a qubit outside the %d-qubit register", t, s->n);
-    return expect_paulis_shard(s, nullptr, 0, x_masks, z_masks, num_terms, out);
 }
 
 // ---- measurement post-path ----------------------------------------------------------------------------------

@@ -150,30 +150,31 @@ class Circuit:
 
 
 
+def _mask_arrays(masks):
+    """[(x, z)] as two uint64 arrays and their pointers: xs, zs, xp, zp."""
+    from ctypes import c_uint64
+    xs = np.array([m[0] for m in masks], dtype=np.uint64)
+    zs = np.array([m[1] for m in masks], dtype=np.uint64)
+    up = ctypes.POINTER(c_uint64)
+    return xs, zs, xs.ctypes.data_as(up), zs.ctypes.data_as(up)
+
+
 def _pauli_term_masks(paulis, num_q: int):
     """Distinct strings of `paulis` as mask arrays, and for every entry the position of its string among them."""
-    from ctypes import c_uint64
     from .pauli import pauli_masks
     index, where = {}, []
     for text in paulis:
         where.append(index.setdefault(pauli_masks(text, num_q), len(index)))
-    xs = np.array([m[0] for m in index], dtype=np.uint64)
-    zs = np.array([m[1] for m in index], dtype=np.uint64)
-    up = ctypes.POINTER(c_uint64)
-    return xs, zs, xs.ctypes.data_as(up), zs.ctypes.data_as(up), np.array(where, dtype=np.intp)
+    return _mask_arrays(index) + (np.array(where, dtype=np.intp),)
 
 
 def _rotation_arrays(rotations, num_q: int):
     """(theta, string) pairs as the arrays qsim_apply_pauli_rotations takes, in order: xs, zs, thetas and their pointers."""
-    from ctypes import c_uint64
     from .pauli import pauli_masks
     rotations = list(rotations)
-    masks = [pauli_masks(text, num_q) for _, text in rotations]
-    xs = np.array([m[0] for m in masks], dtype=np.uint64)
-    zs = np.array([m[1] for m in masks], dtype=np.uint64)
+    xs, zs, xp, zp = _mask_arrays([pauli_masks(text, num_q) for _, text in rotations])
     thetas = np.array([float(theta) for theta, _ in rotations], dtype=np.float64)
-    up = ctypes.POINTER(c_uint64)
-    return xs, zs, thetas, xs.ctypes.data_as(up), zs.ctypes.data_as(up), _dp(thetas)
+    return xs, zs, thetas, xp, zp, _dp(thetas)
 
 
 def _weighted_sum(terms, evaluate):
@@ -186,8 +187,46 @@ def _weighted_sum(terms, evaluate):
     return complex(np.dot(np.asarray(coeffs, dtype=np.complex128), values))
 
 
-class Simulator:
+class _PauliStrings:
+    """Pauli strings on a state: what Simulator and Cluster share.  A class names its two C functions (_expect_fn, _rotate_fn) and
+    has _check(rc); the strings of a Cluster name LOGICAL qubits."""
+
+    def expectation_terms(self, paulis) -> np.ndarray:
+        """<psi|P|psi> for every Pauli string of `paulis` ("X0 Z3 Y17", see pauli_masks), computed on the device
+        (qsim_expect_paulis, qsim_cluster_expect_paulis): one float64 per string, in the caller's order.  Equal strings are
+        evaluated once.  On a Cluster the strings name LOGICAL qubits."""
+        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
+        out = np.empty(xs.size, dtype=np.float64)
+        self._check(getattr(_lib.load(), self._expect_fn)(self._h, xp, zp, xs.size, _dp(out)))
+        return out[where]
+
+    def expectation(self, terms):
+        """sum_t c_t <P_t> for an iterable of (coefficient, Pauli string): <psi|H|psi> of H = sum_t c_t P_t.  A float when
+        every coefficient is real, else a complex."""
+        return _weighted_sum(terms, self.expectation_terms)
+
+    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
+        """state <- exp(-i theta/2 P) state for the Pauli string P ("X0 Y3 Z17", see pauli_masks); on a Cluster the string
+        names LOGICAL qubits."""
+        self.apply_pauli_rotations([(theta, pauli)])
+
+    def apply_pauli_rotations(self, rotations) -> None:
+        """exp(-i theta/2 P) for every (theta, string) of `rotations`, the first one first, as ONE call of
+        qsim_apply_pauli_rotations (qsim_cluster_apply_pauli_rotations): consecutive strings with X/Y on the same qubits share
+        a sweep of the state.  Returns without waiting."""
+        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
+        self._check(getattr(_lib.load(), self._rotate_fn)(self._h, xp, zp, tp, xs.size))
+
+    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
+        """A product formula for exp(-i H time) with H = sum_k c_k P_k given as (c_k, string) pairs, real c_k
+        (pauli.trotter_rotations builds the list: order 1 or 2, `steps` steps), applied as one call."""
+        from .pauli import trotter_rotations
+        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
+
+
+class Simulator(_PauliStrings):
     """One state vector resident on one GPU."""
+    _expect_fn, _rotate_fn, _check = "qsim_expect_paulis", "qsim_apply_pauli_rotations", staticmethod(check)
 
     def __init__(self, num_q: int, device: int = 0, *, fuse: Optional[int] = None, profile: bool = False,
                  external_ptr: Optional[int] = None, precision: int = 64, **options):
@@ -369,36 +408,6 @@ class Simulator:
         check(_lib.load().qsim_norm2(self._h, byref(v)))
         return v.value
 
-    def expectation_terms(self, paulis) -> np.ndarray:
-        """<psi|P|psi> for every Pauli string of `paulis` ("X0 Z3 Y17", see pauli_masks), computed on the device
-        (qsim_expect_paulis): one float64 per string, in the caller's order.  Equal strings are evaluated once."""
-        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
-        out = np.empty(xs.size, dtype=np.float64)
-        check(_lib.load().qsim_expect_paulis(self._h, xp, zp, xs.size, _dp(out)))
-        return out[where]
-
-    def expectation(self, terms):
-        """sum_t c_t <P_t> for an iterable of (coefficient, Pauli string): <psi|H|psi> of H = sum_t c_t P_t.  A float when
-        every coefficient is real, else a complex."""
-        return _weighted_sum(terms, self.expectation_terms)
-
-    # -- Pauli rotations
-    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
-        """state <- exp(-i theta/2 P) state for the Pauli string P ("X0 Y3 Z17", see pauli_masks)."""
-        self.apply_pauli_rotations([(theta, pauli)])
-
-    def apply_pauli_rotations(self, rotations) -> None:
-        """exp(-i theta/2 P) for every (theta, string) of `rotations`, the first one first, as ONE qsim_apply_pauli_rotations call:
-        consecutive strings with X/Y on the same qubits share a sweep of the state.  Returns without waiting."""
-        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
-        check(_lib.load().qsim_apply_pauli_rotations(self._h, xp, zp, tp, xs.size))
-
-    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
-        """A product formula for exp(-i H time) with H = sum_k c_k P_k given as (c_k, string) pairs, real c_k
-        (pauli.trotter_rotations builds the list: order 1 or 2, `steps` steps), applied as one call."""
-        from .pauli import trotter_rotations
-        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
-
     @property
     def device_ptr(self) -> int:
         return int(_lib.load().qsim_device_ptr(self._h) or 0)
@@ -453,8 +462,9 @@ class Simulator:
         check(_lib.load().qsim_reset_stats(self._h))
 
 
-class Cluster:
+class Cluster(_PauliStrings):
     """qsim_cluster: P shards driven by this one process (the C host's multi-GPU path; repeat a device for virtual shards)."""
+    _expect_fn, _rotate_fn = "qsim_cluster_expect_paulis", "qsim_cluster_apply_pauli_rotations"
 
     def __init__(self, num_q: int, num_shards: int, devices: Optional[Sequence[int]] = None, **options):
         self._h = c_void_p()
@@ -494,31 +504,6 @@ class Cluster:
         v = c_double()
         self._check(_lib.load().qsim_cluster_norm2(self._h, byref(v)))
         return v.value
-
-    def expectation_terms(self, paulis) -> np.ndarray:
-        """Simulator.expectation_terms on the sharded state (qsim_cluster_expect_paulis); strings name LOGICAL qubits."""
-        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
-        out = np.empty(xs.size, dtype=np.float64)
-        self._check(_lib.load().qsim_cluster_expect_paulis(self._h, xp, zp, xs.size, _dp(out)))
-        return out[where]
-
-    def expectation(self, terms):
-        """Simulator.expectation on the sharded state."""
-        return _weighted_sum(terms, self.expectation_terms)
-
-    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
-        """Simulator.apply_pauli_rotation on the sharded state; the string names LOGICAL qubits."""
-        self.apply_pauli_rotations([(theta, pauli)])
-
-    def apply_pauli_rotations(self, rotations) -> None:
-        """Simulator.apply_pauli_rotations on the sharded state (qsim_cluster_apply_pauli_rotations)."""
-        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
-        self._check(_lib.load().qsim_cluster_apply_pauli_rotations(self._h, xp, zp, tp, xs.size))
-
-    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
-        """Simulator.evolve on the sharded state."""
-        from .pauli import trotter_rotations
-        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
 
     def sample(self, randoms) -> np.ndarray:
         """measurement() (quantum_simulator.c:270-283) on the sharded state, indices in logical order."""

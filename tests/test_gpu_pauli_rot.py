@@ -28,6 +28,7 @@ from gpu_quantum_simulator_amd import Circuit, Cluster, ShardPlanHandle, Simulat
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
+TOL32 = 2e-5  # tests/test_gpu_fp32.py derives it for a few hundred fp32 roundings per amplitude
 PRECISIONS = [64, 32]
 UP = ctypes.POINTER(ctypes.c_uint64)
 DP = ctypes.POINTER(ctypes.c_double)
@@ -468,3 +469,38 @@ def test_errors(precision):
             cl._check(lib.qsim_cluster_apply_pauli_rotations(cl._h, None, None, None, 0))
             cl.apply_pauli_rotations([])
             assert np.array_equal(_bits(cl), before)
+
+
+GEOMETRY_THETA = 0.7
+
+
+def _geometry_strings(n):
+    """(x, z) with the highest x bit at 0, at 1, on either side of the unit / thread boundary of the sweeps (7 and 8) and at n - 1,
+    as far as the register has these bits, and one diagonal string."""
+    out = []
+    for h in sorted({0, 1, 7, 8, n - 1} & set(range(n))):
+        x = 1 << h | (1 << (h - 2) if h >= 2 else 0)        # a second X two bits below, where there is room
+        z = (1 << h if h % 2 else 0) | 1 << (h + 1) % n     # Y at an odd h, and a Z next to it (n = 1: Y0)
+        out.append((x, z))
+    return out + [(0, 0b101101101 & ((1 << n) - 1))]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("n", [1, 2, 9])
+def test_expectation_of_p_survives_its_own_rotation(n, precision):
+    """exp(-i theta/2 P) commutes with P, so <P> read by k_expect before and after k_pauli_rot applied the rotation is one number:
+    the two kernels walk the state by one geometry (csrc/pauli_sweep.h), and a string that one of them paired or signed differently
+    from the other would move it.  fp64: TOL.  fp32: the rotation rounds every amplitude a few times, once per fused multiply-add;
+    TOL32 is the bound for a few hundred such roundings."""
+    largest = 0.0
+    with Simulator(n, precision=precision) as sim:
+        for x, z in _geometry_strings(n):
+            text = pauli_ref.masks_to_text(x, z, n)
+            sim.write(ref.rand_state(n, 70 + n))
+            before = float(sim.expectation_terms([text])[0])
+            sim.apply_pauli_rotation(GEOMETRY_THETA, text)
+            after = float(sim.expectation_terms([text])[0])
+            print(f"n={n} p{precision} {text}: <P> {before:+.6e} -> {after:+.6e}, moved by {abs(after - before):.3e}")
+            assert abs(after - before) < (TOL if precision == 64 else TOL32)
+            largest = max(largest, abs(before))
+    assert largest > 1e-3  # not a comparison of zeros
