@@ -94,6 +94,10 @@ SIGNATURES = {
     "qsim_pauli_rotations_per_sweep": (c_int, []),
     "qsim_pauli_rotation_sweeps_launched": (c_uint64, []),
     "qsim_cluster_apply_pauli_rotations": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long]),
+    "qsim_pauli_gradient": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, _DP, _DP]),
+    "qsim_pauli_sum_into": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, c_void_p]),
+    "qsim_pauli_gradient_plan": (c_int, [POINTER(c_uint64), c_long, POINTER(c_uint64), c_long, POINTER(c_long), POINTER(c_long)]),
+    "qsim_pauli_adjoint_sweeps_launched": (c_uint64, []),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

@@ -143,6 +143,7 @@ extern "C" void qsim_destroy(qsim_state *s) {
     if (s->h_ops) (void)hipHostFree(s->h_ops);
     if (s->d_scalar) (void)hipFree(s->d_scalar);
     if (s->d_expect) (void)hipFree(s->d_expect);
+    if (s->d_adjoint) (void)hipFree(s->d_adjoint);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }

@@ -4,8 +4,9 @@
 //   engine.cpp    errors, create / destroy, options, reset / support, the gate queue, launch_pass, the plan cache, the flush
 //   planning.cpp  the measured tile-bit orders and schedule choices (process-wide tables, private to it) and the planning API
 //   readout.cpp   reads, writes, norms, sampling                             pack.cpp  re-layouts and buffer hand-overs
-//   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values and rotations
-//                                                                           (the host side of expect.hip and evolve.hip; pauli_sweep.h)
+//   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values, rotations
+//                                                                           and adjoint gradients (the host side of expect.hip,
+//                                                                           evolve.hip and adjoint.hip; pauli_sweep.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 
@@ -101,6 +102,7 @@ struct qsim_state {
     size_t ops_cap = 0, ops_used = 0;
     double *d_scalar = nullptr;
     double *d_expect = nullptr; // qsim_expect_paulis: partial sums of a sweep, then the results of a batch of sweeps; allocated on first use
+    void *d_adjoint = nullptr;  // qsim_pauli_gradient: lambda's 2^n amplitudes for a state without a spare buffer; allocated on first use, the state's own
     // stats
     qsim_stats stats{};
     std::vector<ProfEvent> events;      // recorded, not yet resolved

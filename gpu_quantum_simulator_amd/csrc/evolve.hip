@@ -1,6 +1,7 @@
 // evolve.hip — Pauli-string rotations exp(-i theta/2 P) as in-place sweeps (gfx950).  Its own object, like expect.hip: nothing
 // here is compiled into kernels.hip, whose code layout is part of the measured product.  pauli_sweep.h says how a
-// sweep walks a state (units, bit insertion, parity split, fp32 corners, grids); this file has the 2x2 and the stores.
+// sweep walks a state (units, bit insertion, parity split, fp32 corners, grids) and has the 2x2 itself (rotate_pair, rotate_diag:
+// the adjoint sweep applies it too); this file has the rule and the stores.
 //
 // P maps every index pair {j, j ^ x} to itself, so the rotation is a 2x2 on each pair whatever the string's weight.  With
 // s(j) = (-1)^popcount(j & z), ny = popcount(x & z), c = cos(theta/2) and w = -i sin(theta/2) i^ny:
@@ -29,22 +30,6 @@ struct RotTerms {       // by value: scalar loads
     int32_t count;
 };
 static_assert(sizeof(RotTerms<double>) <= 1024, "term records stay well inside the 4 KiB of kernel arguments");
-
-// one pair, sv = s(j) v
-template <typename R>
-__device__ __forceinline__ void rotate_pair(R &ar, R &ai, R &br, R &bi, R c, R sv, bool odd) {
-    const R pr = odd ? br : bi, pi = odd ? bi : br;   // w b = sv (br, bi) or sv (-bi, br); a's sign: -1 for odd ny
-    const R qr = odd ? ar : ai, qi = odd ? ai : ar;   // w a likewise
-    const R nar = fma(-sv, pr, c * ar), nai = fma(odd ? -sv : sv, pi, c * ai);
-    const R nbr = fma(odd ? sv : -sv, qr, c * br), nbi = fma(sv, qi, c * bi);
-    ar = nar, ai = nai, br = nbr, bi = nbi;
-}
-// x == 0: a' = (c + i sv) a
-template <typename R>
-__device__ __forceinline__ void rotate_diag(R &ar, R &ai, R c, R sv) {
-    const R nr = fma(-sv, ai, c * ar), ni = fma(sv, ar, c * ai);
-    ar = nr, ai = ni;
-}
 
 template <typename R, bool PAIRED>
 __global__ __launch_bounds__(kTPB) void k_pauli_rot(R *a, R *b, SweepGeom g, RotTerms<R> terms) { // a and b may be one buffer

@@ -11,7 +11,8 @@
 // thread's finished sums.
 //
 // Reduction, no atomics: fp64 sums per thread -> xor butterfly in the wave -> waves added in order through LDS -> one row of
-// partial sums per workgroup -> k_expect_final adds the rows in a fixed order.  Same bits from call to call.
+// partial sums per workgroup -> k_expect_final adds the rows in a fixed order (launch_expect_final: the adjoint sweep ends the same
+// way).  Same bits from call to call.
 #include "pauli_sweep.h"
 
 namespace qsim {
@@ -120,15 +121,6 @@ __global__ __launch_bounds__(kTPB) void k_expect(const R *__restrict__ a, const 
     }
 }
 
-// out[k] = sum over the rows of `partial` in a fixed order: lane l adds rows l, l + 64, ... in order, then the butterfly.
-__global__ __launch_bounds__(64) void k_expect_final(const double *__restrict__ partial, int rows, int kt, double *__restrict__ out) {
-    const int k = blockIdx.x;
-    double s = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 64) s += partial[(size_t)r * kt + k];
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    if (threadIdx.x == 0) out[k] = s;
-}
-
 template <typename R, bool PAIRED, int KT>
 hipError_t launch_kt(hipStream_t stream, const void *a, const void *b, const SweepGeom &g, const ExpectSweep &sw, double *d_partial,
                      double *d_out) {
@@ -145,8 +137,7 @@ hipError_t launch_kt(hipStream_t stream, const void *a, const void *b, const Swe
     hipLaunchKernelGGL((k_expect<R, PAIRED, KT>), dim3((unsigned)grid), dim3(kTPB), 0, stream, (const R *)a, (const R *)b, g, rec, d_partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_expect_final, dim3(KT), dim3(64), 0, stream, (const double *)d_partial, (int)grid, KT, d_out);
-    return hipGetLastError();
+    return launch_expect_final(stream, d_partial, (int)grid, KT, d_out);
 }
 
 template <typename R, bool PAIRED>
@@ -161,6 +152,20 @@ hipError_t launch_prec(hipStream_t stream, const void *a, const void *b, const S
 }
 
 } // namespace
+
+// out[k] = sum over the rows of `partial` in a fixed order: lane l adds rows l, l + 64, ... in order, then the butterfly.
+static __global__ __launch_bounds__(64) void k_expect_final(const double *__restrict__ partial, int rows, int kt, double *__restrict__ out) {
+    const int k = blockIdx.x;
+    double s = 0.0;
+    for (int r = threadIdx.x; r < rows; r += 64) s += partial[(size_t)r * kt + k];
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (threadIdx.x == 0) out[k] = s;
+}
+
+hipError_t launch_expect_final(hipStream_t stream, const double *d_partial, int rows, int kt, double *d_out) {
+    hipLaunchKernelGGL(k_expect_final, dim3(kt), dim3(64), 0, stream, d_partial, rows, kt, d_out);
+    return hipGetLastError();
+}
 
 int expect_slots(int count) { return count <= 1 ? 1 : count <= 8 ? 8 : count <= 16 ? 16 : count <= kMaxPauliTermsPerSweep ? 32 : 0; }
 

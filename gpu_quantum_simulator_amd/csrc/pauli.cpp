@@ -1,7 +1,9 @@
-// pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values") and
-// rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations").  pauli_sweep.h has what the
-// two kinds of sweep share.  Every entry point opens with settle() and then only touches qsim_state's buffer, stream and
-// d_expect; expectation values read the buffer, rotations write it.
+// pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values"),
+// rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations") and adjoint-mode gradients of
+// <H> with respect to the angles (adjoint.hip; DESIGN "Adjoint gradients").  pauli_sweep.h has what the sweeps share.  Every
+// entry point opens with settle() and then only touches qsim_state's buffer, stream and d_expect; expectation values read the
+// buffer, rotations write it, a gradient call writes it and a second buffer of the same size (the spare one, or d_adjoint) and
+// leaves the state as it found it.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -24,16 +26,16 @@ static double rotation_v(int ny, double sn) { return pauli_phase(ny + 3) * sn; }
 static double rank_sign(uint64_t rank, uint64_t z, int m) { return (__builtin_popcountll(rank & (z >> m)) & 1) ? -1.0 : 1.0; }
 
 // The argument checks of the two single-state entry points; `third` is the array that goes with the masks (results or angles),
-// `thetas` the angles where there are any.
+// `thetas` the numbers that must be finite where there are any: angles, or coefficients (`number` says which).
 static int check_terms(const char *who, const qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *thetas,
-                       long num_terms) {
+                       long num_terms, const char *number = "angle") {
     if (!s) return fail(QSIM_ERR_ARG, "NULL state");
     if (num_terms < 0) return fail(QSIM_ERR_ARG, "%s: negative term count", who);
     if (num_terms > 0 && (!x_masks || !z_masks || !third)) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
     const uint64_t nmask = index_mask(s->n);
     for (long t = 0; t < num_terms; t++) {
         if ((x_masks[t] | z_masks[t]) & ~nmask) return fail(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, s->n);
-        if (thetas && !std::isfinite(thetas[t])) return fail(QSIM_ERR_ARG, "%s: term %ld has a non-finite angle", who, t);
+        if (thetas && !std::isfinite(thetas[t])) return fail(QSIM_ERR_ARG, "%s: term %ld has a non-finite %s", who, t, number);
     }
     return QSIM_OK;
 }
@@ -213,6 +215,141 @@ extern "C" int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks
             QSIM_TRY(qsim_apply_1q(s, U, __builtin_ctzll(x_masks[r.first])));
         } else {
             QSIM_TRY(pauli_rot_run(s, nullptr, 0, x_masks[r.first], z_masks + r.first, thetas + r.first, r.count));
+        }
+    }
+    return QSIM_OK;
+}
+
+// ---- adjoint gradients ------------------------------------------------------------------------------------------------------------
+// E = <psi_K|H|psi_K> and dE/dtheta_k = Im <lambda_k|P_k|psi_k> (adjoint.hip has the pair formula): forward pass, lambda = H psi,
+// energy, then the backward sweeps over psi and lambda, which also take the state back to where the call found it.
+static std::atomic<uint64_t> g_adjoint_sweeps{0};
+extern "C" uint64_t qsim_pauli_adjoint_sweeps_launched(void) { return g_adjoint_sweeps.load(); }
+
+// The backward sweeps in FORWARD order: maximal runs of consecutive equal x, cut into pieces of K.  Every term, single X and Y too.
+static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *X, long num) {
+    std::vector<std::pair<long, int>> out;
+    for (long t = 0; t < num;) {
+        long e = t + 1;
+        while (e < num && X[e] == X[t]) e++;
+        for (; t < e; t += kPauliRotationsPerSweep) out.emplace_back(t, (int)std::min<long>(kPauliRotationsPerSweep, e - t));
+        t = e;
+    }
+    return out;
+}
+
+extern "C" int qsim_pauli_gradient_plan(const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, long *adjoint_sweeps, long *sum_sweeps) {
+    if (num_rot < 0 || num_ham < 0) return fail(QSIM_ERR_ARG, "qsim_pauli_gradient_plan: negative term count");
+    if (!adjoint_sweeps || !sum_sweeps || (num_rot > 0 && !rot_x) || (num_ham > 0 && !ham_x)) return fail(QSIM_ERR_ARG, "qsim_pauli_gradient_plan: NULL argument");
+    *adjoint_sweeps = (long)adjoint_pieces(rot_x, num_rot).size();
+    *sum_sweeps = (long)pauli_sweeps(ham_x, ~0ULL, num_ham).sweeps.size();
+    return QSIM_OK;
+}
+
+// dst = sum_t C[t] Q_t |state> for a settled state and checked arguments: one sweep per piece of an x group, the first stores.
+static int pauli_sum_sweeps(qsim_state *s, const uint64_t *X, const uint64_t *Z, const double *C, long num, void *dst) {
+    if (num == 0) { // the empty sum
+        HIP_TRY(hipMemsetAsync(dst, 0, s->amp_bytes() << s->n, s->stream));
+        return QSIM_OK;
+    }
+    const PauliSweeps plan = pauli_sweeps(X, ~0ULL, num);
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    for (size_t w = 0; w < plan.sweeps.size(); w++) {
+        SumSweep sw{};
+        sw.x = X[plan.order[(size_t)plan.sweeps[w].first]];
+        sw.count = plan.sweeps[w].second;
+        sw.accumulate = w > 0;
+        for (int k = 0; k < sw.count; k++) {
+            const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
+            const int ny = __builtin_popcountll(X[t] & Z[t]);
+            sw.z[k] = Z[t];
+            sw.c[k] = C[t] * pauli_phase(ny) * ((ny & 1) ? -1.0 : 1.0); // (Q psi)_i = i^ny s(i ^ x) psi_(i^x), and s(i ^ x) = (-1)^ny s(i)
+            if (ny & 1) sw.odd_mask |= 1u << k;
+        }
+        const hipError_t e = launch_pauli_sum(cfg, s->amps, dst, s->f32, s->n, sw);
+        if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "Pauli sum sweep launch failed: %s", hipGetErrorString(e));
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_pauli_sum_into(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *coeffs, long num_terms, void *dst_device) {
+    QSIM_TRY(check_terms("qsim_pauli_sum_into", s, x_masks, z_masks, coeffs, coeffs, num_terms, "coefficient"));
+    QSIM_TRY(await_buffer(s));
+    if (!dst_device || dst_device == s->amps || dst_device == s->spare)
+        return fail(QSIM_ERR_ARG, "qsim_pauli_sum_into: the destination is NULL or one of the state's own buffers");
+    QSIM_TRY(settle(s));
+    return pauli_sum_sweeps(s, x_masks, z_masks, coeffs, num_terms, dst_device);
+}
+
+extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot,
+                                   const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad) {
+    QSIM_TRY(check_terms("qsim_pauli_gradient", s, rot_x, rot_z, thetas, thetas, num_rot));
+    QSIM_TRY(check_terms("qsim_pauli_gradient", s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
+    if (energy) *energy = 0.0;
+    if (grad) std::fill(grad, grad + num_rot, 0.0);
+    if (qsim_holds_nothing(s)) return QSIM_OK; // the zero vector: energy 0, gradient 0, no sweep
+    QSIM_TRY(await_buffer(s));
+    HIP_TRY(hipSetDevice(s->device));
+    // everything that can fail for want of memory comes before the state is touched
+    constexpr int kBatch = 128; // sweeps whose results travel in one copy (d_expect as expect_paulis_shard lays it out)
+    constexpr int kSlots = kMaxPauliTermsPerSweep;
+    void *lam = s->spare && s->spare != s->amps ? s->spare : s->d_adjoint; // the spare buffer is idle outside a flush
+    if (!lam) {
+        HIP_TRY(hipMalloc(&lam, s->amp_bytes() << s->n));
+        s->d_adjoint = lam;
+    }
+    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kBatch * kSlots) * sizeof(double)));
+    double *d_results = s->d_expect + kExpectPartialDoubles;
+
+    QSIM_TRY(qsim_apply_pauli_rotations(s, rot_x, rot_z, thetas, num_rot));
+    QSIM_TRY(settle(s));
+    QSIM_TRY(pauli_sum_sweeps(s, ham_x, ham_z, coeffs, num_ham, lam));
+
+    // row 0: the energy, Re <lambda|psi>, as one paired expectation sweep over the two buffers; then the pieces, last first
+    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(rot_x, num_rot);
+    const size_t rows = 1 + pieces.size();
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    std::vector<double> host((size_t)kBatch * kSlots);
+    for (size_t first = 0; first < rows; first += kBatch) {
+        const size_t last = std::min(rows, first + (size_t)kBatch);
+        for (size_t r = first; r < last; r++) {
+            double *d_out = d_results + (r - first) * kSlots;
+            if (r == 0) {
+                ExpectSweep sw{};
+                sw.full = true; // x == 0 over two buffers: every index, its partner the same index of lambda
+                sw.count = 1;
+                HIP_TRY(launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_out));
+                continue;
+            }
+            const std::pair<long, int> &piece = pieces[pieces.size() - r];
+            RotSweep sw{};
+            sw.x = rot_x[piece.first];
+            sw.count = piece.second;
+            for (int k = 0; k < sw.count; k++) {
+                const uint64_t z = rot_z[piece.first + k];
+                const double half = -0.5 * thetas[piece.first + k]; // U^+
+                const int ny = __builtin_popcountll(sw.x & z);
+                sw.z[k] = z;
+                sw.c[k] = std::cos(half);
+                sw.v[k] = rotation_v(ny, std::sin(half));
+                if (ny & 1) sw.odd_mask |= 1u << k;
+            }
+            const hipError_t e = launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_out);
+            if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "adjoint sweep launch failed: %s", hipGetErrorString(e));
+            g_adjoint_sweeps++;
+        }
+        HIP_TRY(hipMemcpyAsync(host.data(), d_results, (last - first) * kSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (size_t r = first; r < last; r++) {
+            const double *row = host.data() + (r - first) * kSlots;
+            if (r == 0) {
+                if (energy) *energy = row[0];
+                continue;
+            }
+            const std::pair<long, int> &piece = pieces[pieces.size() - r];
+            // Im (i^ny B): the kernel summed Im B (even ny) or Re B (odd); both members of a pair are in B, so the factor is 1, not 2
+            for (int k = 0; grad && k < piece.second; k++)
+                grad[piece.first + k] = pauli_phase(__builtin_popcountll(rot_x[piece.first] & rot_z[piece.first + k])) * row[k];
         }
     }
     return QSIM_OK;

@@ -1,5 +1,6 @@
 // pauli_sweep.h — how a Pauli sweep walks a state: what expect.hip (<psi|P|psi>, read-only), evolve.hip (exp(-i theta/2 P), in
-// place) and their host side pauli.cpp share.  DESIGN §7b opens with the same account.
+// place), adjoint.hip (dE/dtheta: the backward sweep over psi and lambda, and lambda = H psi) and their host side pauli.cpp share.
+// DESIGN §7b opens with the same account.
 //
 // A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
 // pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets
@@ -17,10 +18,13 @@
 // bytes long, no unit (k_expect guards its loads, k_pauli_rot takes a single-thread path of its own).
 //
 // Grids.  Every workgroup of a sweep walks the same number of trips, so a second, partly filled round of workgroups would cost a
-// whole round: the default grid is what is resident at once (resident_grid).  The two kernels cap it differently, on purpose:
+// whole round: the default grid is what is resident at once (resident_grid).  The kernels cap it differently, on purpose:
 // an expectation sweep at kExpectGrid rows whatever LaunchCfg::grid_cap says, because its partial-sum buffer is sized by that; a
 // rotation sweep at grid_cap when one is set (QSIM_OPT_GRID_CAP, as for every other kernel), and at 1024 when the occupancy
-// query fails.
+// query fails.  The adjoint sweep (k_pauli_adjoint) writes amplitudes AND reduces: it follows the expectation sweep's rule — the
+// resident grid, at most kExpectGrid rows, grid_cap NOT applied — because its sums are added row by row, so their bits depend on
+// the grid, and equal calls must return equal bits whatever the option says; its amplitudes are each written by one thread and
+// would not care.  k_pauli_sum (lambda = H psi) only writes, each output by one thread: the rotation sweep's rule.
 #ifndef QSIM_PAULI_SWEEP_H
 #define QSIM_PAULI_SWEEP_H
 
@@ -54,8 +58,24 @@ int expect_slots(int count); // term slots of the instantiation a sweep of `coun
 // d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.
 hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, bool f32, int n, const ExpectSweep &sw, double *d_partial,
                          double *d_out);
+// out[k] = the sum of column k over `rows` rows of `kt` partial sums, added in a fixed order (the last step of every reducing sweep)
+hipError_t launch_expect_final(hipStream_t stream, const double *d_partial, int rows, int kt, double *d_out);
 // a_j' = c a_j + w (-1)^ny s(j) b_(j^x),  b_(j^x)' = c b_(j^x) + w s(j) a_j, term after term.
 hipError_t launch_pauli_rot(const LaunchCfg &cfg, void *a, void *b, bool f32, int n, const RotSweep &sw);
+// The backward sweep of an adjoint gradient over psi and lambda (two buffers, one state each: sw.full is refused).  From the LAST
+// term of sw to the first: d_out[k] = sum over the pairs of s_k(j) Re (odd ny) or Im (even ny) of [conj(lambda_(j^x)) psi_j +
+// (-1)^ny conj(lambda_j) psi_(j^x)]  (x == 0: sum_j s_k(j) Im conj(lambda_j) psi_j), then term k's 2x2 — c and v as for
+// launch_pauli_rot, of MINUS theta_k — on psi and on lambda.  k < expect_slots(count); d_partial as for launch_expect.
+hipError_t launch_pauli_adjoint(const LaunchCfg &cfg, void *psi, void *lam, bool f32, int n, const RotSweep &sw, double *d_partial, double *d_out);
+// Term k of a sum of strings with one x: c = coefficient times the non-zero component of i^ny times (-1)^ny; bit k of odd_mask: ny
+// is odd, the term belongs to the imaginary part of the weight.
+struct SumSweep : PauliSweep {
+    double c[kMaxPauliTermsPerSweep];
+    uint32_t odd_mask;
+    bool accumulate; // dst += instead of dst =
+};
+// dst_i (=|+=) src_(i^x) (sum_even c_k s_k(i) + i sum_odd c_k s_k(i)), out of place: src and dst are different buffers.
+hipError_t launch_pauli_sum(const LaunchCfg &cfg, const void *src, void *dst, bool f32, int n, const SumSweep &sw);
 
 // the partner index and every z must stay inside the buffer of 2^n amplitudes
 inline bool check_sweep(const PauliSweep &sw, int n) {
@@ -73,6 +93,9 @@ constexpr int kTidBits = 8;
 static_assert((1 << kTidBits) == kTPB, "unit index = (q << kTidBits) | tid");
 // units per thread and trip: 8 independent 16-byte loads in flight (a paired sweep loads two units per unit visited)
 constexpr int units_per_trip(bool paired) { return paired ? 4 : 8; }
+// the adjoint sweep walks two buffers: the same 8 loads in flight are half as many units (a paired sweep keeps four units live per
+// unit visited)
+constexpr int adjoint_units_per_trip(bool paired) { return units_per_trip(paired) / 2; }
 
 struct SweepGeom {      // by value: a kernel argument
     uint64_t units;     // 16-byte units to visit
@@ -136,6 +159,23 @@ __device__ __forceinline__ uint64_t expand(const SweepGeom &g, uint64_t t) {
 template <typename R>
 __device__ __forceinline__ typename Vec16<R>::type load_unit(const R *p, uint64_t amp) {
     return *reinterpret_cast<const typename Vec16<R>::type *>(p + 2 * amp);
+}
+
+
+// The 2x2 of one rotation term on one pair, sv = s(j) v (evolve.hip has the rule): shared by k_pauli_rot and k_pauli_adjoint.
+template <typename R>
+__device__ __forceinline__ void rotate_pair(R &ar, R &ai, R &br, R &bi, R c, R sv, bool odd) {
+    const R pr = odd ? br : bi, pi = odd ? bi : br;   // w b = sv (br, bi) or sv (-bi, br); a's sign: -1 for odd ny
+    const R qr = odd ? ar : ai, qi = odd ? ai : ar;   // w a likewise
+    const R nar = fma(-sv, pr, c * ar), nai = fma(odd ? -sv : sv, pi, c * ai);
+    const R nbr = fma(odd ? sv : -sv, qr, c * br), nbi = fma(sv, qi, c * bi);
+    ar = nar, ai = nai, br = nbr, bi = nbi;
+}
+// x == 0: a' = (c + i sv) a
+template <typename R>
+__device__ __forceinline__ void rotate_diag(R &ar, R &ai, R c, R sv) {
+    const R nr = fma(-sv, ai, c * ar), ni = fma(sv, ar, c * ai);
+    ar = nr, ai = ni;
 }
 
 } // namespace qsim

@@ -177,6 +177,19 @@ def _rotation_arrays(rotations, num_q: int):
     return xs, zs, thetas, xp, zp, _dp(thetas)
 
 
+def _hamiltonian_arrays(terms, num_q: int):
+    """(real coefficient, string) pairs as the arrays qsim_pauli_gradient and qsim_pauli_sum_into take: xs, zs, coeffs and their
+    pointers.  ValueError for a complex coefficient."""
+    from .pauli import pauli_masks
+    terms = list(terms)
+    for coeff, text in terms:
+        if isinstance(coeff, complex) or (hasattr(coeff, "dtype") and coeff.dtype.kind == "c"):
+            raise ValueError(f"coefficient {coeff!r} of {text!r} is complex: a Hamiltonian's coefficients are real")
+    xs, zs, xp, zp = _mask_arrays([pauli_masks(text, num_q) for _, text in terms])
+    coeffs = np.array([float(c) for c, _ in terms], dtype=np.float64)
+    return xs, zs, coeffs, xp, zp, _dp(coeffs)
+
+
 def _weighted_sum(terms, evaluate):
     """sum_t c_t <P_t> for (coefficient, string) pairs: a float when every coefficient is real, else a complex."""
     terms = list(terms)
@@ -260,6 +273,24 @@ class Simulator(_PauliStrings):
     # -- options / lifecycle
     def set_option(self, opt: int, value: int) -> None:
         check(_lib.load().qsim_set_option(self._h, opt, value))
+
+    # -- adjoint gradients (single states only: a Cluster has no counterpart)
+    def energy_and_gradient(self, rotations, terms):
+        """(E, grad): E = <psi|H|psi> after the rotations and grad[k] = dE/dtheta_k, for `rotations` as apply_pauli_rotations
+        takes them and H = `terms` as expectation takes them, real coefficients (ValueError for a complex one).  Adjoint
+        differentiation on the device (qsim_pauli_gradient): one forward pass, one application of H, one backward pass.  The
+        state is left as the call found it, to rounding."""
+        rxs, rzs, thetas, rxp, rzp, tp = _rotation_arrays(rotations, self.num_qubits)
+        hxs, hzs, coeffs, hxp, hzp, cp = _hamiltonian_arrays(terms, self.num_qubits)
+        energy, grad = c_double(0.0), np.zeros(rxs.size, dtype=np.float64)
+        check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
+        return float(energy.value), grad
+
+    def pauli_sum_into(self, terms, dst_ptr: int) -> None:
+        """dst = sum_t c_t Q_t |state> for (real coefficient, string) pairs, written to the device buffer at `dst_ptr` (2^n
+        amplitudes of this state's precision, not this state's own buffer); queued on the state's stream, not waited for."""
+        xs, zs, coeffs, xp, zp, cp = _hamiltonian_arrays(terms, self.num_qubits)
+        check(_lib.load().qsim_pauli_sum_into(self._h, xp, zp, cp, xs.size, c_void_p(dst_ptr)))
 
     def reset(self, holds_index0: bool = True) -> None:
         check(_lib.load().qsim_reset_shard(self._h, 1 if holds_index0 else 0))

@@ -186,6 +186,35 @@ int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks, const uin
 /* Host only, no device: what the call above does with these terms — sweeps launched and terms queued as 2x2 gates. */
 int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, long *sweeps, long *queued_as_gates);
 int qsim_pauli_rotations_per_sweep(void); /* K: 32, the one-bit-per-term masks' limit; an unmeasured default ("Pauli rotations") */
+/* ---- adjoint-mode gradients of <H> for circuits of Pauli rotations, on the device (new) ----
+ * E = <psi_K|H|psi_K> and grad[k] = dE/dtheta_k for psi_K = prod_k exp(-i thetas[k]/2 P_k) |state>, H = sum_t coeffs[t] Q_t (real
+ * coefficients): all num_rot derivatives from one forward pass, one application of H and one backward pass, instead of the two
+ * circuit executions per parameter of the shift rule.  With |lambda_K> = H|psi_K> and |lambda_(k-1)> = U_k^+ |lambda_k>,
+ * dE/dtheta_k = Im <lambda_k|P_k|psi_k>.
+ * Forward: qsim_apply_pauli_rotations (its routing, single X/Y through the gate queue).  Then lambda = H psi (one out-of-place sweep
+ * per piece of an x_mask group of H, qsim_pauli_terms_per_sweep() terms each), energy = Re <lambda|psi> (one paired sweep), then the
+ * backward sweeps: maximal runs of consecutive equal x_mask, cut into pieces of qsim_pauli_rotations_per_sweep(), last run first; a
+ * sweep reads and writes psi and lambda once and differentiates AND undoes its terms in registers, from the last to the first,
+ * whether or not they commute.  In the backward pass EVERY term goes through a sweep, single X/Y and the identity included (the
+ * identity's derivative is 0 up to rounding: a global phase).
+ * lambda lives in the state's spare buffer when it has one (it is idle outside a flush), otherwise in a buffer of the state's own
+ * that is allocated on first use and freed by qsim_destroy — whatever QSIM_OPT_PINGPONG says, and for external states too.
+ * QSIM_ERR_ALLOC when that fails, with the state untouched.  The sums are fp64 in both precisions and are added in a fixed order:
+ * equal calls return equal bits, and QSIM_OPT_GRID_CAP does not apply to the backward sweeps (it would change the order).  The
+ * results of up to 128 sweeps travel in one device-to-host copy; the call waits for its results.
+ * On return the state holds what it held before the call, to the rounding of 2 num_rot rotations.  energy or grad may be NULL.
+ * num_rot == 0: the energy alone.  A shard that holds nothing (qsim_holds_nothing): energy 0, grad zeros, no sweep.
+ * QSIM_ERR_ARG, with the state unchanged: a NULL state, NULL arrays with a positive count, a negative count, a mask bit at or above
+ * the register's qubit count, a non-finite theta or coefficient.
+ * Single states only, fp64 and fp32: there is NO qsim_cluster_* counterpart (a sharded lambda needs a second exchange scratch). */
+int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot,
+                        const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad);
+/* dst (device, 2^n amplitudes of the state's precision, not the state's own buffers) = sum_t coeffs[t] Q_t |state>; on qsim_stream(),
+ * not waited for.  num_terms == 0 writes zeros.  QSIM_ERR_ARG as above, and for dst_device NULL or equal to the state's buffer or
+ * its spare buffer. */
+int qsim_pauli_sum_into(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *coeffs, long num_terms, void *dst_device);
+/* Host only: sweeps the gradient call makes after its forward pass. */
+int qsim_pauli_gradient_plan(const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, long *adjoint_sweeps, long *sum_sweeps);
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
@@ -435,6 +464,7 @@ int qsim_reset_stats(qsim_state *s);
  * cluster's) launched by this process so far.  One process-wide counter for all states and shards together, which qsim_stats
  * does not have and qsim_reset_stats does not clear: take differences, and only where one thread applies rotations. */
 uint64_t qsim_pauli_rotation_sweeps_launched(void);
+uint64_t qsim_pauli_adjoint_sweeps_launched(void); /* the same for the backward sweeps of qsim_pauli_gradient */
 /* Per-launch record (QSIM_OPT_PROFILE=1) since the last qsim_reset_stats: returns the number of records and,
  * for 0 <= index < count, fills the kernel class, the fused blocks in that launch, the tile's high-qubit
  * mask and the HIP-event time. */
