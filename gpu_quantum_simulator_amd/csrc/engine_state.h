@@ -125,7 +125,7 @@ struct qsim_state {
     hipError_t alloc_err = hipSuccess;
 };
 
-// The re-layout of an exchange done by the stores of the last tile pass in front of it (qsim_flush_pack; kernels_impl.inc PACK).
+// The re-layout of an exchange done by the stores of the last tile pass in front of it (qsim_flush_pack; tile_kernel.inc k_tile PACK).
 struct PackJob {
     qsim::PackMap map{};
     int bits[3] = {0, 0, 0};

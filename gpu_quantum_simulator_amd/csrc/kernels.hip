@@ -16,6 +16,18 @@
 //                                                    quantum_simulator_preproces_constant.cu:169-178 — rebuilt
 //                                                    as a full-grid, LDS-tiled pass instead of one block
 // Index arithmetic is 64-bit throughout (the reference's `int th_id` stops at n = 31, naive.cu:74).
+//
+// The kernels and their launchers are generic in the amplitude precision by being compiled twice: the .inc files below are included,
+// in this order, inside namespace f64 and again inside namespace f32 (not templates: the order of the kernels in the code object
+// follows the order of definition, and code layout is part of what is measured).  Which file owns what:
+//   amp.inc              real_t, amp_t, kAmpShift; cmul, cfma, shfl_xor2
+//   gate_kernels.inc     k_init, k_zero_outside and the one-gate streaming kernels k_gate1_hi/lo, k_phase, k_diag1_full, k_cx, k_gate2_hh
+//   tile_kernel.inc      the tile pass: TileDev (+ make_tile_dev, tile_full), the LDS swizzle, coef_t, the hand-placed scalar loads,
+//                        PartPlan, tile_op_part, tile_op_small, tile_apply_ops, pack_perm, k_tile
+//   readout_kernels.inc  k_norm2, k_block_prob, k_block_prob_masked, k_gather_masked
+//   pack_kernel.inc      extract, PackDst, k_pack
+//   launch.inc           every host launcher: the grid helpers, tile_threads (the one shape rule), launch_tile_t (the one variant choice)
+// This file: what both precisions share, the two inclusions, and the precision dispatch behind the launchers of qsim_internal.h.
 #include <type_traits>
 #include "qsim_internal.h"
 
@@ -34,7 +46,12 @@ __device__ __forceinline__ uint64_t insert_zero(uint64_t t, int q) {
 #define QSIM_COEF_PAIRS 0
 #define QSIM_TILE_MIN_WAVES(T) 1 /* fp64: B=13 x 512 threads deliberately runs at 210 VGPRs, one workgroup per CU */
 namespace f64 {
-#include "kernels_impl.inc"
+#include "amp.inc"
+#include "gate_kernels.inc"
+#include "tile_kernel.inc"
+#include "readout_kernels.inc"
+#include "pack_kernel.inc"
+#include "launch.inc"
 } // namespace f64
 #undef QSIM_REAL
 #undef QSIM_AMP_SHIFT
@@ -43,10 +60,15 @@ namespace f64 {
 
 #define QSIM_REAL float
 #define QSIM_AMP_SHIFT 3
-#define QSIM_COEF_PAIRS 1 /* block coefficients arrive as (ur, ui) / (-ui, ur) pairs: v_pk_fma_f32 (kernels_impl.inc coef_t) */
+#define QSIM_COEF_PAIRS 1 /* block coefficients arrive as (ur, ui) / (-ui, ur) pairs: v_pk_fma_f32 (tile_kernel.inc coef_t) */
 #define QSIM_TILE_MIN_WAVES(T) ((T) >= 512 ? 4 : 1) /* fp32 tiles are half the LDS bytes: always two workgroups per CU */
 namespace f32 {
-#include "kernels_impl.inc"
+#include "amp.inc"
+#include "gate_kernels.inc"
+#include "tile_kernel.inc"
+#include "readout_kernels.inc"
+#include "pack_kernel.inc"
+#include "launch.inc"
 } // namespace f32
 #undef QSIM_REAL
 #undef QSIM_AMP_SHIFT

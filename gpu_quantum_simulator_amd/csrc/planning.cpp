@@ -64,7 +64,7 @@ uint64_t qsim::wisdom_epoch() { return g_wisdom_epoch.load(); }
 
 // The high bits the state is still zero in (new to the support with this pass) go to the top of the order, the others keep
 // theirs: the topmost bits are walked by the registers of a lane, and k_tile<SPARSE> then loads only the registers that hold
-// something (kernels_impl.inc tile_live_regs).  Stable, so placing twice changes nothing.
+// something (launch.inc tile_live_regs).  Stable, so placing twice changes nothing.
 void qsim::place_new_bits(TileGeom &g, uint64_t zero_mask) {
     std::stable_partition(g.high, g.high + g.n_high, [&](int b) { return !((zero_mask >> b) & 1ULL); });
 }

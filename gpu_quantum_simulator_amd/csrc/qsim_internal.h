@@ -71,7 +71,7 @@ struct TileOp {
     uint32_t pad1[8];
     PartRec rec[kMaxBanks][kMaxParts];
 };
-// TOP_PART header packing (tile_op.cpp writes it, kernels_impl.inc part_geometry / part_prepare read it): kLaneNibbles lane
+// TOP_PART header packing (tile_op.cpp writes it, tile_kernel.inc part_geometry / part_prepare read it): kLaneNibbles lane
 // nibbles in b[0..4], kLaneNone for a group-index bit that walks no tile bit, and in b[7] the bits of PartPlan::info the engine
 // decides — log2 T at kInfoLog2TShift, kInfoSkips, kInfoBarrier (a workgroup barrier between the reads and the writes).
 constexpr int kLaneNibbles = 10;

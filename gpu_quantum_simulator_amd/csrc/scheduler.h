@@ -104,7 +104,7 @@ struct TileBlock {
 
 // tile_op.cpp: the block as the TileOp k_tile reads under geometry g.  false when a qubit is on the wrong side of the tile or the
 // block cannot be expressed (Scheduler::merge_blocks never produces such a block).  f32: the state holds fp32 amplitudes — 8-byte
-// LDS slots, coefficients rounded once, here, and stored as the float pairs the fp32 kernels consume (kernels_impl.inc coef_t).
+// LDS slots, coefficients rounded once, here, and stored as the float pairs the fp32 kernels consume (tile_kernel.inc coef_t).
 bool to_tile_op(const TileGeom &g, const TileBlock &blk, TileOp &t, bool f32 = false);
 
 struct Pass {

@@ -1,227 +1,6 @@
-// kernels_impl.inc — the kernels and their launchers, generic in the amplitude precision.  Included twice by kernels.hip
-// (namespace f64: QSIM_REAL = double, 16-byte amplitudes; namespace f32: QSIM_REAL = float, 8-byte amplitudes — the
-// precision of the reference's CUDA variants, quantum_simulator_naive.cu:145-149).  No include guards on purpose.
-
-
-// Amplitudes travel as clang's native 2 x real vector (fp64: one global_load_dwordx4 / ds_read_b128 each; fp32: dwordx2 /
-// b64) and, unlike the HIP_vector_type wrapper, a first-class value (arrays of it stay in registers).
-typedef QSIM_REAL real_t;
-typedef real_t amp_t __attribute__((ext_vector_type(2)));
-constexpr int kAmpShift = QSIM_AMP_SHIFT; // log2(sizeof(amp_t))
-static_assert(sizeof(amp_t) == (1u << kAmpShift), "QSIM_AMP_SHIFT must match the amplitude size");
-
-// r = a*u (complex), then r += b*w — written as explicit FMAs so hipcc keeps one v_fma_f64 each.
-__device__ __forceinline__ amp_t cmul(amp_t a, real_t ur, real_t ui) {
-    amp_t r;
-    r.x = fma(a.x, ur, -(a.y * ui));
-    r.y = fma(a.x, ui, a.y * ur);
-    return r;
-}
-__device__ __forceinline__ amp_t cfma(amp_t a, real_t ur, real_t ui, amp_t acc) {
-    amp_t r;
-    r.x = fma(a.x, ur, fma(-a.y, ui, acc.x));
-    r.y = fma(a.x, ui, fma(a.y, ur, acc.y));
-    return r;
-}
-__device__ __forceinline__ amp_t shfl_xor2(amp_t a, int mask) {
-    amp_t r;
-    r.x = __shfl_xor(a.x, mask, 64);
-    r.y = __shfl_xor(a.y, mask, 64);
-    return r;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// |0...0>
-__global__ __launch_bounds__(TPB) void k_init(amp_t *__restrict__ v, uint64_t N, double amp0) {
-    const uint64_t stride = (uint64_t)gridDim.x * TPB;
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < N; i += stride)
-        v[i] = amp_t{(real_t)(i == 0 ? amp0 : 0.0), (real_t)0};
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Dense 2x2, target bit q >= 6.  Work item = amplitude pair (i0, i0 | 2^q); consecutive lanes take
-// consecutive i0, so each wave-instruction reads/writes one contiguous KiB from each of two streams
-// 2^q amplitudes apart.  IPT pairs per thread -> 2*IPT independent 16-B loads in flight per lane.
-// Zeroes every amplitude whose index has a bit of zero_mask set: materialises a state that the tile passes have only
-// written inside its support so far (qsim_state::support).  Write-only.
-__global__ __launch_bounds__(TPB) void k_zero_outside(amp_t *__restrict__ v, uint64_t N, uint64_t zero_mask) {
-    const uint64_t stride = (uint64_t)gridDim.x * TPB;
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < N; i += stride)
-        if (i & zero_mask) v[i] = amp_t{(real_t)0, (real_t)0};
-}
-
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_gate1_hi(amp_t *__restrict__ v, uint64_t npairs, int q, M2 U,
-                                                  uint64_t ntiles) {
-    const uint64_t bit = 1ULL << q;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        uint64_t i0[IPT];
-        amp_t a0[IPT], a1[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            i0[k] = insert_zero(t, q);
-            if (!GUARD || t < npairs) {
-                a0[k] = v[i0[k]];
-                a1[k] = v[i0[k] | bit];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            if (!GUARD || t < npairs) {
-                v[i0[k]] = cfma(a1[k], U.re[1], U.im[1], cmul(a0[k], U.re[0], U.im[0]));
-                v[i0[k] | bit] = cfma(a1[k], U.re[3], U.im[3], cmul(a0[k], U.re[2], U.im[2]));
-            }
-        }
-    }
-}
-
-// Dense 2x2, target bit q < 6: both amplitudes of a pair sit in the same wave's contiguous KiB.  Each
-// lane loads its own amplitude (perfectly coalesced), fetches the partner's with a wave shuffle
-// (lane ^ 2^q — the butterfly), and computes its own output row.  Same flops per amplitude as the pair
-// form, no second pass, no LDS allocation.
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_gate1_lo(amp_t *__restrict__ v, uint64_t N, int q, M2 U, uint64_t ntiles) {
-    const bool up = (threadIdx.x >> q) & 1; // bit q of the amplitude index == bit q of the lane id
-    const real_t own_r = up ? U.re[3] : U.re[0], own_i = up ? U.im[3] : U.im[0];
-    const real_t par_r = up ? U.re[2] : U.re[1], par_i = up ? U.im[2] : U.im[1];
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t i0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        amp_t a[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t i = i0 + (uint64_t)k * TPB;
-            a[k] = (!GUARD || i < N) ? v[i] : amp_t{(real_t)0, (real_t)0};
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t i = i0 + (uint64_t)k * TPB;
-            const amp_t p = shfl_xor2(a[k], 1 << q);
-            const amp_t r = cfma(p, par_r, par_i, cmul(a[k], own_r, own_i));
-            if (!GUARD || i < N) v[i] = r;
-        }
-    }
-}
-
-// diag(1, lambda): only the bit=1 half is read and written (16*N bytes instead of 32*N).
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_phase(amp_t *__restrict__ v, uint64_t nitems, int q, double lr, double li,
-                                               uint64_t ntiles) {
-    const uint64_t bit = 1ULL << q;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        uint64_t idx[IPT];
-        amp_t a[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            idx[k] = insert_zero(t, q) | bit;
-            if (!GUARD || t < nitems) a[k] = v[idx[k]];
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            if (!GUARD || t < nitems) v[idx[k]] = cmul(a[k], lr, li);
-        }
-    }
-}
-
-// diag(d0, d1) over every amplitude (used when d0 != 1, or when q < 2 makes the half form touch every
-// 64-B sector anyway).
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_diag1_full(amp_t *__restrict__ v, uint64_t N, int q, double d0r, double d0i,
-                                                    double d1r, double d1i, uint64_t ntiles) {
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t i0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        amp_t a[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t i = i0 + (uint64_t)k * TPB;
-            if (!GUARD || i < N) a[k] = v[i];
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t i = i0 + (uint64_t)k * TPB;
-            const bool up = (i >> q) & 1;
-            if (!GUARD || i < N) v[i] = cmul(a[k], up ? d1r : d0r, up ? d1i : d0i);
-        }
-    }
-}
-
-// CX: swap v[i | c] <-> v[i | c | t] over the N/4 indices i with both bits clear.
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_cx(amp_t *__restrict__ v, uint64_t nitems, int lo, int hi, uint64_t cbit,
-                                            uint64_t tbit, uint64_t ntiles) {
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        uint64_t ia[IPT];
-        amp_t a[IPT], b[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            ia[k] = insert_zero(insert_zero(t, lo), hi) | cbit;
-            if (!GUARD || t < nitems) {
-                a[k] = v[ia[k]];
-                b[k] = v[ia[k] | tbit];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            if (!GUARD || t < nitems) {
-                v[ia[k]] = b[k];
-                v[ia[k] | tbit] = a[k];
-            }
-        }
-    }
-}
-
-// Dense 4x4 with both target bits >= 6: four coalesced streams, all arithmetic in registers, matrix in
-// kernel arguments (scalar registers).  Row/column index = (bit hi, bit lo), row-major
-// (quantum_simulator_4x4.cu:119-134).
-template <int IPT, bool GUARD>
-__global__ __launch_bounds__(TPB) void k_gate2_hh(amp_t *__restrict__ v, uint64_t nitems, int lo, int hi, M4 U,
-                                                  uint64_t ntiles) {
-    const uint64_t blo = 1ULL << lo, bhi = 1ULL << hi;
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * (uint64_t)(TPB * IPT) + threadIdx.x;
-        uint64_t i00[IPT];
-        amp_t x[IPT][4];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            i00[k] = insert_zero(insert_zero(t, lo), hi);
-            if (!GUARD || t < nitems) {
-                x[k][0] = v[i00[k]];
-                x[k][1] = v[i00[k] | blo];
-                x[k][2] = v[i00[k] | bhi];
-                x[k][3] = v[i00[k] | bhi | blo];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t t = t0 + (uint64_t)k * TPB;
-            if (!GUARD || t < nitems) {
-                amp_t y[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    amp_t acc = cmul(x[k][0], U.re[4 * r], U.im[4 * r]);
-#pragma unroll
-                    for (int c = 1; c < 4; c++) acc = cfma(x[k][c], U.re[4 * r + c], U.im[4 * r + c], acc);
-                    y[r] = acc;
-                }
-                v[i00[k]] = y[0];
-                v[i00[k] | blo] = y[1];
-                v[i00[k] | bhi] = y[2];
-                v[i00[k] | bhi | blo] = y[3];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
+// tile_kernel.inc — the cache-blocked pass: TileDev, the LDS swizzle and coefficient types, the hand-placed scalar loads, the part
+// records and block forms, and k_tile itself.
+//
 // Cache-blocked pass.  A tile is the 2^B amplitudes that agree on every index bit outside the tile set
 // T = {0..L-1} U {high[0..H-1]}; it is 2^H contiguous runs of 2^L amplitudes (16*2^L bytes each), so
 // global traffic stays in whole-KiB pieces whatever the high qubits are.  One workgroup stages a tile
@@ -245,6 +24,23 @@ struct TileDev {
     int8_t high[16];    // ... and in order: tile-local bit L+j is global bit high[j].  ANY order: which tile bits the lanes of a
                         // wave, the waves of a workgroup and the registers of a lane walk is the engine's choice
 };
+static TileDev make_tile_dev(const TileGeom &g, bool from_zero_ket, double amp0, uint64_t zero_mask, int live_regs) {
+    TileDev td{};
+    td.tile_bits = g.tile_bits; td.low_bits = g.low_bits; td.n_high = g.n_high; td.n = g.n;
+    td.from_zero_ket = from_zero_ket ? 1 : 0;
+    td.amp0 = amp0;
+    td.zero_mask = zero_mask;
+    td.live_regs = live_regs;
+    for (int j = 0; j < g.n_high; j++) { td.high_mask |= 1ULL << g.high[j]; td.high[j] = (int8_t)g.high[j]; }
+    return td;
+}
+
+// `threads` lanes share `items` pieces of work in whole rounds: every lane has one in every round, no tail guard.
+constexpr bool whole_rounds(uint32_t items, uint32_t threads) { return items >= threads && items % threads == 0; }
+// A tile of `slots` amplitudes is staged in and out without tail guards (k_tile's FULL; tile_live_regs on the host): asked of
+// the slot QUADS.  PartPlan::FULL asks the same of a block's 8-row items instead, and the two differ: 2^10 slots on 256
+// threads are whole rounds of quads and half a round of items, so that tile stages unguarded and applies its blocks guarded.
+constexpr bool tile_full(uint32_t slots, uint32_t threads) { return whole_rounds(slots / 4, threads); }
 
 // software PDEP: spreads the low bits of x over the set bits of mask, lowest first
 __device__ __forceinline__ uint64_t deposit(uint64_t x, uint64_t mask) {
@@ -356,6 +152,19 @@ __device__ __forceinline__ coef_t sgpr_coef(const V &v, int j) {
 #endif
 }
 constexpr int kRecCoefByte = 2 * kPartRows * 4; // offsetof(PartRec, coef)
+// The row offsets and the first NB coefficient batches of a record, and the wait that names them.  (The four coef_t of a batch
+// stay written out where they are used: built by a helper, the same rows change the schedule of every k_tile with blocks.)
+template <int NB>
+__device__ __forceinline__ void load_rows(ConstRec rec, u32x8 &rowoff, u32x16 &c0, u32x16 &c1, u32x16 &c2, u32x16 &c3) {
+    rowoff = sload8<32>(rec);
+    c0 = sload16<kRecCoefByte>(rec); c1 = sload16<kRecCoefByte + 64>(rec);
+    if constexpr (NB == 4) {
+        c2 = sload16<kRecCoefByte + 128>(rec); c3 = sload16<kRecCoefByte + 192>(rec);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+    } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1));
+    }
+}
 
 // One TOP_PART block (qsim_internal.h): every lane owns one (group, part) = 8 positions of the block, i.e. 8 / T whole classes;
 // the parts of a group are dealt part-major, so a wave works on ONE part and everything it needs of the block is the one
@@ -370,6 +179,7 @@ template <int B, int THREADS>
 struct PartPlan {
     static constexpr uint32_t ITEMS = (1u << B) / kPartRows;
     static constexpr int IPT = ITEMS >= (uint32_t)THREADS ? ITEMS / THREADS : 1;
+    static constexpr bool FULL = whole_rounds(ITEMS, THREADS); // over the items, not tile_full's slot quads
     ConstRec rec[IPT];
     uint32_t base[IPT];
     uint32_t info; // bit 0: run (the tile's bank is not the identity), bits 1-2: log2 T, bit 3: skips, bit 4: barrier between reads and writes
@@ -412,10 +222,9 @@ __device__ __forceinline__ PartPlan<B, THREADS> part_prepare(uint32_t lds_base, 
 
 template <int B, int THREADS, int T, bool SKIPS>
 __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uint32_t tid, bool mid_barrier) {
-    constexpr uint32_t E = 1u << B;
-    constexpr uint32_t ITEMS = E / kPartRows;
-    constexpr int IPT = ITEMS >= (uint32_t)THREADS ? ITEMS / THREADS : 1;
-    constexpr bool FULL = ITEMS >= (uint32_t)THREADS && ITEMS % THREADS == 0;
+    constexpr uint32_t ITEMS = PartPlan<B, THREADS>::ITEMS;
+    constexpr int IPT = PartPlan<B, THREADS>::IPT;
+    constexpr bool FULL = PartPlan<B, THREADS>::FULL;
     constexpr int NC = kPartRows / T; // classes per part
     static_assert(kRecCoefByte == 64 && sizeof(PartRec) == 64 + 512, "record layout");
     const ConstRec *rec = pl.rec;
@@ -473,10 +282,7 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
             // (4 result registers live instead of 8 — the VGPRs that buys are the second tile of prefetch — and the LDS store path,
             // 13 cycles per wave-instruction, gets its work in two helpings)
             if constexpr (IPT != 1) {
-                rowoff = sload8<32>(rec[i]);
-                c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]);
-                c2 = sload16<kRecCoefByte + 128>(rec[i]); c3 = sload16<kRecCoefByte + 192>(rec[i]);
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+                load_rows<4>(rec[i], rowoff, c0, c1, c2, c3);
             } else {
                 rowoff = rowoff1;
             }
@@ -512,10 +318,7 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
             continue; // (written above)
         } else if constexpr (T == 2) {
             if constexpr (IPT != 1) {
-                rowoff = sload8<32>(rec[i]);
-                c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]);
-                c2 = sload16<kRecCoefByte + 128>(rec[i]); c3 = sload16<kRecCoefByte + 192>(rec[i]); // two rows of two entries each
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3));
+                load_rows<4>(rec[i], rowoff, c0, c1, c2, c3); // a batch: two rows of two entries each
             } else {
                 rowoff = rowoff1;
             }
@@ -530,9 +333,7 @@ __device__ __forceinline__ void tile_op_part(const PartPlan<B, THREADS> &pl, uin
             }
         } else {
             if constexpr (IPT != 1) {
-                rowoff = sload8<32>(rec[i]);
-                c0 = sload16<kRecCoefByte>(rec[i]); c1 = sload16<kRecCoefByte + 64>(rec[i]); // four rows of one entry each
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(rowoff), "+s"(c0), "+s"(c1));
+                load_rows<2>(rec[i], rowoff, c0, c1, c2, c3); // a batch: four rows of one entry each
             } else {
                 rowoff = rowoff1;
             }
@@ -662,7 +463,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     amp_t *lds = reinterpret_cast<amp_t *>(smem);
     constexpr uint32_t E = 1u << B;
     constexpr int APT = (E + THREADS - 1) / THREADS;                              // amplitudes per thread
-    constexpr bool FULL = E / 4 >= THREADS && (E / 4) % THREADS == 0;              // no tail guards needed
+    constexpr bool FULL = tile_full(E, THREADS);                                   // no tail guards needed
     const int L = g.low_bits, H = g.n_high;
     uint64_t *hoff = reinterpret_cast<uint64_t *>(smem + (sizeof(amp_t) << B));
     ConstOps scales = (ConstOps)(uintptr_t)ops_g; // n_scale tile-uniform factors, then the n_ops blocks
@@ -672,6 +473,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     // parts share no bit (tid < THREADS, a power of two >= 64)
     const uint32_t tid_sw = sw_slot(tid);
     auto stage_slot = [&](int k) { return (tid_sw ^ lds_sw_fold<kAmpShift>((uint32_t)(k * THREADS) >> kSwLow)) + (uint32_t)(k * THREADS); };
+    auto live = [&](int k) { return FULL || tid + k * THREADS < E; }; // the lane's slot k exists (tiles with tail guards)
     const uint32_t lowmask = (1u << L) - 1u;
     const uint64_t nmask = g.n >= 64 ? ~0ULL : ((1ULL << g.n) - 1ULL);
     const uint64_t outer_mask = nmask & ~(g.high_mask | (uint64_t)lowmask) & ~g.zero_mask; // the tiles to visit: outer bits that may be 1
@@ -754,10 +556,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
             return;
         }
 #pragma unroll
-        for (int k = 0; k < APT; k++) {
-            const uint32_t e = tid + k * THREADS;
-            pf[k] = (FULL || e < E) ? *elem_ptr(tb, k) : amp_t{(real_t)0, (real_t)0};
-        }
+        for (int k = 0; k < APT; k++) pf[k] = live(k) ? *elem_ptr(tb, k) : amp_t{(real_t)0, (real_t)0};
     };
     auto process = [&](uint64_t base, bool prefetch_next) {
         if (n_scale > 0) { // wave-uniform: blocks whose qubits all lie outside the tile are one factor per tile
@@ -779,10 +578,8 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
                 if (!(sparse_lane_ok && ((k_off[k] >> kAmpShift) & g.zero_mask) == 0)) pf[k] = amp_t{(real_t)0, (real_t)0};
         }
 #pragma unroll
-        for (int k = 0; k < APT; k++) {
-            const uint32_t e = tid + k * THREADS;
-            if (FULL || e < E) lds[stage_slot(k)] = pf[k];
-        }
+        for (int k = 0; k < APT; k++)
+            if (live(k)) lds[stage_slot(k)] = pf[k];
         __syncthreads();
         if (prefetch_next) fetch(next_base(base));
 
@@ -792,24 +589,18 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
         // whose wave-uniform address part (tile base + register-bit offset + distance to the output buffer) stays scalar
         amp_t so[APT];
 #pragma unroll
-        for (int k = 0; k < APT; k++) {
-            const uint32_t e = tid + k * THREADS;
-            if (FULL || e < E) so[k] = lds[stage_slot(k)];
-        }
-        if (PACK) {
+        for (int k = 0; k < APT; k++)
+            if (live(k)) so[k] = lds[stage_slot(k)];
+        if (PACK) { // (two loops on purpose: one loop over a PACK ? : address leaves the guarded small tiles with other code)
             const uint64_t sbase = (pack_perm(pm, base) | pm.konst) << kAmpShift; // wave-uniform
 #pragma unroll
-            for (int k = 0; k < APT; k++) {
-                const uint32_t e = tid + k * THREADS;
-                if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(vout) + lane_out + (sbase + k_out[k])) = so[k];
-            }
+            for (int k = 0; k < APT; k++)
+                if (live(k)) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(vout) + lane_out + (sbase + k_out[k])) = so[k];
         } else {
             const uint64_t sbase = (base << kAmpShift) + (uint64_t)out_shift; // wave-uniform
 #pragma unroll
-            for (int k = 0; k < APT; k++) {
-                const uint32_t e = tid + k * THREADS;
-                if (FULL || e < E) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(v) + lane_off + (sbase + k_off[k])) = so[k];
-            }
+            for (int k = 0; k < APT; k++)
+                if (live(k)) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(v) + lane_off + (sbase + k_off[k])) = so[k];
         }
         __syncthreads();
     };
@@ -821,419 +612,4 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
         base = next_base(base);
         process(base, j + 1 < cnt);
     }
-}
-
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void k_norm2(const amp_t *__restrict__ v, uint64_t N, double *out) {
-    double acc = 0.0;
-    const uint64_t stride = (uint64_t)gridDim.x * TPB;
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < N; i += stride) {
-        const amp_t a = v[i];
-        acc = fma((double)a.x, (double)a.x, fma((double)a.y, (double)a.y, acc));
-    }
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    __shared__ double part[TPB / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < TPB / 64; w++) s += part[w];
-        atomicAdd(out, s);
-    }
-}
-
-// Probability mass per block of 2^block_bits amplitudes (measurement post-path).  One workgroup per block; the
-// reduction order is fixed (lane-strided partial sums, xor-butterfly inside the wave, waves added in order), so the
-// result does not depend on scheduling.
-__global__ __launch_bounds__(TPB) void k_block_prob(const amp_t *__restrict__ v, uint64_t N, int block_bits,
-                                                    double *__restrict__ out, uint64_t nblocks) {
-    __shared__ double part[TPB / 64];
-    for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        const uint64_t lo = b << block_bits;
-        uint64_t hi = lo + (1ULL << block_bits);
-        if (hi > N) hi = N;
-        double acc = 0.0;
-        for (uint64_t i = lo + threadIdx.x; i < hi; i += TPB) {
-            const amp_t a = v[i];
-            acc += fma((double)a.x, (double)a.x, (double)a.y * (double)a.y);
-        }
-        for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int w = 0; w < TPB / 64; w++) t += part[w];
-            out[b] = t;
-        }
-        __syncthreads();
-    }
-}
-
-// The same sums over blocks that are NOT contiguous: block w holds the amplitudes at deposit(w, hi_mask) | deposit(i,
-// lo_mask), i = 0 .. 2^lo_bits - 1 (hi_mask and lo_mask are disjoint sets of index bits).  A sharded state whose qubit
-// map was permuted by exchanges keeps a LOGICAL block of the measurement post-path in such a set of local positions, so
-// the block sums are formed where the amplitudes are and only the sums travel to the host.  Same fixed reduction order.
-__global__ __launch_bounds__(TPB) void k_block_prob_masked(const amp_t *__restrict__ v, uint64_t hi_mask, uint64_t lo_mask, int lo_bits,
-                                                           double *__restrict__ out, uint64_t nblocks) {
-    __shared__ double part[TPB / 64];
-    const uint64_t count = 1ULL << lo_bits;
-    for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        const uint64_t base = deposit(b, hi_mask);
-        double acc = 0.0;
-        for (uint64_t i = threadIdx.x; i < count; i += TPB) {
-            const amp_t a = v[base | deposit(i, lo_mask)];
-            acc += fma((double)a.x, (double)a.x, (double)a.y * (double)a.y);
-        }
-        for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int w = 0; w < TPB / 64; w++) t += part[w];
-            out[b] = t;
-        }
-        __syncthreads();
-    }
-}
-
-// out[i] = v[base | deposit(i, lo_mask)]: one such block, in the order of i, for the host to look inside.
-__global__ __launch_bounds__(TPB) void k_gather_masked(const amp_t *__restrict__ v, uint64_t base, uint64_t lo_mask, uint64_t count,
-                                                       amp_t *__restrict__ out) {
-    const uint64_t stride = (uint64_t)gridDim.x * TPB;
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < count; i += stride) out[i] = v[base | deposit(i, lo_mask)];
-}
-
-// Shard re-layout ahead of a global<->local qubit exchange: gathers so that the p selected index bits
-// become the top p bits (the destination block id) while the other bits keep their order.  Writes are
-// fully coalesced; reads come in runs of 2^bits[0] amplitudes.
-// Scatter form: consecutive lanes READ consecutive amplitudes (always fully coalesced); a wave's 64 stores
-// fall into 2^(selected bits below 6) contiguous segments, i.e. >= 128 B pieces for up to three selected
-// bits wherever they are.  (The gather form would read 16/32-B fragments when bit 0 or 1 is selected and
-// fetch those sectors once per destination block.)
-// dst = (pext(src, sel) << rest_bits) | pext(src, keep).  PEXT over disjoint bit ranges splits, so the part
-// that depends on the work tile is wave-uniform scalar work and the part that depends on the lane is
-// computed once per thread, outside the tile loop.
-__device__ __forceinline__ uint64_t extract(uint64_t x, uint64_t mask) { // software PEXT
-    uint64_t out = 0;
-    int k = 0;
-    while (mask) {
-        const uint64_t low = mask & (0 - mask);
-        if (x & low) out |= 1ULL << k;
-        k++;
-        mask &= mask - 1;
-    }
-    return out;
-}
-
-// Block b of the packed layout need not follow block b-1 in memory: each of the 2^p blocks has its own destination, so
-// a shard can write its blocks straight into the buffers of the group members that will own them (another shard's
-// buffer on the same device, or a peer-mapped one) — pack and transfer in one kernel.  Up to 8 blocks (p <= 3) travel
-// as kernel arguments; the single-buffer layout is the special case blk[b] = out + b * 2^(n-p).
-struct PackDst { amp_t *blk[8]; };
-__device__ __forceinline__ amp_t *pack_block(const PackDst &d, uint32_t b) {
-    amp_t *r = d.blk[0];
-#pragma unroll
-    for (uint32_t j = 1; j < 8; j++) r = (b == j) ? d.blk[j] : r; // select chain: no runtime-indexed kernel-argument array
-    return r;
-}
-
-template <int IPT, bool SPLIT>
-__global__ __launch_bounds__(TPB) void k_pack(const amp_t *__restrict__ in, amp_t *__restrict__ out, PackDst dst, uint64_t N, int n,
-                                              int p, uint64_t sel_mask, uint64_t ntiles, uint32_t skip, uint64_t zero_mask) {
-    constexpr int SB = 10; // log2(TPB * IPT): index bits owned by the position inside a work tile
-    static_assert(TPB * IPT == (1 << SB), "tile split");
-    const int rest_bits = n - p;
-    const uint64_t nmask = n >= 64 ? ~0ULL : ((1ULL << n) - 1ULL);
-    const uint64_t keep_mask = nmask & ~sel_mask;
-    const uint64_t lo = (1ULL << SB) - 1ULL;
-    const uint64_t rest_mask = (1ULL << rest_bits) - 1ULL;
-    const int pc_keep_lo = __popcll(keep_mask & lo), pc_sel_lo = __popcll(sel_mask & lo);
-    uint64_t add[IPT];
-#pragma unroll
-    for (int k = 0; k < IPT; k++) {
-        const uint64_t e = (uint64_t)k * TPB + threadIdx.x;
-        add[k] = (extract(e, sel_mask & lo) << rest_bits) | extract(e, keep_mask & lo);
-    }
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t base = ((extract(tile, sel_mask >> SB) << pc_sel_lo) << rest_bits) |
-                              (extract(tile, keep_mask >> SB) << pc_keep_lo); // wave-uniform
-        const uint64_t s0 = (tile << SB) + threadIdx.x;
-        amp_t a[IPT];
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t sidx = s0 + (uint64_t)k * TPB;
-            // zero_mask: index bits the state is zero in BY DEFINITION (memory outside its support was never written: qsim_state::support)
-            a[k] = (sidx < N && !(sidx & zero_mask)) ? in[sidx] : amp_t{(real_t)0, (real_t)0};
-        }
-#pragma unroll
-        for (int k = 0; k < IPT; k++) {
-            const uint64_t sidx = s0 + (uint64_t)k * TPB;
-            if (sidx >= N) continue;
-            const uint64_t di = base | add[k];
-            if (skip && ((skip >> (uint32_t)(di >> rest_bits)) & 1u)) continue; // a block nobody will read (its receiver holds nothing afterwards)
-            if (SPLIT) pack_block(dst, (uint32_t)(di >> rest_bits))[di & rest_mask] = a[k];
-            else out[di] = a[k];
-        }
-    }
-}
-
-// ===================================================================================================
-// launchers
-static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-static inline unsigned grid_for(const LaunchCfg &cfg, uint64_t ntiles) {
-    uint64_t g = ntiles;
-    if (cfg.grid_cap > 0 && g > (uint64_t)cfg.grid_cap) g = (uint64_t)cfg.grid_cap;
-    if (g > kMaxGrid) g = kMaxGrid;
-    return (unsigned)(g ? g : 1);
-}
-
-hipError_t launch_init(const LaunchCfg &cfg, void *v, int n, double amp0) {
-    const uint64_t N = 1ULL << n;
-    uint64_t blocks = ceil_div(N, TPB);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_init, dim3((unsigned)blocks), dim3(TPB), 0, cfg.stream, (amp_t *)v, N, amp0);
-    return hipGetLastError();
-}
-
-hipError_t launch_zero_outside(const LaunchCfg &cfg, void *v, int n, uint64_t zero_mask) {
-    const uint64_t N = 1ULL << n;
-    uint64_t grid = ceil_div(N, TPB);
-    if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(k_zero_outside, dim3((unsigned)grid), dim3(TPB), 0, cfg.stream, (amp_t *)v, N, zero_mask);
-    return hipGetLastError();
-}
-
-#define QSIM_DISPATCH_GUARD(KERN, IPT, items, ...)                                                                    \
-    do {                                                                                                              \
-        const uint64_t nt_ = ceil_div((items), (uint64_t)TPB * (IPT));                                                \
-        if ((items) % ((uint64_t)TPB * (IPT)) == 0)                                                                   \
-            hipLaunchKernelGGL((KERN<IPT, false>), dim3(grid_for(cfg, nt_)), dim3(TPB), 0, cfg.stream, __VA_ARGS__,    \
-                               nt_);                                                                                  \
-        else                                                                                                          \
-            hipLaunchKernelGGL((KERN<IPT, true>), dim3(grid_for(cfg, nt_)), dim3(TPB), 0, cfg.stream, __VA_ARGS__,     \
-                               nt_);                                                                                  \
-    } while (0)
-
-hipError_t launch_gate1(const LaunchCfg &cfg, void *v, int n, int q, const M2 &U) {
-    const uint64_t N = 1ULL << n;
-    if (q >= 6) {
-        const uint64_t npairs = N >> 1;
-        QSIM_DISPATCH_GUARD(k_gate1_hi, 4, npairs, (amp_t *)v, npairs, q, U);
-    } else {
-        QSIM_DISPATCH_GUARD(k_gate1_lo, 4, N, (amp_t *)v, N, q, U);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_phase(const LaunchCfg &cfg, void *v, int n, int q, double lr, double li) {
-    const uint64_t items = (1ULL << n) >> 1;
-    QSIM_DISPATCH_GUARD(k_phase, 4, items, (amp_t *)v, items, q, lr, li);
-    return hipGetLastError();
-}
-
-hipError_t launch_diag1_full(const LaunchCfg &cfg, void *v, int n, int q, double d0r, double d0i, double d1r,
-                             double d1i) {
-    const uint64_t N = 1ULL << n;
-    QSIM_DISPATCH_GUARD(k_diag1_full, 4, N, (amp_t *)v, N, q, d0r, d0i, d1r, d1i);
-    return hipGetLastError();
-}
-
-hipError_t launch_cx(const LaunchCfg &cfg, void *v, int n, int control, int target) {
-    if (control == target) return hipSuccess; // quantum_simulator.c:99 — no index qualifies
-    const uint64_t items = (1ULL << n) >> 2;
-    const int lo = control < target ? control : target, hi = control < target ? target : control;
-    const uint64_t cbit = 1ULL << control, tbit = 1ULL << target;
-    QSIM_DISPATCH_GUARD(k_cx, 4, items, (amp_t *)v, items, lo, hi, cbit, tbit);
-    return hipGetLastError();
-}
-
-hipError_t launch_gate2(const LaunchCfg &cfg, void *v, int n, int q_hi, int q_lo, const M4 &U) {
-    const uint64_t items = (1ULL << n) >> 2;
-    QSIM_DISPATCH_GUARD(k_gate2_hh, 2, items, (amp_t *)v, items, q_lo, q_hi, U);
-    return hipGetLastError();
-}
-
-static int tile_lds_bytes(int tile_bits, int n_high) { return ((int)sizeof(amp_t) << tile_bits) + (8 << n_high); }
-
-constexpr bool tile_has_pack(int b, int threads) { return kAmpShift == 4 && b == 12 && threads == 512; } // the production shape of fp64 shards
-
-// How many registers of a lane hold slots inside the support (TileDev::live_regs): all of them, halved for every high bit in
-// zero_mask counted from the top of the order down, as far as the register role reaches.  Tiles with tail guards: all.
-static int tile_live_regs(const TileGeom &g, int threads, uint64_t zero_mask) {
-    const int slots = 1 << g.tile_bits;
-    if (slots / 4 < threads || (slots / 4) % threads != 0) return (slots + threads - 1) / threads; // not FULL: the guarded path loads every slot
-    int live = slots / threads;
-    for (int j = g.n_high - 1; j >= 0 && live > 1 && ((zero_mask >> g.high[j]) & 1ULL); j--) live >>= 1;
-    return live;
-}
-
-template <int B, int THREADS>
-static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops,
-                                bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
-    uint64_t tile_mask = (1ULL << g.low_bits) - 1ULL;
-    for (int j = 0; j < g.n_high; j++) tile_mask |= 1ULL << g.high[j];
-    const uint64_t nmask = g.n >= 64 ? ~0ULL : ((1ULL << g.n) - 1ULL);
-    zero_mask &= nmask; // (a generating pass gets all bits from the engine: only the tile at base 0 exists)
-    const uint64_t ntiles = 1ULL << __builtin_popcountll(nmask & ~tile_mask & ~zero_mask); // tiles whose base index may be non-zero
-    const int lds = tile_lds_bytes(g.tile_bits, g.n_high);
-    // the opt-in to more than 64 KiB of dynamic LDS is per device (a cluster drives several from one process)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    constexpr bool kHasPack = tile_has_pack(B, THREADS);
-    const bool packed = pack != nullptr && pack->k > 0;
-    if (packed && !kHasPack) return hipErrorNotSupported;
-    // four instantiations at most (PACK x SPARSE), each opted in once per device
-    const bool sparse = zero_mask != 0 && !from_zero_ket; // a pass over a partially written state: k_tile<SPARSE>
-    static bool attr_set[4][64] = {{false}};
-    auto opt_in = [&](const void *fn, int which) -> hipError_t {
-        if (attr_set[which][dev]) return hipSuccess;
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) attr_set[which][dev] = true;
-        return e;
-    };
-    {
-        hipError_t e = opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, false, false>), 0);
-        // (the warm-up call opts in both plain instantiations: a run from a reset needs the SPARSE one a pass or two later)
-        if (e == hipSuccess && ((sparse && !packed) || cfg.warm_only)) e = opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, false, true>), 1);
-        if constexpr (kHasPack) {
-            if (e == hipSuccess && packed)
-                e = sparse ? opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, true, true>), 3) : opt_in(reinterpret_cast<const void *>(&k_tile<B, THREADS, true, false>), 2);
-        }
-        if (e != hipSuccess) return e;
-    }
-    if (cfg.warm_only) return hipSuccess;
-    TileDev td;
-    td.tile_bits = g.tile_bits; td.low_bits = g.low_bits; td.n_high = g.n_high; td.n = g.n;
-    td.from_zero_ket = from_zero_ket ? 1 : 0;
-    td.amp0 = amp0;
-    td.high_mask = 0;
-    td.zero_mask = zero_mask;
-    for (int j = 0; j < 16; j++) td.high[j] = 0;
-    for (int j = 0; j < g.n_high; j++) { td.high_mask |= 1ULL << g.high[j]; td.high[j] = (int8_t)g.high[j]; }
-    // the registers of a lane walk the topmost high bits (tile slot bits log2(THREADS) .. B-1): each of them, from the top, that
-    // the state is zero in halves the registers that hold anything
-    td.live_regs = tile_live_regs(g, THREADS, sparse ? zero_mask : 0);
-    // tiles per workgroup: enough to amortise the exposed first load — 64 where that still leaves four rounds of workgroups
-    // (2048), down to 8 otherwise.  Round 4, late: 64 instead of 8 takes 1 % off a step at every size (tools/tpw_sweep.py: n = 30
-    // 66.0 -> 65.4 ms, 128 tiles 66.3, 256 68.3, one round of 512 workgroups 69.6; n = 28 17.14 -> 16.9 with 32; n = 32 260.7 -> 258.8) ...
-    int tpw = cfg.grid_cap > 0 ? (int)((ntiles + cfg.grid_cap - 1) / (uint64_t)cfg.grid_cap) : 64;
-    if (cfg.grid_cap <= 0)
-        while (tpw > 8 && ntiles / (uint64_t)tpw < 2048) tpw >>= 1;
-    // ... but never fewer workgroups than the chip holds at once (2 per CU with 64 KiB tiles): a workgroup that walks
-    // several tiles prefetches the next one while it works, one with a single tile exposes its load.  Small registers
-    // used to get one tile per workgroup (">= 4096 workgroups"): n = 24 356 k -> 502 k gate-applies/s, n = 25 229 k ->
-    // 255 k, n = 26 129 k -> 133 k with the floor at 512; from n = 27 up there are 4096 workgroups of 8 tiles either way.
-    constexpr uint64_t kMinWorkgroups = 512;
-    while (tpw > 1 && ntiles / (uint64_t)tpw < kMinWorkgroups) tpw >>= 1;
-    if (tpw < 1) tpw = 1;
-    const uint64_t grid = (ntiles + tpw - 1) / (uint64_t)tpw;
-    // d_ops: g.n_scale tile-uniform factors first, then the blocks
-    const int n_scale = n_ops > 0 ? g.n_scale : 0;
-    PackMap pm{};
-#define QSIM_TILE_GO(PACK_, SPARSE_, PM_)                                                                                                          \
-    hipLaunchKernelGGL((k_tile<B, THREADS, PACK_, SPARSE_>), dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, \
-                       n_ops - n_scale, ntiles, tpw, n_scale, PM_)
-    if constexpr (kHasPack) {
-        if (packed) {
-            if (sparse) QSIM_TILE_GO(true, true, *pack);
-            else QSIM_TILE_GO(true, false, *pack);
-            return hipGetLastError();
-        }
-    }
-    if (sparse) QSIM_TILE_GO(false, true, pm);
-    else QSIM_TILE_GO(false, false, pm);
-#undef QSIM_TILE_GO
-    return hipGetLastError();
-}
-
-// threads: 0 = the default for the tile size.  Tiles below 2^8 amplitudes (tiny registers) use the 2^8 kernel's
-// tail guards with a smaller E, so every size from 1 to 13 bits has an instantiation.
-// which (tile size, thread count) launch_tile picks for a geometry: the re-layout variant exists for one of them
-static bool launch_tile_can_pack(const TileGeom &g, int threads) { return tile_has_pack(g.tile_bits, g.tile_bits == 12 && threads != 256 && threads != 1024 ? 512 : 0); }
-
-hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads,
-                       bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
-#define QSIM_TILE(B_, T_) launch_tile_t<B_, T_>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, zero_mask, pack)
-    switch (g.tile_bits) {
-    case 0: return QSIM_TILE(0, 64);
-    case 1: return QSIM_TILE(1, 64);
-    case 2: return QSIM_TILE(2, 64);
-    case 3: return QSIM_TILE(3, 64);
-    case 4: return QSIM_TILE(4, 64);
-    case 5: return QSIM_TILE(5, 64);
-    case 6: return QSIM_TILE(6, 64);
-    case 7: return QSIM_TILE(7, 64);
-    case 8: return QSIM_TILE(8, 64);
-    case 9: return QSIM_TILE(9, 128);
-    case 10: return threads == 512 ? QSIM_TILE(10, 512) : QSIM_TILE(10, 256);
-    case 11: return threads == 512 ? QSIM_TILE(11, 512) : QSIM_TILE(11, 256);
-    case 12:
-        if (threads == 256) return QSIM_TILE(12, 256);
-        if (threads == 1024) return QSIM_TILE(12, 1024);
-        return QSIM_TILE(12, 512);
-    case 13:
-        // default: the shape with 64 KiB tiles runs 512 threads and two workgroups per CU (fp32); 128 KiB tiles take 1024
-        if (threads == 512 || (threads == 0 && kAmpShift == 3)) return QSIM_TILE(13, 512);
-        return QSIM_TILE(13, 1024);
-#if QSIM_AMP_SHIFT == 3
-    // unreachable (QSIM_OPT_TILE_BITS stops at 13: the op header packs only kLaneNibbles free tile bits), but without this instantiation
-    // the compiler lays out the setup of f32 k_tile<13, 512> differently and the fp32 step is 1.2 % slower (DESIGN §3)
-    case 14: return QSIM_TILE(14, 1024);
-#endif
-    default: return hipErrorInvalidValue;
-    }
-#undef QSIM_TILE
-}
-
-hipError_t launch_norm2(const LaunchCfg &cfg, const void *v, int n, double *d_out) {
-    const uint64_t N = 1ULL << n;
-    uint64_t blocks = ceil_div(N, (uint64_t)TPB * 8);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(k_norm2, dim3((unsigned)blocks), dim3(TPB), 0, cfg.stream, (const amp_t *)v, N, d_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_block_prob(const LaunchCfg &cfg, const void *v, int n, int block_bits, double *d_out) {
-    const uint64_t N = 1ULL << n;
-    const uint64_t nblocks = (N + (1ULL << block_bits) - 1) >> block_bits;
-    uint64_t grid = nblocks > 65536 ? 65536 : nblocks;
-    hipLaunchKernelGGL(k_block_prob, dim3((unsigned)grid), dim3(TPB), 0, cfg.stream, (const amp_t *)v, N, block_bits, d_out,
-                       nblocks);
-    return hipGetLastError();
-}
-
-hipError_t launch_block_prob_masked(const LaunchCfg &cfg, const void *v, uint64_t hi_mask, uint64_t lo_mask, double *d_out) {
-    const int lo_bits = __builtin_popcountll(lo_mask);
-    const uint64_t nblocks = 1ULL << __builtin_popcountll(hi_mask);
-    const uint64_t grid = nblocks > 65536 ? 65536 : nblocks;
-    hipLaunchKernelGGL(k_block_prob_masked, dim3((unsigned)grid), dim3(TPB), 0, cfg.stream, (const amp_t *)v, hi_mask, lo_mask, lo_bits, d_out, nblocks);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather_masked(const LaunchCfg &cfg, const void *v, uint64_t base, uint64_t lo_mask, void *d_out) {
-    const uint64_t count = 1ULL << __builtin_popcountll(lo_mask);
-    uint64_t grid = ceil_div(count, TPB);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(k_gather_masked, dim3((unsigned)grid), dim3(TPB), 0, cfg.stream, (const amp_t *)v, base, lo_mask, count, (amp_t *)d_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_pack(const LaunchCfg &cfg, const void *in, void *out, void *const *blocks, int n, const int *bits, int p, uint32_t skip, uint64_t zero_mask) {
-    uint64_t sel = 0;
-    for (int j = 0; j < p; j++) sel |= 1ULL << bits[j];
-    const uint64_t N = 1ULL << n;
-    const uint64_t nt = ceil_div(N, (uint64_t)TPB * 4);
-    unsigned grid = grid_for(cfg, nt);
-    if (grid > 8192) grid = 8192; // persistent: the per-thread PEXT above is paid once per 2^10 * (nt / grid) amplitudes
-    PackDst d{};
-    if (blocks) {
-        if (p > 3) return hipErrorInvalidValue;
-        for (int b = 0; b < (1 << p); b++) d.blk[b] = (amp_t *)blocks[b];
-        hipLaunchKernelGGL((k_pack<4, true>), dim3(grid), dim3(TPB), 0, cfg.stream, (const amp_t *)in, (amp_t *)nullptr, d, N, n, p, sel, nt, skip, zero_mask);
-    } else {
-        if (p > 5) skip = 0; // the mask has 32 bits
-        hipLaunchKernelGGL((k_pack<4, false>), dim3(grid), dim3(TPB), 0, cfg.stream, (const amp_t *)in, (amp_t *)out, d, N, n, p, sel, nt, skip, zero_mask);
-    }
-    return hipGetLastError();
 }

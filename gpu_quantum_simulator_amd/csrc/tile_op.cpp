@@ -1,5 +1,5 @@
 // tile_op.cpp — the TileOp encoder: a scheduled TileBlock as the record k_tile reads through scalar loads (layout:
-// qsim_internal.h TileOp).  Host code with a bit-exact contract with kernels_impl.inc: the LDS offsets it stores are passed
+// qsim_internal.h TileOp).  Host code with a bit-exact contract with tile_kernel.inc: the LDS offsets it stores are passed
 // through the same swizzle (lds_sw_fold) and its header is decoded by part_geometry / part_prepare.
 #include <algorithm>
 #include <cstring>
@@ -54,7 +54,7 @@ template <int S> static int lane_score(const uint32_t v[5]) {
     return writes ? 2 : 1;
 }
 
-// Which free tile-local bit each bit of a lane's group index walks (kernels_impl.inc part_geometry).  Any assignment enumerates the
+// Which free tile-local bit each bit of a lane's group index walks (tile_kernel.inc part_geometry).  Any assignment enumerates the
 // groups; this one is chosen so that the lanes that share an LDS cycle fall on different banks.  The layout swizzle makes that true
 // for holes-free low bits; a block's qubits punch holes, and the ascending assignment then collides for many hole patterns (24 % of
 // the LDS-active cycles of the bench schedule were bank conflicts).  The five lowest lane bits get the first 5-tuple of distinct free
@@ -235,7 +235,7 @@ bool to_tile_op(const TileGeom &g, const TileBlock &blk, TileOp &t, bool f32) {
         }
     if (skips) t.flags |= kOpFlagSkips;
     if (closed) t.flags |= kOpFlagClosed;
-    // what the kernel branches on, in the bit positions of kernels_impl.inc PartPlan::info
+    // what the kernel branches on, in the bit positions of tile_kernel.inc PartPlan::info
     const uint32_t log2T = T == 4 ? 2 : T == 2 ? 1 : 0;
     t.b[7] = (uint8_t)((log2T << kInfoLog2TShift) | (skips ? kInfoSkips : 0u) | (K > 3 && !closed ? kInfoBarrier : 0u));
     return true;

@@ -141,7 +141,7 @@ def test_fp32_states(monkeypatch, n, opts):
 
 
 def _threads(opts, precision=64):
-    """Threads per workgroup launch_tile picks for a geometry (kernels_impl.inc launch_tile)."""
+    """Threads per workgroup launch_tile picks for a geometry (launch.inc tile_threads)."""
     b = opts.get("tile_bits", 12)
     if opts.get("tile_threads"):
         return opts["tile_threads"]
