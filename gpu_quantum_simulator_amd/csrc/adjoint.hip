@@ -1,7 +1,7 @@
 // adjoint.hip — adjoint-mode gradients of <H> for circuits of Pauli rotations (gfx950): the fused backward sweep k_pauli_adjoint and
 // the out-of-place lambda = H psi, k_pauli_sum.  Its own object, like expect.hip and evolve.hip: nothing here is compiled into
-// kernels.hip.  pauli_sweep.h says how a sweep walks a state (units, bit insertion, parity split, fp32 corners, grids); DESIGN §7d
-// has the derivation.
+// kernels.hip.  pauli_sweep.h says how a sweep walks a state (units, bit insertion, parity split, fp32 corners, grids) and has the term
+// record and the device helpers the sweeps share; DESIGN §7d has the derivation.
 //
 // Backward sweep.  With |lambda_k> = U_(k+1)^+ ... U_K^+ H |psi_K>, dE/dtheta_k = Im <lambda_k|P_k|psi_k>, and with a = psi_j,
 // b = psi_(j^x), la = lambda_j, lb = lambda_(j^x), s(j) = (-1)^popcount(j & z), ny = popcount(x & z):
@@ -21,33 +21,14 @@
 namespace qsim {
 namespace {
 
-template <typename R, int KT>
-struct AdjTerms {       // by value: scalar loads
-    uint64_t z[KT];     // unused slots: 0
-    R c[KT], v[KT];     // of -theta: rounded once to the state's precision by the host
-    uint32_t odd;       // bit k: ny is odd — w = v is real, and the term sums the real part of its bracket; else w = i v, imaginary part
-    int32_t count;
-};
-static_assert(sizeof(AdjTerms<double, kMaxPauliTermsPerSweep>) <= 1024, "term records stay well inside the 4 KiB of kernel arguments");
-
 template <typename R, bool PAIRED, int KT>
-__global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeom g, AdjTerms<R, KT> terms, double *__restrict__ partial) {
+__global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeom g, RotTerms<R, KT> terms, double *__restrict__ partial) {
     using V = typename Vec16<R>::type;
     constexpr int A = sizeof(R) == 8 ? 1 : 2;       // amplitudes per unit
     constexpr int AS = A - 1;
     constexpr int U = adjoint_units_per_trip(PAIRED);
     const uint32_t tid = threadIdx.x;
     const bool two_units = PAIRED && g.odd_slot;    // the partner sits in a unit of its own (else: in the odd slot of a's unit)
-    auto load = [&](const R *p, uint64_t amp) -> V {
-        if constexpr (A == 2) if (g.amps < 2) { // a register of one fp32 amplitude is 8 bytes long
-            const float2 one = *reinterpret_cast<const float2 *>(p);
-            V v{};
-            v.x = one.x;
-            v.y = one.y;
-            return v;
-        }
-        return load_unit(p, amp);
-    };
     auto store = [&](R *p, uint64_t amp, const V &v) {
         if constexpr (A == 2) if (g.amps < 2) {
             *reinterpret_cast<float2 *>(p) = float2{v.x, v.y};
@@ -76,8 +57,8 @@ __global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeo
             V va{}, vb{}, wa{}, wb{};
             if (t < g.units) {
                 const uint64_t j = expand<R>(g, t);
-                va = load(psi, j);
-                wa = load(lam, j);
+                va = load_unit_or_one(g, psi, j);
+                wa = load_unit_or_one(g, lam, j);
                 if (two_units) {
                     vb = load_unit(psi, (j ^ g.x) & ~(uint64_t)AS);
                     wb = load_unit(lam, (j ^ g.x) & ~(uint64_t)AS);
@@ -105,11 +86,11 @@ __global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeo
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint64_t ju = expand<R>(g, (q0 + u) << kTidBits); // uniform part of the amplitude index
-                const uint32_t sg = (((uint32_t)__builtin_popcountll(ju & z) & 1u) << 31) ^ mine;
+                const uint32_t sg = parity_sign(ju, z) ^ mine;
 #pragma unroll
                 for (int s = 0; s < A; s++) {
                     if (s >= slots) continue;
-                    const uint32_t sgs = s ? sg ^ ((uint32_t)(z & 1ULL) << 31) : sg;
+                    const uint32_t sgs = s ? odd_slot_sign(sg, z) : sg;
                     // every product of two floats is exact in fp64
                     const double pr = ar[u][s], pi = ai[u][s], mr = lar[u][s], mi = lai[u][s];
                     double t;
@@ -136,23 +117,13 @@ __global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeo
         for (int u = 0; u < U; u++) {
             const uint64_t t = ((q0 + u) << kTidBits) | tid;
             if (t >= g.units) continue;
-            const uint64_t j = expand<R>(g, t);
-            if constexpr (A == 1) {
-                store(psi, j, V{ar[u][0], ai[u][0]});
-                store(lam, j, V{lar[u][0], lai[u][0]});
-                if (two_units) {
-                    store(psi, j ^ g.x, V{br[u][0], bi[u][0]});
-                    store(lam, j ^ g.x, V{lbr[u][0], lbi[u][0]});
-                }
-            } else { // selects on values, so that every store stays one 16-byte store
-                const bool same = PAIRED && !g.odd_slot, swapped = (g.x & 1) != 0;
-                store(psi, j, V{ar[u][0], ai[u][0], same ? br[u][0] : ar[u][1], same ? bi[u][0] : ai[u][1]});
-                store(lam, j, V{lar[u][0], lai[u][0], same ? lbr[u][0] : lar[u][1], same ? lbi[u][0] : lai[u][1]});
-                if (two_units) {
-                    const uint64_t p = (j ^ g.x) & ~(uint64_t)AS;
-                    store(psi, p, V{swapped ? br[u][1] : br[u][0], swapped ? bi[u][1] : bi[u][0], swapped ? br[u][0] : br[u][1], swapped ? bi[u][0] : bi[u][1]});
-                    store(lam, p, V{swapped ? lbr[u][1] : lbr[u][0], swapped ? lbi[u][1] : lbi[u][0], swapped ? lbr[u][0] : lbr[u][1], swapped ? lbi[u][0] : lbi[u][1]});
-                }
+            const uint64_t j = expand<R>(g, t), p = (j ^ g.x) & ~(uint64_t)AS;
+            const bool same = PAIRED && !g.odd_slot, swapped = (g.x & 1) != 0;
+            store(psi, j, own_unit(same, ar[u], ai[u], br[u], bi[u]));
+            store(lam, j, own_unit(same, lar[u], lai[u], lbr[u], lbi[u]));
+            if (two_units) {
+                store(psi, p, partner_unit(swapped, br[u], bi[u]));
+                store(lam, p, partner_unit(swapped, lbr[u], lbi[u]));
             }
         }
     }
@@ -175,42 +146,18 @@ __global__ __launch_bounds__(kTPB) void k_pauli_adjoint(R *psi, R *lam, SweepGeo
 
 template <typename R, bool PAIRED, int KT>
 hipError_t launch_kt(hipStream_t stream, void *psi, void *lam, const SweepGeom &g, const RotSweep &sw, double *d_partial, double *d_out) {
-    AdjTerms<R, KT> rec{};
-    for (int k = 0; k < sw.count && k < KT; k++) {
-        rec.z[k] = sw.z[k];
-        rec.c[k] = (R)sw.c[k];
-        rec.v[k] = (R)sw.v[k];
-    }
-    rec.odd = sw.odd_mask;
-    rec.count = sw.count;
-    constexpr uint64_t per_block = (uint64_t)kTPB * adjoint_units_per_trip(PAIRED);
-    // the expectation sweep's rule: resident at once, at most the rows of d_partial, whatever LaunchCfg::grid_cap says
-    const int resident = resident_grid<k_pauli_adjoint<R, PAIRED, KT>>();
-    const uint64_t cap = resident > 0 && resident < kExpectGrid ? resident : kExpectGrid;
-    uint64_t grid = (g.units + per_block - 1) / per_block;
-    if (grid > cap) grid = cap;
-    if (grid == 0) grid = 1;
-    hipLaunchKernelGGL((k_pauli_adjoint<R, PAIRED, KT>), dim3((unsigned)grid), dim3(kTPB), 0, stream, (R *)psi, (R *)lam, g, rec, d_partial);
+    RotTerms<R, KT> rec{};
+    fill_terms(rec, sw);
+    const unsigned grid = reducing_grid<k_pauli_adjoint<R, PAIRED, KT>>(g.units, (uint64_t)kTPB * adjoint_units_per_trip(PAIRED));
+    hipLaunchKernelGGL((k_pauli_adjoint<R, PAIRED, KT>), dim3(grid), dim3(kTPB), 0, stream, (R *)psi, (R *)lam, g, rec, d_partial);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_expect_final(stream, d_partial, (int)grid, KT, d_out);
 }
 
-template <typename R, bool PAIRED>
-hipError_t launch_prec(hipStream_t stream, void *psi, void *lam, const SweepGeom &g, const RotSweep &sw, double *d_partial, double *d_out) {
-    switch (expect_slots(sw.count)) {
-    case 1: return launch_kt<R, PAIRED, 1>(stream, psi, lam, g, sw, d_partial, d_out);
-    case 8: return launch_kt<R, PAIRED, 8>(stream, psi, lam, g, sw, d_partial, d_out);
-    case 16: return launch_kt<R, PAIRED, 16>(stream, psi, lam, g, sw, d_partial, d_out);
-    case 32: return launch_kt<R, PAIRED, 32>(stream, psi, lam, g, sw, d_partial, d_out);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 // ---- lambda = H psi ---------------------------------------------------------------------------------------------------------------
 constexpr int KS = kMaxPauliTermsPerSweep;
 constexpr int kSumUnits = 4; // units per thread and trip: 4 loads of the source in flight, and 4 of the destination when it accumulates
-static_assert(KS <= 32, "one bit per term in SumTerms::odd and in a thread's parity mask");
 
 template <typename R>
 struct SumTerms {       // by value: scalar loads
@@ -229,16 +176,6 @@ __global__ __launch_bounds__(kTPB) void k_pauli_sum(const R *__restrict__ src, R
     constexpr int U = kSumUnits;
     const uint32_t tid = threadIdx.x;
     const bool tiny = A == 2 && g.amps < 2; // a register of one fp32 amplitude is 8 bytes long
-    auto load = [&](const R *p, uint64_t amp) -> V {
-        if constexpr (A == 2) if (tiny) {
-            const float2 one = *reinterpret_cast<const float2 *>(p);
-            V v{};
-            v.x = one.x;
-            v.y = one.y;
-            return v;
-        }
-        return load_unit(p, amp);
-    };
 
     const uint64_t il = expand<R>(g, tid);
     uint32_t own = 0;
@@ -253,8 +190,8 @@ __global__ __launch_bounds__(kTPB) void k_pauli_sum(const R *__restrict__ src, R
             vd[u] = V{};
             if (t < g.units) {
                 const uint64_t i = expand<R>(g, t);
-                vs[u] = load(src, (i ^ g.x) & ~(uint64_t)AS);
-                if (accumulate) vd[u] = load(dst, i);
+                vs[u] = load_unit_or_one(g, src, (i ^ g.x) & ~(uint64_t)AS);
+                if (accumulate) vd[u] = load_unit_or_one(g, dst, i);
             }
         }
         R wr[U][A], wi[U][A]; // the weight of output slot s of unit u
@@ -270,10 +207,10 @@ __global__ __launch_bounds__(kTPB) void k_pauli_sum(const R *__restrict__ src, R
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint64_t iu = expand<R>(g, (q0 + u) << kTidBits); // uniform part of the output index
-                const uint32_t sg = (((uint32_t)__builtin_popcountll(iu & z) & 1u) << 31) ^ mine;
+                const uint32_t sg = parity_sign(iu, z) ^ mine;
 #pragma unroll
                 for (int s = 0; s < A; s++) {
-                    const R f = flip(c, s ? sg ^ ((uint32_t)(z & 1ULL) << 31) : sg);
+                    const R f = flip(c, s ? odd_slot_sign(sg, z) : sg);
                     if (odd) wi[u][s] += f;
                     else wr[u][s] += f;
                 }
@@ -303,20 +240,9 @@ __global__ __launch_bounds__(kTPB) void k_pauli_sum(const R *__restrict__ src, R
 template <typename R>
 hipError_t launch_sum_prec(const LaunchCfg &cfg, const void *src, void *dst, const SweepGeom &g, const SumSweep &sw) {
     SumTerms<R> rec{};
-    for (int k = 0; k < sw.count; k++) {
-        rec.z[k] = sw.z[k];
-        rec.c[k] = (R)sw.c[k];
-    }
-    rec.odd = sw.odd_mask;
-    rec.count = sw.count;
-    constexpr uint64_t per_block = (uint64_t)kTPB * kSumUnits;
-    uint64_t grid = (g.units + per_block - 1) / per_block;
-    // the rotation sweep's rule: every output is written by one thread, so QSIM_OPT_GRID_CAP applies as for every kernel
-    const int resident = resident_grid<k_pauli_sum<R>>();
-    const uint64_t cap = cfg.grid_cap > 0 ? (uint64_t)cfg.grid_cap : resident > 0 ? (uint64_t)resident : 1024;
-    if (grid > cap) grid = cap;
-    if (grid == 0) grid = 1;
-    hipLaunchKernelGGL((k_pauli_sum<R>), dim3((unsigned)grid), dim3(kTPB), 0, cfg.stream, (const R *)src, (R *)dst, g, rec, sw.accumulate ? 1 : 0);
+    fill_terms(rec, sw);
+    const unsigned grid = writing_grid<k_pauli_sum<R>>(cfg, g.units, (uint64_t)kTPB * kSumUnits);
+    hipLaunchKernelGGL((k_pauli_sum<R>), dim3(grid), dim3(kTPB), 0, cfg.stream, (const R *)src, (R *)dst, g, rec, sw.accumulate ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -326,8 +252,11 @@ hipError_t launch_pauli_adjoint(const LaunchCfg &cfg, void *psi, void *lam, bool
     if (!check_sweep(sw, n) || sw.full || !psi || !lam || psi == lam || !d_partial || !d_out) return hipErrorInvalidValue;
     const bool paired = sw.x != 0;
     const SweepGeom g = sweep_geom(sw.x, false, f32, n);
-    if (f32) return paired ? launch_prec<float, true>(cfg.stream, psi, lam, g, sw, d_partial, d_out) : launch_prec<float, false>(cfg.stream, psi, lam, g, sw, d_partial, d_out);
-    return paired ? launch_prec<double, true>(cfg.stream, psi, lam, g, sw, d_partial, d_out) : launch_prec<double, false>(cfg.stream, psi, lam, g, sw, d_partial, d_out);
+    return for_precision_and_pairing(f32, paired, [&](auto r, auto p) {
+        return for_term_slots(sw.count, [&](auto kt) {
+            return launch_kt<decltype(r), decltype(p)::value, decltype(kt)::value>(cfg.stream, psi, lam, g, sw, d_partial, d_out);
+        });
+    });
 }
 
 hipError_t launch_pauli_sum(const LaunchCfg &cfg, const void *src, void *dst, bool f32, int n, const SumSweep &sw) {

@@ -544,19 +544,15 @@ extern "C" int qsim_cluster_norm2(qsim_cluster *c, double *out) {
     return QSIM_OK;
 }
 
-// What the two Pauli entry points open with: the argument checks (`third`: the results or the angles; `thetas`: the angles, where
-// there are any), every mask mapped from logical qubits through `pos` into X and Z, and the refusal to pair shards across devices.
+// What the two Pauli entry points open with: the argument checks of every Pauli entry point (`third`: the results or the angles;
+// `thetas`: the angles, where there are any), then every mask mapped from logical qubits through `pos` into X and Z, and the refusal
+// to pair shards across devices.
 static int physical_terms(qsim_cluster *c, const char *who, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *thetas,
                           long num_terms, std::vector<uint64_t> &X, std::vector<uint64_t> &Z) {
     if (!c) return cfail(QSIM_ERR_ARG, "NULL cluster");
-    if (num_terms < 0) return cfail(QSIM_ERR_ARG, "%s: negative term count", who);
-    if (num_terms == 0) return QSIM_OK;
-    if (!x_masks || !z_masks || !third) return cfail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    const uint64_t nmask = qsim::index_mask(c->n);
+    if (const int rc = qsim::check_pauli_terms(cfail, who, c->n, x_masks, z_masks, third, thetas, num_terms)) return rc;
     X.resize((size_t)num_terms), Z.resize((size_t)num_terms);
     for (long t = 0; t < num_terms; t++) {
-        if ((x_masks[t] | z_masks[t]) & ~nmask) return cfail(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, c->n);
-        if (thetas && !std::isfinite(thetas[t])) return cfail(QSIM_ERR_ARG, "%s: term %ld has a non-finite angle", who, t);
         X[(size_t)t] = physical_index(c, x_masks[t]);
         Z[(size_t)t] = physical_index(c, z_masks[t]);
         if ((X[(size_t)t] >> c->m) != 0 && !c->same_device)

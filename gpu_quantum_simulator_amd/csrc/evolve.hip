@@ -1,7 +1,7 @@
 // evolve.hip — Pauli-string rotations exp(-i theta/2 P) as in-place sweeps (gfx950).  Its own object, like expect.hip: nothing
 // here is compiled into kernels.hip, whose code layout is part of the measured product.  pauli_sweep.h says how a
-// sweep walks a state (units, bit insertion, parity split, fp32 corners, grids) and has the 2x2 itself (rotate_pair, rotate_diag:
-// the adjoint sweep applies it too); this file has the rule and the stores.
+// sweep walks a state (units, bit insertion, parity split, fp32 corners, grids) and has the term record, the 2x2 itself (rotate_pair,
+// rotate_diag) and the packing for the stores, which the adjoint sweep uses too; this file has the rule and the kernel.
 //
 // P maps every index pair {j, j ^ x} to itself, so the rotation is a 2x2 on each pair whatever the string's weight.  With
 // s(j) = (-1)^popcount(j & z), ny = popcount(x & z), c = cos(theta/2) and w = -i sin(theta/2) i^ny:
@@ -20,19 +20,9 @@ namespace qsim {
 namespace {
 
 constexpr int KT = kMaxPauliTermsPerSweep;
-static_assert(KT <= 32, "one bit per term in RotTerms::odd and in a thread's parity mask");
-
-template <typename R>
-struct RotTerms {       // by value: scalar loads
-    uint64_t z[KT];
-    R c[KT], v[KT];     // rounded once to the state's precision by the host
-    uint32_t odd;       // bit k: ny is odd — w = v is real and a's sign is opposite to b's; else w = i v
-    int32_t count;
-};
-static_assert(sizeof(RotTerms<double>) <= 1024, "term records stay well inside the 4 KiB of kernel arguments");
 
 template <typename R, bool PAIRED>
-__global__ __launch_bounds__(kTPB) void k_pauli_rot(R *a, R *b, SweepGeom g, RotTerms<R> terms) { // a and b may be one buffer
+__global__ __launch_bounds__(kTPB) void k_pauli_rot(R *a, R *b, SweepGeom g, RotTerms<R, KT> terms) { // a and b may be one buffer
     using V = typename Vec16<R>::type;
     constexpr int A = sizeof(R) == 8 ? 1 : 2;       // amplitudes per unit
     constexpr int AS = A - 1;
@@ -89,11 +79,11 @@ __global__ __launch_bounds__(kTPB) void k_pauli_rot(R *a, R *b, SweepGeom g, Rot
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint64_t ju = expand<R>(g, (q0 + u) << kTidBits); // uniform part of the amplitude index
-                const uint32_t sg = (((uint32_t)__builtin_popcountll(ju & z) & 1u) << 31) ^ mine;
+                const uint32_t sg = parity_sign(ju, z) ^ mine;
 #pragma unroll
                 for (int s = 0; s < A; s++) {
                     if (s >= slots) continue;
-                    const R sv = flip(v, s ? sg ^ ((uint32_t)(z & 1ULL) << 31) : sg);
+                    const R sv = flip(v, s ? odd_slot_sign(sg, z) : sg);
                     if (PAIRED) rotate_pair(ar[u][s], ai[u][s], br[u][s], bi[u][s], c, sv, odd);
                     else rotate_diag(ar[u][s], ai[u][s], c, sv);
                 }
@@ -104,38 +94,18 @@ __global__ __launch_bounds__(kTPB) void k_pauli_rot(R *a, R *b, SweepGeom g, Rot
             const uint64_t t = ((q0 + u) << kTidBits) | tid;
             if (t >= g.units) continue;
             const uint64_t j = expand<R>(g, t);
-            if constexpr (A == 1) {
-                store(a, j, V{ar[u][0], ai[u][0]});
-                if (two_units) store(b, j ^ g.x, V{br[u][0], bi[u][0]});
-            } else { // selects on values, so that every store stays one 16-byte store
-                const bool same = PAIRED && !g.odd_slot, swapped = (g.x & 1) != 0;
-                store(a, j, V{ar[u][0], ai[u][0], same ? br[u][0] : ar[u][1], same ? bi[u][0] : ai[u][1]});
-                if (two_units)
-                    store(b, (j ^ g.x) & ~(uint64_t)AS,
-                          V{swapped ? br[u][1] : br[u][0], swapped ? bi[u][1] : bi[u][0], swapped ? br[u][0] : br[u][1], swapped ? bi[u][0] : bi[u][1]});
-            }
+            store(a, j, own_unit(PAIRED && !g.odd_slot, ar[u], ai[u], br[u], bi[u]));
+            if (two_units) store(b, (j ^ g.x) & ~(uint64_t)AS, partner_unit((g.x & 1) != 0, br[u], bi[u]));
         }
     }
 }
 
 template <typename R, bool PAIRED>
 hipError_t launch_prec(const LaunchCfg &cfg, void *a, void *b, const SweepGeom &g, const RotSweep &sw) {
-    RotTerms<R> rec{};
-    for (int k = 0; k < sw.count; k++) {
-        rec.z[k] = sw.z[k];
-        rec.c[k] = (R)sw.c[k];
-        rec.v[k] = (R)sw.v[k];
-    }
-    rec.odd = sw.odd_mask;
-    rec.count = sw.count;
-    constexpr uint64_t per_block = (uint64_t)kTPB * units_per_trip(PAIRED);
-    uint64_t grid = (g.units + per_block - 1) / per_block;
-    // QSIM_OPT_GRID_CAP > 0 caps the grid as it does for every kernel (a huge cap: one workgroup per block of units)
-    const int resident = resident_grid<k_pauli_rot<R, PAIRED>>();
-    const uint64_t cap = cfg.grid_cap > 0 ? (uint64_t)cfg.grid_cap : resident > 0 ? (uint64_t)resident : 1024;
-    if (grid > cap) grid = cap;
-    if (grid == 0) grid = 1;
-    hipLaunchKernelGGL((k_pauli_rot<R, PAIRED>), dim3((unsigned)grid), dim3(kTPB), 0, cfg.stream, (R *)a, (R *)b, g, rec);
+    RotTerms<R, KT> rec{};
+    fill_terms(rec, sw);
+    const unsigned grid = writing_grid<k_pauli_rot<R, PAIRED>>(cfg, g.units, (uint64_t)kTPB * units_per_trip(PAIRED));
+    hipLaunchKernelGGL((k_pauli_rot<R, PAIRED>), dim3(grid), dim3(kTPB), 0, cfg.stream, (R *)a, (R *)b, g, rec);
     return hipGetLastError();
 }
 
@@ -146,8 +116,7 @@ hipError_t launch_pauli_rot(const LaunchCfg &cfg, void *a, void *b, bool f32, in
     if (sw.full == (a == b)) return hipErrorInvalidValue; // every index counts exactly when the partner is another buffer
     const bool paired = sw.x != 0 || sw.full;
     const SweepGeom g = sweep_geom(sw.x, sw.full, f32, n);
-    if (f32) return paired ? launch_prec<float, true>(cfg, a, b, g, sw) : launch_prec<float, false>(cfg, a, b, g, sw);
-    return paired ? launch_prec<double, true>(cfg, a, b, g, sw) : launch_prec<double, false>(cfg, a, b, g, sw);
+    return for_precision_and_pairing(f32, paired, [&](auto r, auto p) { return launch_prec<decltype(r), decltype(p)::value>(cfg, a, b, g, sw); });
 }
 
 } // namespace qsim

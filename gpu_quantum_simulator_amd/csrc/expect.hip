@@ -32,16 +32,6 @@ __global__ __launch_bounds__(kTPB) void k_expect(const R *__restrict__ a, const 
     constexpr int AS = A - 1;
     constexpr int U = units_per_trip(PAIRED);
     const uint32_t tid = threadIdx.x;
-    auto load = [&](const R *p, uint64_t amp) -> V {
-        if constexpr (A == 2) if (g.amps < 2) { // a register of one fp32 amplitude is 8 bytes long
-            const float2 one = *reinterpret_cast<const float2 *>(p);
-            V v{};
-            v.x = one.x;
-            v.y = one.y;
-            return v;
-        }
-        return load_unit(p, amp);
-    };
 
     double acc[KT];
 #pragma unroll
@@ -56,8 +46,8 @@ __global__ __launch_bounds__(kTPB) void k_expect(const R *__restrict__ a, const 
             vb[u] = V{};
             if (t < g.units) {
                 const uint64_t j = expand<R>(g, t);
-                va[u] = load(a, j);
-                if (PAIRED) vb[u] = load(b, (j ^ g.x) & ~(uint64_t)AS);
+                va[u] = load_unit_or_one(g, a, j);
+                if (PAIRED) vb[u] = load_unit_or_one(g, b, (j ^ g.x) & ~(uint64_t)AS);
             }
         }
 #pragma unroll
@@ -93,12 +83,12 @@ __global__ __launch_bounds__(kTPB) void k_expect(const R *__restrict__ a, const 
 #pragma unroll
             for (int k = 0; k < KT; k++) {
                 const uint64_t z = terms.z[k];
-                const uint32_t sg = ((uint32_t)__builtin_popcountll(ju & z) & 1u) << 31; // scalar
+                const uint32_t sg = parity_sign(ju, z); // scalar
                 const bool use_im = PAIRED && ((terms.im >> k) & 1u);
 #pragma unroll
                 for (int s = 0; s < A; s++) {
                     const double v = use_im ? im[s] : re[s];
-                    acc[k] += flip(v, s ? sg ^ ((uint32_t)(z & 1ULL) << 31) : sg);
+                    acc[k] += flip(v, s ? odd_slot_sign(sg, z) : sg);
                 }
             }
         }
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(kTPB) void k_expect(const R *__restrict__ a, const 
     __shared__ double part[kTPB / 64][KT];
 #pragma unroll
     for (int k = 0; k < KT; k++) {
-        double v = flip(acc[k], ((uint32_t)__builtin_popcountll(jl & terms.z[k]) & 1u) << 31);
+        double v = flip(acc[k], parity_sign(jl, terms.z[k]));
         for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
         if ((tid & 63) == 0) part[tid >> 6][k] = v;
     }
@@ -127,28 +117,11 @@ hipError_t launch_kt(hipStream_t stream, const void *a, const void *b, const Swe
     TermRec<KT> rec{};
     for (int k = 0; k < sw.count && k < KT; k++) rec.z[k] = sw.z[k];
     rec.im = sw.im_mask;
-    constexpr uint64_t per_block = (uint64_t)kTPB * units_per_trip(PAIRED);
-    // resident at once (the 32-slot instantiations hold 3 workgroups per CU, the others 4 and more), at most the rows of d_partial
-    const int resident = resident_grid<k_expect<R, PAIRED, KT>>();
-    const uint64_t cap = resident > 0 && resident < kExpectGrid ? resident : kExpectGrid;
-    uint64_t grid = (g.units + per_block - 1) / per_block;
-    if (grid > cap) grid = cap;
-    if (grid == 0) grid = 1;
-    hipLaunchKernelGGL((k_expect<R, PAIRED, KT>), dim3((unsigned)grid), dim3(kTPB), 0, stream, (const R *)a, (const R *)b, g, rec, d_partial);
+    const unsigned grid = reducing_grid<k_expect<R, PAIRED, KT>>(g.units, (uint64_t)kTPB * units_per_trip(PAIRED));
+    hipLaunchKernelGGL((k_expect<R, PAIRED, KT>), dim3(grid), dim3(kTPB), 0, stream, (const R *)a, (const R *)b, g, rec, d_partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_expect_final(stream, d_partial, (int)grid, KT, d_out);
-}
-
-template <typename R, bool PAIRED>
-hipError_t launch_prec(hipStream_t stream, const void *a, const void *b, const SweepGeom &g, const ExpectSweep &sw, double *d_partial, double *d_out) {
-    switch (expect_slots(sw.count)) {
-    case 1: return launch_kt<R, PAIRED, 1>(stream, a, b, g, sw, d_partial, d_out);
-    case 8: return launch_kt<R, PAIRED, 8>(stream, a, b, g, sw, d_partial, d_out);
-    case 16: return launch_kt<R, PAIRED, 16>(stream, a, b, g, sw, d_partial, d_out);
-    case 32: return launch_kt<R, PAIRED, 32>(stream, a, b, g, sw, d_partial, d_out);
-    default: return hipErrorInvalidValue;
-    }
 }
 
 } // namespace
@@ -174,8 +147,11 @@ hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, boo
     if (!check_sweep(sw, n)) return hipErrorInvalidValue;
     const bool paired = sw.x != 0 || sw.full;
     const SweepGeom g = sweep_geom(sw.x, sw.full, f32, n);
-    if (f32) return paired ? launch_prec<float, true>(cfg.stream, a, b, g, sw, d_partial, d_out) : launch_prec<float, false>(cfg.stream, a, b, g, sw, d_partial, d_out);
-    return paired ? launch_prec<double, true>(cfg.stream, a, b, g, sw, d_partial, d_out) : launch_prec<double, false>(cfg.stream, a, b, g, sw, d_partial, d_out);
+    return for_precision_and_pairing(f32, paired, [&](auto r, auto p) {
+        return for_term_slots(sw.count, [&](auto kt) {
+            return launch_kt<decltype(r), decltype(p)::value, decltype(kt)::value>(cfg.stream, a, b, g, sw, d_partial, d_out);
+        });
+    });
 }
 
 } // namespace qsim

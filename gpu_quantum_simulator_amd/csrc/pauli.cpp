@@ -25,17 +25,51 @@ static double rotation_v(int ny, double sn) { return pauli_phase(ny + 3) * sn; }
 // Z on rank qubits (mask bits from m up): a sign per shard
 static double rank_sign(uint64_t rank, uint64_t z, int m) { return (__builtin_popcountll(rank & (z >> m)) & 1) ? -1.0 : 1.0; }
 
-// The argument checks of the two single-state entry points; `third` is the array that goes with the masks (results or angles),
-// `thetas` the numbers that must be finite where there are any: angles, or coefficients (`number` says which).
-static int check_terms(const char *who, const qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *thetas,
+// qsim_internal.h says what is checked; the single-state entry points call it through check_terms, the cluster's through physical_terms
+int qsim::check_pauli_terms(int (*report)(int, const char *, ...), const char *who, int n, const uint64_t *x_masks, const uint64_t *z_masks,
+                            const void *third, const double *numbers, long num_terms, const char *number) {
+    if (num_terms < 0) return report(QSIM_ERR_ARG, "%s: negative term count", who);
+    if (num_terms > 0 && (!x_masks || !z_masks || !third)) return report(QSIM_ERR_ARG, "%s: NULL argument", who);
+    const uint64_t nmask = index_mask(n);
+    for (long t = 0; t < num_terms; t++) {
+        if ((x_masks[t] | z_masks[t]) & ~nmask) return report(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, n);
+        if (numbers && !std::isfinite(numbers[t])) return report(QSIM_ERR_ARG, "%s: term %ld has a non-finite %s", who, t, number);
+    }
+    return QSIM_OK;
+}
+static int check_terms(const char *who, const qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const void *third, const double *numbers,
                        long num_terms, const char *number = "angle") {
     if (!s) return fail(QSIM_ERR_ARG, "NULL state");
-    if (num_terms < 0) return fail(QSIM_ERR_ARG, "%s: negative term count", who);
-    if (num_terms > 0 && (!x_masks || !z_masks || !third)) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    const uint64_t nmask = index_mask(s->n);
-    for (long t = 0; t < num_terms; t++) {
-        if ((x_masks[t] | z_masks[t]) & ~nmask) return fail(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, s->n);
-        if (thetas && !std::isfinite(thetas[t])) return fail(QSIM_ERR_ARG, "%s: term %ld has a non-finite %s", who, t, number);
+    return check_pauli_terms(fail, who, s->n, x_masks, z_masks, third, numbers, num_terms, number);
+}
+// What a launcher of pauli_sweep.h returned, as the call's result: `sweep` names it in the message
+static int launched(const char *sweep, hipError_t e) {
+    if (e == hipSuccess) return QSIM_OK;
+    return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s sweep launch failed: %s", sweep, hipGetErrorString(e));
+}
+
+// ---- result rows ------------------------------------------------------------------------------------------------------------------
+// What reducing sweeps leave their sums in: s->d_expect, allocated on first use, is the partial sums of the sweep that runs
+// (kExpectPartialDoubles) and behind them kRowBatch rows of kRowSlots results, one row per sweep, so that the results of up to
+// kRowBatch sweeps travel in one copy behind one synchronisation.
+static constexpr int kRowBatch = 128;
+static constexpr int kRowSlots = kMaxPauliTermsPerSweep;
+static int alloc_result_rows(qsim_state *s) {
+    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kRowBatch * kRowSlots) * sizeof(double)));
+    return QSIM_OK;
+}
+// launch(r, d_row) queues the sweep of row r < rows on the state's stream; scatter(r, row) gets its kRowSlots sums on the host.
+// Batch after batch in order of r; what a row means is the caller's.
+template <typename Launch, typename Scatter>
+static int sweep_result_rows(qsim_state *s, size_t rows, Launch launch, Scatter scatter) {
+    double *d_rows = s->d_expect + kExpectPartialDoubles;
+    std::vector<double> host((size_t)kRowBatch * kRowSlots);
+    for (size_t first = 0; first < rows; first += kRowBatch) {
+        const size_t last = std::min(rows, first + (size_t)kRowBatch);
+        for (size_t r = first; r < last; r++) QSIM_TRY(launch(r, d_rows + (r - first) * kRowSlots));
+        HIP_TRY(hipMemcpyAsync(host.data(), d_rows, (last - first) * kRowSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (size_t r = first; r < last; r++) scatter(r, host.data() + (r - first) * kRowSlots);
     }
     return QSIM_OK;
 }
@@ -89,16 +123,12 @@ int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank,
         if ((X[t] >> m) != x_rank) return fail(QSIM_ERR_ARG, "expectation: terms of one shard call must pair the same shards");
     if ((x_rank != 0) != (partner != nullptr)) return fail(QSIM_ERR_ARG, "expectation: a partner buffer goes with x on rank qubits, and only with it");
     QSIM_TRY(settle(s));
-    constexpr int kBatch = 128; // sweeps whose results travel in one copy
-    constexpr int kSlots = kMaxPauliTermsPerSweep;
-    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kBatch * kSlots) * sizeof(double)));
-    double *d_results = s->d_expect + kExpectPartialDoubles;
+    QSIM_TRY(alloc_result_rows(s));
     const PauliSweeps plan = pauli_sweeps(X, mmask, num);
-    std::vector<double> host((size_t)kBatch * kSlots);
-    LaunchCfg cfg{s->stream, s->grid_cap};
-    for (size_t first = 0; first < plan.sweeps.size(); first += kBatch) {
-        const size_t last = std::min(plan.sweeps.size(), first + (size_t)kBatch);
-        for (size_t w = first; w < last; w++) {
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    return sweep_result_rows(
+        s, plan.sweeps.size(),
+        [&](size_t w, double *d_row) {
             ExpectSweep sw{};
             sw.x = X[plan.order[(size_t)plan.sweeps[w].first]] & mmask;
             sw.full = x_rank != 0;
@@ -108,18 +138,14 @@ int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank,
                 sw.z[k] = Z[t] & mmask;
                 if (__builtin_popcountll(X[t] & Z[t]) & 1) sw.im_mask |= 1u << k;
             }
-            HIP_TRY(launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, s->d_expect, d_results + (w - first) * kSlots));
-        }
-        HIP_TRY(hipMemcpyAsync(host.data(), d_results, (last - first) * kSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t w = first; w < last; w++)
+            return launched("expectation", launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, s->d_expect, d_row));
+        },
+        [&](size_t w, const double *row) {
             for (int k = 0; k < plan.sweeps[w].second; k++) {
                 const long t = plan.order[(size_t)(plan.sweeps[w].first + k)];
-                const double f = expect_factor(X[t], __builtin_popcountll(X[t] & Z[t])) * rank_sign(rank, Z[t], m);
-                out[t] = f * host[(w - first) * kSlots + (size_t)k];
+                out[t] = expect_factor(X[t], __builtin_popcountll(X[t] & Z[t])) * rank_sign(rank, Z[t], m) * row[k];
             }
-    }
-    return QSIM_OK;
+        });
 }
 
 extern "C" int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, double *out) {
@@ -165,6 +191,24 @@ void qsim::pauli_rot_1q(bool y, double theta, double *U) {
     std::copy(y ? uy : ux, (y ? uy : ux) + 8, U);
 }
 
+// `count` terms of one x as one sweep of the angles sign * theta (-1: the inverse, for the way back of a gradient) on the shard
+// `rank` of local mask `mmask` (m bits); x carries the rank bits too, ny counts them, the sweep's masks are the local part.
+static RotSweep rot_sweep(uint64_t x, const uint64_t *Z, const double *thetas, int count, double sign, uint64_t rank, uint64_t mmask, int m) {
+    RotSweep sw{};
+    sw.x = x & mmask;
+    sw.full = (x & ~mmask) != 0;
+    sw.count = count;
+    for (int k = 0; k < count; k++) {
+        const double half = sign * 0.5 * thetas[k];
+        const int ny = __builtin_popcountll(x & Z[k]);
+        sw.z[k] = Z[k] & mmask;
+        sw.c[k] = std::cos(half);
+        sw.v[k] = rotation_v(ny, std::sin(half)) * rank_sign(rank, Z[k], m);
+        if (ny & 1) sw.odd_mask |= 1u << k;
+    }
+    return sw;
+}
+
 int qsim::pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x, const uint64_t *Z, const double *thetas, long count) {
     if (!s || count < 0 || (count > 0 && (!Z || !thetas))) return fail(QSIM_ERR_ARG, "rotation: NULL argument or negative term count");
     const int m = s->n;
@@ -175,21 +219,8 @@ int qsim::pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x,
     HIP_TRY(hipSetDevice(s->device)); // a cluster drives several devices from one thread, and settle() may have had nothing to do
     const LaunchCfg cfg{s->stream, s->grid_cap};
     for (long first = 0; first < count; first += kPauliRotationsPerSweep) {
-        RotSweep sw{};
-        sw.x = x & mmask;
-        sw.full = partner != nullptr;
-        sw.count = (int)std::min<long>(kPauliRotationsPerSweep, count - first);
-        for (int k = 0; k < sw.count; k++) {
-            const uint64_t z = Z[first + k];
-            const double half = 0.5 * thetas[first + k];
-            const int ny = __builtin_popcountll(x & z);
-            sw.z[k] = z & mmask;
-            sw.c[k] = std::cos(half);
-            sw.v[k] = rotation_v(ny, std::sin(half)) * rank_sign(rank, z, m);
-            if (ny & 1) sw.odd_mask |= 1u << k;
-        }
-        const hipError_t e = launch_pauli_rot(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw);
-        if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "rotation sweep launch failed: %s", hipGetErrorString(e));
+        const RotSweep sw = rot_sweep(x, Z + first, thetas + first, (int)std::min<long>(kPauliRotationsPerSweep, count - first), 1.0, rank, mmask, m);
+        QSIM_TRY(launched("rotation", launch_pauli_rot(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw)));
         g_sweeps_launched++;
     }
     return QSIM_OK;
@@ -266,8 +297,7 @@ static int pauli_sum_sweeps(qsim_state *s, const uint64_t *X, const uint64_t *Z,
             sw.c[k] = C[t] * pauli_phase(ny) * ((ny & 1) ? -1.0 : 1.0); // (Q psi)_i = i^ny s(i ^ x) psi_(i^x), and s(i ^ x) = (-1)^ny s(i)
             if (ny & 1) sw.odd_mask |= 1u << k;
         }
-        const hipError_t e = launch_pauli_sum(cfg, s->amps, dst, s->f32, s->n, sw);
-        if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "Pauli sum sweep launch failed: %s", hipGetErrorString(e));
+        QSIM_TRY(launched("Pauli sum", launch_pauli_sum(cfg, s->amps, dst, s->f32, s->n, sw)));
     }
     return QSIM_OK;
 }
@@ -291,15 +321,12 @@ extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const u
     QSIM_TRY(await_buffer(s));
     HIP_TRY(hipSetDevice(s->device));
     // everything that can fail for want of memory comes before the state is touched
-    constexpr int kBatch = 128; // sweeps whose results travel in one copy (d_expect as expect_paulis_shard lays it out)
-    constexpr int kSlots = kMaxPauliTermsPerSweep;
     void *lam = s->spare && s->spare != s->amps ? s->spare : s->d_adjoint; // the spare buffer is idle outside a flush
     if (!lam) {
         HIP_TRY(hipMalloc(&lam, s->amp_bytes() << s->n));
         s->d_adjoint = lam;
     }
-    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kBatch * kSlots) * sizeof(double)));
-    double *d_results = s->d_expect + kExpectPartialDoubles;
+    QSIM_TRY(alloc_result_rows(s));
 
     QSIM_TRY(qsim_apply_pauli_rotations(s, rot_x, rot_z, thetas, num_rot));
     QSIM_TRY(settle(s));
@@ -307,50 +334,30 @@ extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const u
 
     // row 0: the energy, Re <lambda|psi>, as one paired expectation sweep over the two buffers; then the pieces, last first
     const std::vector<std::pair<long, int>> pieces = adjoint_pieces(rot_x, num_rot);
-    const size_t rows = 1 + pieces.size();
     const LaunchCfg cfg{s->stream, s->grid_cap};
-    std::vector<double> host((size_t)kBatch * kSlots);
-    for (size_t first = 0; first < rows; first += kBatch) {
-        const size_t last = std::min(rows, first + (size_t)kBatch);
-        for (size_t r = first; r < last; r++) {
-            double *d_out = d_results + (r - first) * kSlots;
+    return sweep_result_rows(
+        s, 1 + pieces.size(),
+        [&](size_t r, double *d_row) -> int {
             if (r == 0) {
                 ExpectSweep sw{};
                 sw.full = true; // x == 0 over two buffers: every index, its partner the same index of lambda
                 sw.count = 1;
-                HIP_TRY(launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_out));
-                continue;
+                return launched("expectation", launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row));
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
-            RotSweep sw{};
-            sw.x = rot_x[piece.first];
-            sw.count = piece.second;
-            for (int k = 0; k < sw.count; k++) {
-                const uint64_t z = rot_z[piece.first + k];
-                const double half = -0.5 * thetas[piece.first + k]; // U^+
-                const int ny = __builtin_popcountll(sw.x & z);
-                sw.z[k] = z;
-                sw.c[k] = std::cos(half);
-                sw.v[k] = rotation_v(ny, std::sin(half));
-                if (ny & 1) sw.odd_mask |= 1u << k;
-            }
-            const hipError_t e = launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_out);
-            if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "adjoint sweep launch failed: %s", hipGetErrorString(e));
+            const RotSweep sw = rot_sweep(rot_x[piece.first], rot_z + piece.first, thetas + piece.first, piece.second, -1.0 /* U^+ */, 0, index_mask(s->n), s->n);
+            QSIM_TRY(launched("adjoint", launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row)));
             g_adjoint_sweeps++;
-        }
-        HIP_TRY(hipMemcpyAsync(host.data(), d_results, (last - first) * kSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t r = first; r < last; r++) {
-            const double *row = host.data() + (r - first) * kSlots;
+            return QSIM_OK;
+        },
+        [&](size_t r, const double *row) {
             if (r == 0) {
                 if (energy) *energy = row[0];
-                continue;
+                return;
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
             // Im (i^ny B): the kernel summed Im B (even ny) or Re B (odd); both members of a pair are in B, so the factor is 1, not 2
             for (int k = 0; grad && k < piece.second; k++)
                 grad[piece.first + k] = pauli_phase(__builtin_popcountll(rot_x[piece.first] & rot_z[piece.first + k])) * row[k];
-        }
-    }
-    return QSIM_OK;
+        });
 }

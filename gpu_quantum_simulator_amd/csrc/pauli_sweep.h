@@ -12,21 +12,23 @@
 // t = (q << kTidBits) | tid is expanded to an amplitude index by a bit insertion (the zero at bit h), which is linear over OR of
 // disjoint bit sets: popcount(j & z) = popcount(E(q << kTidBits) & z) + popcount(E(tid) & z) (+ z bit 0 for the odd fp32 slot).
 // The first part is uniform over the workgroup (scalar unit), the second is constant per thread.
-// fp32 corners: x odd puts the partner in the other half of its unit (each kernel swaps the halves itself, in one line: as a shared
-// inline function the swap changed the instruction schedule of the fp32 paired k_expect instantiations); x == 1 on one state puts
-// both members of a pair in ONE unit (odd_slot == 0: every unit is visited, its even slot is j); a register of one amplitude is 8
-// bytes long, no unit (k_expect guards its loads, k_pauli_rot takes a single-thread path of its own).
+// fp32 corners: x odd puts the partner in the other half of its unit; x == 1 on one state puts both members of a pair in ONE unit
+// (odd_slot == 0: every unit is visited, its even slot is j); a register of one amplitude is 8 bytes long, no unit
+// (load_unit_or_one; k_pauli_rot takes a single-thread path of its own).
+//
+// What the kernels share is here only where sharing left every kernel body instruction for instruction as it was.  Each kernel
+// therefore still has its own: the way from units to (ar, ai, br, bi) with the fp32 half-swap in one line (shared, it changed the
+// fp32 paired instantiations of k_expect and of k_pauli_adjoint), the thread's own parity mask `own` (k_pauli_rot, k_pauli_adjoint
+// and k_pauli_sum changed), the choice "s ? odd_slot_sign : sg" (as a function of s it changed all four) and the block reduction of
+// k_expect and k_pauli_adjoint (both changed).  The way back, own_unit and partner_unit, is shared.
 //
 // Grids.  Every workgroup of a sweep walks the same number of trips, so a second, partly filled round of workgroups would cost a
-// whole round: the default grid is what is resident at once (resident_grid).  The kernels cap it differently, on purpose:
-// an expectation sweep at kExpectGrid rows whatever LaunchCfg::grid_cap says, because its partial-sum buffer is sized by that; a
-// rotation sweep at grid_cap when one is set (QSIM_OPT_GRID_CAP, as for every other kernel), and at 1024 when the occupancy
-// query fails.  The adjoint sweep (k_pauli_adjoint) writes amplitudes AND reduces: it follows the expectation sweep's rule — the
-// resident grid, at most kExpectGrid rows, grid_cap NOT applied — because its sums are added row by row, so their bits depend on
-// the grid, and equal calls must return equal bits whatever the option says; its amplitudes are each written by one thread and
-// would not care.  k_pauli_sum (lambda = H psi) only writes, each output by one thread: the rotation sweep's rule.
+// whole round: the default grid is what is resident at once (resident_grid).  Two rules cap it, on purpose differently: reducing_grid
+// (k_expect, k_pauli_adjoint) and writing_grid (k_pauli_rot, k_pauli_sum), which say why.
 #ifndef QSIM_PAULI_SWEEP_H
 #define QSIM_PAULI_SWEEP_H
+
+#include <type_traits>
 
 #include "qsim_internal.h"
 
@@ -140,6 +142,75 @@ int resident_grid() {
     return grid;
 }
 
+// The grid of a sweep that REDUCES (k_expect, k_pauli_adjoint): the resident grid, at most kExpectGrid workgroups because the
+// partial-sum buffer has that many rows, whatever LaunchCfg::grid_cap says — the sums are added row by row, so their bits depend on
+// the grid, and equal calls must return equal bits whatever the option says.  (k_pauli_adjoint writes amplitudes too; each is
+// written by one thread and would not care.)  The 32-slot instantiations of k_expect hold 3 workgroups per CU, the others 4 and more.
+template <auto Kernel>
+unsigned reducing_grid(uint64_t units, uint64_t per_block) {
+    const int resident = resident_grid<Kernel>();
+    const uint64_t cap = resident > 0 && resident < kExpectGrid ? resident : kExpectGrid;
+    uint64_t grid = (units + per_block - 1) / per_block;
+    if (grid > cap) grid = cap;
+    return grid == 0 ? 1u : (unsigned)grid;
+}
+// The grid of a sweep that only WRITES, every output by one thread (k_pauli_rot, k_pauli_sum): QSIM_OPT_GRID_CAP > 0 caps it as it
+// does for every kernel (a huge cap: one workgroup per block of units); otherwise the resident grid, and 1024 when the occupancy
+// query fails.
+template <auto Kernel>
+unsigned writing_grid(const LaunchCfg &cfg, uint64_t units, uint64_t per_block) {
+    const int resident = resident_grid<Kernel>();
+    const uint64_t cap = cfg.grid_cap > 0 ? (uint64_t)cfg.grid_cap : resident > 0 ? (uint64_t)resident : 1024;
+    uint64_t grid = (units + per_block - 1) / per_block;
+    if (grid > cap) grid = cap;
+    return grid == 0 ? 1u : (unsigned)grid;
+}
+
+// ---- which instantiation a launch runs in ---------------------------------------------------------------------------------------
+// f(R{}, std::bool_constant<PAIRED>{}) for the state's precision and for whether the sweep has a partner
+template <typename F>
+hipError_t for_precision_and_pairing(bool f32, bool paired, F &&f) {
+    if (f32) return paired ? f(float{}, std::true_type{}) : f(float{}, std::false_type{});
+    return paired ? f(double{}, std::true_type{}) : f(double{}, std::false_type{});
+}
+// f(std::integral_constant<int, KT>{}) for KT = expect_slots(count)
+template <typename F>
+hipError_t for_term_slots(int count, F &&f) {
+    switch (expect_slots(count)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- term records: what a kernel gets of a RotSweep or SumSweep, by value (scalar loads) -------------------------------------------
+static_assert(kMaxPauliTermsPerSweep <= 32, "one bit per term in a record's `odd` and in a thread's parity mask");
+// k_pauli_rot (KT = kMaxPauliTermsPerSweep, terms of +theta) and k_pauli_adjoint (KT = expect_slots(count), terms of -theta)
+template <typename R, int KT>
+struct RotTerms {
+    uint64_t z[KT];     // unused slots: 0
+    R c[KT], v[KT];     // rounded once to the state's precision by the host
+    uint32_t odd;       // bit k: ny is odd — w = v is real and a's sign is opposite to b's (the adjoint sweep sums the real part of its
+                        // bracket); else w = i v (the imaginary part)
+    int32_t count;
+};
+static_assert(sizeof(RotTerms<double, kMaxPauliTermsPerSweep>) <= 1024, "term records stay well inside the 4 KiB of kernel arguments");
+// z, c, odd and count of the sweep's terms, and v where the record has one (RotTerms; adjoint.hip's SumTerms has none)
+template <typename Rec, typename Sweep>
+void fill_terms(Rec &rec, const Sweep &sw) {
+    using R = std::remove_reference_t<decltype(rec.c[0])>;
+    constexpr int slots = (int)(sizeof(rec.z) / sizeof(rec.z[0]));
+    for (int k = 0; k < sw.count && k < slots; k++) {
+        rec.z[k] = sw.z[k];
+        rec.c[k] = (R)sw.c[k];
+        if constexpr (std::is_same_v<Sweep, RotSweep>) rec.v[k] = (R)sw.v[k];
+    }
+    rec.odd = sw.odd_mask;
+    rec.count = sw.count;
+}
+
 // ---- device helpers -----------------------------------------------------------------------------------------------------------
 template <typename R> struct Vec16;
 template <> struct Vec16<double> { using type = double2; };
@@ -160,7 +231,37 @@ template <typename R>
 __device__ __forceinline__ typename Vec16<R>::type load_unit(const R *p, uint64_t amp) {
     return *reinterpret_cast<const typename Vec16<R>::type *>(p + 2 * amp);
 }
-
+// the same for a register that may be a single fp32 amplitude: 8 bytes long, no unit
+template <typename R>
+__device__ __forceinline__ typename Vec16<R>::type load_unit_or_one(const SweepGeom &g, const R *p, uint64_t amp) {
+    if constexpr (sizeof(R) == 4) if (g.amps < 2) {
+        const float2 one = *reinterpret_cast<const float2 *>(p);
+        float4 v{};
+        v.x = one.x;
+        v.y = one.y;
+        return v;
+    }
+    return load_unit(p, amp);
+}
+// (-1)^popcount(j & z) as a sign bit (bit 31) for flip — j: the index bits that are uniform over the workgroup (scalar), or a thread's
+// own — and the same for the odd fp32 slot of a unit, whose index has bit 0 set
+__device__ __forceinline__ uint32_t parity_sign(uint64_t j, uint64_t z) { return ((uint32_t)__builtin_popcountll(j & z) & 1u) << 31; }
+__device__ __forceinline__ uint32_t odd_slot_sign(uint32_t sg, uint64_t z) { return sg ^ ((uint32_t)(z & 1ULL) << 31); }
+// One state's visited unit and its partner's unit as they are stored, from (xr, xi) of the visited member's slots and (yr, yi) of
+// the partner's.  fp32: selects on values, so that every store stays one 16-byte store; `same`: x == 1 on one state, the pair is
+// the unit; `swapped`: x is odd, the partner sits in the other half of its unit.
+template <typename R, int A>
+__device__ __forceinline__ typename Vec16<R>::type own_unit(bool same, const R (&xr)[A], const R (&xi)[A], const R (&yr)[A], const R (&yi)[A]) {
+    using V = typename Vec16<R>::type;
+    if constexpr (A == 1) return V{xr[0], xi[0]};
+    else return V{xr[0], xi[0], same ? yr[0] : xr[1], same ? yi[0] : xi[1]};
+}
+template <typename R, int A>
+__device__ __forceinline__ typename Vec16<R>::type partner_unit(bool swapped, const R (&yr)[A], const R (&yi)[A]) {
+    using V = typename Vec16<R>::type;
+    if constexpr (A == 1) return V{yr[0], yi[0]};
+    else return V{swapped ? yr[1] : yr[0], swapped ? yi[1] : yi[0], swapped ? yr[0] : yr[1], swapped ? yi[0] : yi[1]};
+}
 
 // The 2x2 of one rotation term on one pair, sv = s(j) v (evolve.hip has the rule): shared by k_pauli_rot and k_pauli_adjoint.
 template <typename R>

@@ -188,6 +188,12 @@ hipError_t launch_pack(const LaunchCfg &cfg, const void *in, void *out, void *co
 // ---- pauli.cpp: Pauli strings on one state that is shard `rank` of a register whose local qubits are the low qsim_num_qubits(s) bits
 // of the masks (pauli_sweep.h has the sweeps themselves).  A partner is the buffer of shard rank ^ x_rank, quiescent, materialised
 // and on the same device; it goes with x on rank qubits (x_rank != 0) and only with it, and then every local index is swept.
+// The argument checks every Pauli entry point opens with, once its state or cluster is known to be there: no negative count, no
+// NULL array (`third`: the one that goes with the masks — results, angles or coefficients), no mask bit at or above n, and
+// `numbers` (angles or coefficients; `number` says which in the message) finite where there are any.  `report` is fail or cfail:
+// whose last error it becomes.  Hidden: the library's exports stay what they were.
+__attribute__((visibility("hidden"))) int check_pauli_terms(int (*report)(int, const char *, ...), const char *who, int n, const uint64_t *x_masks, const uint64_t *z_masks, const void *third,
+                      const double *numbers, long num_terms, const char *number = "angle");
 // <P_t> restricted to the shard; every term has the same x_rank.  Adds nothing up across shards.
 int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms,
                         double *out);
