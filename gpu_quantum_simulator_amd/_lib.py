@@ -92,6 +92,9 @@ SIGNATURES = {
     "qsim_apply_pauli_rotations": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long]),
     "qsim_pauli_rotation_plan": (c_int, [POINTER(c_uint64), POINTER(c_uint64), c_long, POINTER(c_long), POINTER(c_long)]),
     "qsim_pauli_rotations_per_sweep": (c_int, []),
+    "qsim_apply_controlled_pauli_rotations": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), _DP, c_long]),
+    "qsim_controlled_rotation_plan": (c_int, [POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), c_long, c_int, c_int, POINTER(c_long), POINTER(c_long),
+                                              POINTER(c_uint64)]),
     "qsim_pauli_rotation_sweeps_launched": (c_uint64, []),
     "qsim_cluster_apply_pauli_rotations": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long]),
     "qsim_pauli_gradient": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, _DP, _DP]),

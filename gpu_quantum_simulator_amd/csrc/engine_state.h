@@ -5,8 +5,9 @@
 //   planning.cpp  the measured tile-bit orders and schedule choices (process-wide tables, private to it) and the planning API
 //   readout.cpp   reads, writes, norms, sampling                             pack.cpp  re-layouts and buffer hand-overs
 //   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values, rotations
-//                                                                           and adjoint gradients (the host side of expect.hip,
-//                                                                           evolve.hip and adjoint.hip; pauli_sweep.h)
+//                                                                           (controlled ones too) and adjoint gradients (the host
+//                                                                           side of expect.hip, evolve.hip, crot.hip and
+//                                                                           adjoint.hip; pauli_sweep.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 

@@ -1,5 +1,6 @@
 // pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values"),
-// rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations") and adjoint-mode gradients of
+// rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations"), the same under control qubits
+// (crot.hip; DESIGN "Controlled Pauli rotations") and adjoint-mode gradients of
 // <H> with respect to the angles (adjoint.hip; DESIGN "Adjoint gradients").  pauli_sweep.h has what the sweeps share.  Every
 // entry point opens with settle() and then only touches qsim_state's buffer, stream and d_expect; expectation values read the
 // buffer, rotations write it, a gradient call writes it and a second buffer of the same size (the spare one, or d_adjoint) and
@@ -155,7 +156,7 @@ extern "C" int qsim_expect_paulis(qsim_state *s, const uint64_t *x_masks, const 
 
 // ---- rotations ------------------------------------------------------------------------------------------------------------------
 // A term that is X or Y on a single qubit is a 2x2 for the gate queue; every other term goes to an in-place sweep, and consecutive
-// sweep terms with one x mask share a sweep.
+// sweep terms with one x mask (and one control mask, where there are controls: below) share a sweep.
 // Terms per sweep: 32, the record count of k_pauli_rot; not backed by a measurement yet (DESIGN "Pauli rotations").
 static constexpr int kPauliRotationsPerSweep = kMaxPauliTermsPerSweep;
 extern "C" int qsim_pauli_rotations_per_sweep(void) { return kPauliRotationsPerSweep; }
@@ -165,20 +166,22 @@ extern "C" uint64_t qsim_pauli_rotation_sweeps_launched(void) { return g_sweeps_
 
 long qsim::rotation_sweeps(long run_length) { return (run_length + kPauliRotationsPerSweep - 1) / kPauliRotationsPerSweep; }
 
-static bool is_gate(uint64_t x, uint64_t z, uint64_t local_mask) {
-    return __builtin_popcountll(x) == 1 && (z & ~x) == 0 && (x & local_mask) != 0;
+// with at most one control: the 2x2, or its 4x4 under the control
+static bool is_gate(uint64_t c, uint64_t x, uint64_t z, uint64_t local_mask) {
+    return __builtin_popcountll(c) <= 1 && __builtin_popcountll(x) == 1 && (z & ~x) == 0 && (x & local_mask) != 0;
 }
 
-std::vector<RotRoute> qsim::route_rotations(const uint64_t *X, const uint64_t *Z, long num, uint64_t local_mask) {
+std::vector<RotRoute> qsim::route_rotations(const uint64_t *X, const uint64_t *Z, long num, uint64_t local_mask, const uint64_t *C) {
     std::vector<RotRoute> out;
+    auto c = [&](long t) { return C ? C[t] : 0; };
     for (long t = 0; t < num;) {
-        if (is_gate(X[t], Z[t], local_mask)) {
+        if (is_gate(c(t), X[t], Z[t], local_mask)) {
             out.push_back({t, 1, true});
             t++;
             continue;
         }
         long e = t + 1;
-        while (e < num && X[e] == X[t] && !is_gate(X[e], Z[e], local_mask)) e++;
+        while (e < num && X[e] == X[t] && c(e) == c(t) && !is_gate(c(e), X[e], Z[e], local_mask)) e++;
         out.push_back({t, e - t, false});
         t = e;
     }
@@ -237,16 +240,102 @@ extern "C" int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t 
     return QSIM_OK;
 }
 
+// ---- controlled rotations (crot.hip; DESIGN "Controlled Pauli rotations") ---------------------------------------------------------
+// Term t acts as exp(-i theta/2 P_t) where every qubit of c_masks[t] is 1 and as the identity elsewhere.  route_rotations has the
+// rule: one control on a single X or Y is a 4x4 for the gate queue, every other controlled term goes to a sweep of the control
+// subspace, and a run shares sweeps only under one control mask.  A term without controls takes the uncontrolled path.
+static int check_controls(const char *who, int n, const uint64_t *C, const uint64_t *X, const uint64_t *Z, long num) {
+    for (long t = 0; C && t < num; t++) {
+        if (C[t] & ~index_mask(n)) return fail(QSIM_ERR_ARG, "%s: term %ld names a control qubit outside the %d-qubit register", who, t, n);
+        if (C[t] & (X[t] | Z[t])) return fail(QSIM_ERR_ARG, "%s: term %ld: a control qubit carries a Pauli factor", who, t);
+    }
+    return QSIM_OK;
+}
+
+// [[I, 0], [0, R]] on (control, target) as qsim_apply_2q takes it: row / column index = (bit q_hi, bit q_lo), R = pauli_rot_1q
+static void controlled_rot_2q(bool y, double theta, bool control_is_hi, double *U) {
+    double R[8];
+    pauli_rot_1q(y, theta, R);
+    std::fill(U, U + 32, 0.0);
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) {
+            const int rc = control_is_hi ? r >> 1 : r & 1, cc = control_is_hi ? c >> 1 : c & 1;
+            const int rt = control_is_hi ? r & 1 : r >> 1, ct = control_is_hi ? c & 1 : c >> 1;
+            if (rc != cc) continue;
+            if (rc) U[2 * (4 * r + c)] = R[2 * (2 * rt + ct)], U[2 * (4 * r + c) + 1] = R[2 * (2 * rt + ct) + 1];
+            else U[2 * (4 * r + c)] = rt == ct ? 1.0 : 0.0;
+        }
+}
+
+// One run under the control mask c != 0, on a single state
+static int controlled_rot_run(qsim_state *s, uint64_t c, uint64_t x, const uint64_t *Z, const double *thetas, long count) {
+    if (count == 0 || qsim_holds_nothing(s)) return QSIM_OK;
+    QSIM_TRY(settle(s));
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    for (long first = 0; first < count; first += kPauliRotationsPerSweep) {
+        const RotSweep sw = rot_sweep(x, Z + first, thetas + first, (int)std::min<long>(kPauliRotationsPerSweep, count - first), 1.0, 0, index_mask(s->n), s->n);
+        QSIM_TRY(launched("controlled rotation", launch_pauli_crot(cfg, s->amps, s->f32, s->n, c, sw)));
+        g_sweeps_launched++;
+    }
+    return QSIM_OK;
+}
+
+// checked arguments; C may be NULL: no controls anywhere
+static int apply_rotations(qsim_state *s, const uint64_t *C, const uint64_t *X, const uint64_t *Z, const double *thetas, long num) {
+    for (const RotRoute &r : route_rotations(X, Z, num, index_mask(s->n), C)) {
+        const uint64_t c = C ? C[r.first] : 0, x = X[r.first];
+        if (r.gate) {
+            const bool y = (Z[r.first] & x) != 0;
+            const int target = __builtin_ctzll(x), control = c ? __builtin_ctzll(c) : -1;
+            double U[32];
+            if (c) {
+                controlled_rot_2q(y, thetas[r.first], control > target, U);
+                QSIM_TRY(qsim_apply_2q(s, U, std::max(control, target), std::min(control, target)));
+            } else {
+                pauli_rot_1q(y, thetas[r.first], U);
+                QSIM_TRY(qsim_apply_1q(s, U, target));
+            }
+        } else if (c) {
+            QSIM_TRY(controlled_rot_run(s, c, x, Z + r.first, thetas + r.first, r.count));
+        } else {
+            QSIM_TRY(pauli_rot_run(s, nullptr, 0, x, Z + r.first, thetas + r.first, r.count));
+        }
+    }
+    return QSIM_OK;
+}
+
 extern "C" int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *thetas, long num_terms) {
     QSIM_TRY(check_terms("qsim_apply_pauli_rotations", s, x_masks, z_masks, thetas, thetas, num_terms));
-    for (const RotRoute &r : route_rotations(x_masks, z_masks, num_terms, index_mask(s->n))) {
+    return apply_rotations(s, nullptr, x_masks, z_masks, thetas, num_terms);
+}
+
+extern "C" int qsim_apply_controlled_pauli_rotations(qsim_state *s, const uint64_t *c_masks, const uint64_t *x_masks, const uint64_t *z_masks,
+                                                     const double *thetas, long num_terms) {
+    const char *who = "qsim_apply_controlled_pauli_rotations";
+    QSIM_TRY(check_terms(who, s, x_masks, z_masks, thetas, thetas, num_terms));
+    QSIM_TRY(check_controls(who, s->n, c_masks, x_masks, z_masks, num_terms));
+    return apply_rotations(s, c_masks, x_masks, z_masks, thetas, num_terms);
+}
+
+extern "C" int qsim_controlled_rotation_plan(const uint64_t *c_masks, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, int num_q,
+                                             int precision_bits, long *sweeps, long *queued_as_gates, uint64_t *units_visited) {
+    const char *who = "qsim_controlled_rotation_plan";
+    if (!sweeps || !queued_as_gates || !units_visited) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
+    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    QSIM_TRY(check_pauli_terms(fail, who, num_q, x_masks, z_masks, x_masks, nullptr, num_terms));
+    QSIM_TRY(check_controls(who, num_q, c_masks, x_masks, z_masks, num_terms));
+    *sweeps = *queued_as_gates = 0;
+    *units_visited = 0;
+    const bool f32 = precision_bits == 32;
+    for (const RotRoute &r : route_rotations(x_masks, z_masks, num_terms, index_mask(num_q), c_masks)) {
         if (r.gate) {
-            double U[8];
-            pauli_rot_1q((z_masks[r.first] & x_masks[r.first]) != 0, thetas[r.first], U);
-            QSIM_TRY(qsim_apply_1q(s, U, __builtin_ctzll(x_masks[r.first])));
-        } else {
-            QSIM_TRY(pauli_rot_run(s, nullptr, 0, x_masks[r.first], z_masks + r.first, thetas + r.first, r.count));
+            ++*queued_as_gates;
+            continue;
         }
+        const uint64_t c = c_masks ? c_masks[r.first] : 0, x = x_masks[r.first];
+        *sweeps += rotation_sweeps(r.count);
+        *units_visited += (uint64_t)rotation_sweeps(r.count) * (c ? ctrl_geom(c, x, f32, num_q).units : sweep_geom(x, false, f32, num_q).units);
     }
     return QSIM_OK;
 }

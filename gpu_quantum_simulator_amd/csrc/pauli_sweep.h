@@ -1,6 +1,6 @@
 // pauli_sweep.h — how a Pauli sweep walks a state: what expect.hip (<psi|P|psi>, read-only), evolve.hip (exp(-i theta/2 P), in
-// place), adjoint.hip (dE/dtheta: the backward sweep over psi and lambda, and lambda = H psi) and their host side pauli.cpp share.
-// DESIGN §7b opens with the same account.
+// place), adjoint.hip (dE/dtheta: the backward sweep over psi and lambda, and lambda = H psi), crot.hip (the rotation under control
+// qubits: CtrlGeom below) and their host side pauli.cpp share.  DESIGN §7b opens with the same account.
 //
 // A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
 // pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets
@@ -64,6 +64,10 @@ hipError_t launch_expect(const LaunchCfg &cfg, const void *a, const void *b, boo
 hipError_t launch_expect_final(hipStream_t stream, const double *d_partial, int rows, int kt, double *d_out);
 // a_j' = c a_j + w (-1)^ny s(j) b_(j^x),  b_(j^x)' = c b_(j^x) + w s(j) a_j, term after term.
 hipError_t launch_pauli_rot(const LaunchCfg &cfg, void *a, void *b, bool f32, int n, const RotSweep &sw);
+// The same 2x2s, term after term, on the indices whose bits of `controls` are all 1 and nowhere else (crot.hip): one
+// state, one buffer (sw.full is refused), controls != 0, inside the buffer and disjoint from sw.x.  A z bit on a control qubit is
+// a constant sign there, folded into the term's v.
+hipError_t launch_pauli_crot(const LaunchCfg &cfg, void *a, bool f32, int n, uint64_t controls, const RotSweep &sw);
 // The backward sweep of an adjoint gradient over psi and lambda (two buffers, one state each: sw.full is refused).  From the LAST
 // term of sw to the first: d_out[k] = sum over the pairs of s_k(j) Re (odd ny) or Im (even ny) of [conj(lambda_(j^x)) psi_j +
 // (-1)^ny conj(lambda_j) psi_(j^x)]  (x == 0: sum_j s_k(j) Im conj(lambda_j) psi_j), then term k's 2x2 — c and v as for
@@ -124,6 +128,42 @@ inline SweepGeom sweep_geom(uint64_t x, bool full, bool f32, int n) {
     }
     g.units = g.odd_slot ? (amps_visited >> as) : N >> as;
     if (g.units == 0) g.units = 1; // one fp32 amplitude
+    return g;
+}
+
+// A sweep under controls (k_pauli_crot) visits the indices with every control bit 1 and, for x != 0, the highest bit h of x clear:
+// 2^-c of what sweep_geom visits.  A unit index is expanded by inserting one fixed bit per set bit of `zeros` — the list of
+// insertion positions in the unit index, as a bit set, taken lowest first (each insertion leaves the bits below its position and the
+// bits inserted before it where they are).  Every inserted bit is a zero, so the expansion stays linear over OR, and the control
+// bits are OR-ed in afterwards as the constant `ones`.  fp32: amplitude bit 0 is the slot inside a unit and is never inserted —
+// x == 1 is odd_slot == 0 as in SweepGeom, and a control on qubit 0 leaves the odd slot of every visited unit as the only active
+// one (first_slot == 1); the two cannot meet, controls and x are disjoint.
+struct CtrlGeom {       // by value: a kernel argument
+    uint64_t units;     // 16-byte units to visit
+    uint64_t x;         // partner amplitude = amplitude ^ x
+    uint64_t zeros;     // bit p: a zero is inserted at bit p of the unit index (h and the controls, but for amplitude bit 0 in fp32)
+    uint64_t ones;      // the control bits of a unit's (even) amplitude index
+    uint32_t odd_slot;  // as in SweepGeom
+    uint32_t first_slot;// fp32: 1 when qubit 0 is a control (slot 0 is loaded and stored as it is)
+};
+
+inline CtrlGeom ctrl_geom(uint64_t controls, uint64_t x, bool f32, int n) {
+    const uint64_t N = 1ULL << n;
+    const int as = f32 ? 1 : 0;
+    CtrlGeom g{};
+    g.x = x;
+    g.odd_slot = 1;
+    uint64_t fixed = controls;
+    if (x != 0) {
+        const int h = 63 - __builtin_clzll(x);
+        fixed |= 1ULL << h;
+        if (h < as) g.odd_slot = 0;
+    }
+    g.first_slot = (uint32_t)(controls & (uint64_t)as);
+    g.ones = controls & ~(uint64_t)as;
+    g.zeros = (fixed & (N - 1ULL)) >> as;
+    g.units = (N >> as) >> __builtin_popcountll(g.zeros);
+    if (g.units == 0) g.units = 1; // one fp32 amplitude (no control fits such a register)
     return g;
 }
 

@@ -199,8 +199,9 @@ int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const
                         double *out);
 // How a list of rotations exp(-i theta/2 P) is carried out, in the caller's order.  A term that is X or Y on ONE qubit inside
 // local_mask is a gate for the queue; every other term belongs to a run: a maximal stretch of consecutive such terms with equal x.
+// c_masks (NULL: none): a term's control qubits.  The gate rule holds under at most ONE control (the 4x4); a run has one control mask.
 struct RotRoute { long first, count; bool gate; };
-std::vector<RotRoute> route_rotations(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, uint64_t local_mask);
+std::vector<RotRoute> route_rotations(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, uint64_t local_mask, const uint64_t *c_masks = nullptr);
 long rotation_sweeps(long run_length); // ceil(run_length / K)
 // One run; x carries the run's rank bits too.  Launches on the state's stream and returns.
 int pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x, const uint64_t *z_masks, const double *thetas, long count);

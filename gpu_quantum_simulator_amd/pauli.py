@@ -1,5 +1,5 @@
-"""Pauli strings as the two masks qsim_expect_paulis and qsim_apply_pauli_rotations take, and the rotation list of a product
-formula.  Pure Python: usable without the library.
+"""Pauli strings as the two masks qsim_expect_paulis and qsim_apply_pauli_rotations take, the control mask of a controlled
+rotation, and the rotation list of a product formula.  Pure Python: usable without the library.
 
 A string is written sparsely in the project's qubit numbering (qubit q = bit q of the amplitude index): "X0 Z3 Y17" —
 whitespace-separated, letters XYZ in either case, "I5" allowed and ignored, "" = the identity."""
@@ -27,6 +27,22 @@ def pauli_masks(text: str, num_q: int) -> Tuple[int, int]:
         if letter in "ZY":
             z |= 1 << q
     return x, z
+
+
+def control_mask(controls: Iterable[int], num_q: int, pauli: str = "") -> int:
+    """The control mask of a controlled rotation: bit q set for every qubit number q of `controls`.  ValueError for a qubit named
+    twice, a qubit outside [0, num_q) and a control that the string `pauli` also names with X, Y or Z."""
+    x, z = pauli_masks(pauli, num_q)
+    mask = 0
+    for q in controls:
+        if int(q) != q or not 0 <= q < num_q:
+            raise ValueError(f"control qubit {q!r} is outside the {num_q}-qubit register")
+        if mask >> int(q) & 1:
+            raise ValueError(f"control qubit {q} is named twice")
+        if (x | z) >> int(q) & 1:
+            raise ValueError(f"control qubit {q} carries a Pauli factor in {pauli!r}")
+        mask |= 1 << int(q)
+    return mask
 
 
 def trotter_rotations(terms: Iterable, time: float, steps: int = 1, order: int = 1) -> List[Tuple[float, str]]:

@@ -177,6 +177,18 @@ def _rotation_arrays(rotations, num_q: int):
     return xs, zs, thetas, xp, zp, _dp(thetas)
 
 
+def _split_controls(rotations):
+    """(theta, string) and (theta, string, controls) entries, mixed, as ([(theta, string)], [controls]); controls () where none."""
+    pairs, controls = [], []
+    for entry in rotations:
+        entry = tuple(entry)
+        if len(entry) not in (2, 3):
+            raise ValueError(f"a rotation is (theta, string) or (theta, string, controls), not {entry!r}")
+        pairs.append(entry[:2])
+        controls.append(tuple(entry[2]) if len(entry) == 3 else ())
+    return pairs, controls
+
+
 def _hamiltonian_arrays(terms, num_q: int):
     """(real coefficient, string) pairs as the arrays qsim_pauli_gradient and qsim_pauli_sum_into take: xs, zs, coeffs and their
     pointers.  ValueError for a complex coefficient."""
@@ -218,17 +230,28 @@ class _PauliStrings:
         every coefficient is real, else a complex."""
         return _weighted_sum(terms, self.expectation_terms)
 
-    def apply_pauli_rotation(self, theta: float, pauli: str) -> None:
+    def apply_pauli_rotation(self, theta: float, pauli: str, controls=()) -> None:
         """state <- exp(-i theta/2 P) state for the Pauli string P ("X0 Y3 Z17", see pauli_masks); on a Cluster the string
-        names LOGICAL qubits."""
-        self.apply_pauli_rotations([(theta, pauli)])
+        names LOGICAL qubits.  `controls` (a Simulator only): qubit numbers; the rotation then acts where all of them are 1."""
+        self.apply_pauli_rotations([(theta, pauli, controls)])
 
     def apply_pauli_rotations(self, rotations) -> None:
         """exp(-i theta/2 P) for every (theta, string) of `rotations`, the first one first, as ONE call of
         qsim_apply_pauli_rotations (qsim_cluster_apply_pauli_rotations): consecutive strings with X/Y on the same qubits share
-        a sweep of the state.  Returns without waiting."""
-        xs, zs, thetas, xp, zp, tp = _rotation_arrays(rotations, self.num_qubits)
-        self._check(getattr(_lib.load(), self._rotate_fn)(self._h, xp, zp, tp, xs.size))
+        a sweep of the state.  Returns without waiting.
+        An entry may be (theta, string, controls) instead, controls being qubit numbers: that rotation acts only where every
+        control qubit is 1 (qsim_apply_controlled_pauli_rotations: a sweep of 2^-c of the state for c controls; consecutive
+        terms share it under one control set).  ValueError for a control named twice, outside the register, or named by the
+        string too — and for any control on a Cluster: sharded states have no controlled rotations yet."""
+        pairs, controls = _split_controls(rotations)
+        xs, zs, thetas, xp, zp, tp = _rotation_arrays(pairs, self.num_qubits)
+        if any(controls):
+            self._apply_controlled(pairs, controls, xp, zp, tp)
+        else:
+            self._check(getattr(_lib.load(), self._rotate_fn)(self._h, xp, zp, tp, xs.size))
+
+    def _apply_controlled(self, pairs, controls, xp, zp, tp) -> None:
+        raise ValueError("sharded states have no controlled rotations yet")
 
     def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
         """A product formula for exp(-i H time) with H = sum_k c_k P_k given as (c_k, string) pairs, real c_k
@@ -285,6 +308,36 @@ class Simulator(_PauliStrings):
         energy, grad = c_double(0.0), np.zeros(rxs.size, dtype=np.float64)
         check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
         return float(energy.value), grad
+
+    # -- controlled rotations (single states only)
+    def _apply_controlled(self, pairs, controls, xp, zp, tp) -> None:
+        from ctypes import c_uint64
+        from .pauli import control_mask
+        cs = np.array([control_mask(c, self.num_qubits, text) for (_, text), c in zip(pairs, controls)], dtype=np.uint64)
+        check(_lib.load().qsim_apply_controlled_pauli_rotations(self._h, cs.ctypes.data_as(ctypes.POINTER(c_uint64)), xp, zp, tp, cs.size))
+
+    def apply_mcphase(self, phi: float, qubits) -> None:
+        """diag(1, ..., 1, e^(i phi)) on `qubits`: the phase e^(i phi) where all of them are 1 — the controlled identity string
+        with theta = -2 phi, one sweep over 2^-len(qubits) of the state.  Symmetric in the qubits."""
+        self.apply_pauli_rotation(-2.0 * phi, "", qubits)
+
+    def apply_mcz(self, qubits) -> None:
+        """The multi-controlled Z on `qubits` (a Grover oracle's phase flip of |1...1>): apply_mcphase(pi, qubits)."""
+        self.apply_mcphase(np.pi, qubits)
+
+    def apply_mcx(self, controls, target: int) -> None:
+        """X on `target` where every qubit of `controls` is 1 (two controls: the Toffoli gate).  No control: the X gate; one:
+        apply_cx.  More: the controlled rotation by pi about X on the target, which is -i X there, then the controlled identity
+        with theta = -pi, the phase i — two sweeps, each over 2^-len(controls) of the state, together exactly X."""
+        controls = tuple(controls)
+        if len(controls) == 0:
+            self.apply_1q(np.array([[0, 1], [1, 0]]), target)
+        elif len(controls) == 1:
+            if controls[0] == target:
+                raise ValueError(f"control qubit {target} is the target")
+            self.apply_cx(controls[0], target)
+        else:
+            self.apply_pauli_rotations([(np.pi, f"X{target}", controls), (-np.pi, "", controls)])
 
     def pauli_sum_into(self, terms, dst_ptr: int) -> None:
         """dst = sum_t c_t Q_t |state> for (real coefficient, string) pairs, written to the device buffer at `dst_ptr` (2^n

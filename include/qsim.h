@@ -186,6 +186,36 @@ int qsim_apply_pauli_rotations(qsim_state *s, const uint64_t *x_masks, const uin
 /* Host only, no device: what the call above does with these terms — sweeps launched and terms queued as 2x2 gates. */
 int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, long *sweeps, long *queued_as_gates);
 int qsim_pauli_rotations_per_sweep(void); /* K: 32, the one-bit-per-term masks' limit; an unmeasured default ("Pauli rotations") */
+/* ---- controlled Pauli rotations: "... if these qubits are 1" (new) ----
+ * qsim_apply_pauli_rotations with a control mask per term: term t maps the state to [(1 - Pi_t) + Pi_t exp(-i thetas[t]/2 P_t)] state,
+ * Pi_t the projector on "every qubit of c_masks[t] is 1"; angle convention and kept global phase as above, so the identity string
+ * (x = z = 0) under controls is the multi-controlled phase e^(-i theta/2) on the control subspace (theta = -2 phi: diag(1, ..., 1,
+ * e^(i phi)) on the control qubits; phi = pi: a multi-controlled Z).  Terms are applied in the caller's order.  c_masks == NULL: no
+ * controls anywhere; a term with c_masks[t] == 0 takes exactly the path qsim_apply_pauli_rotations gives it, and a call without
+ * any control leaves the bits that call leaves.
+ * Routing of a term WITH controls: one control and X or Y on ONE qubit is queued as its 4x4 (qsim_apply_2q: it fuses like a cx, no
+ * sweep).  Every other controlled term — controlled single-qubit Z terms and the controlled identity included — goes to a
+ * controlled sweep, launched after the queued gates: the 2x2 of the uncontrolled sweep on the same pairs {j, j ^ x}, but only on
+ * the 2^(n-c) indices whose c control bits are 1, so it reads and writes 2^-c of the state.  A maximal run of consecutive sweep
+ * terms with equal x_mask AND equal control mask shares sweeps, qsim_pauli_rotations_per_sweep() terms each; a change of control
+ * mask ends a run as a change of x_mask does.  Controlled sweeps count in qsim_pauli_rotation_sweeps_launched().
+ * Otherwise as qsim_apply_pauli_rotations: returns without waiting, no device allocation, no host synchronisation,
+ * QSIM_OPT_GRID_CAP applies, every amplitude is written by one thread (equal calls give equal bits; an amplitude inside the
+ * control subspace gets the bits the uncontrolled sweep of the same terms gives it), a shard that holds nothing stays untouched,
+ * num_terms == 0 does nothing, a lazily held |0...0> or a partial state is settled first and the support is dense afterwards.
+ * QSIM_ERR_ARG, with the state unchanged: everything qsim_apply_pauli_rotations refuses, a control bit at or above the register's
+ * qubit count, and a control mask that overlaps the term's x_mask | z_mask (a control qubit carries a Pauli factor).
+ * Out of scope: controls in qsim_pauli_gradient, controls on clusters or shards (no qsim_cluster_* counterpart), controlled terms
+ * in product formulas (Simulator.evolve), and a QASM spelling — the parser's grammar is the reference's. */
+int qsim_apply_controlled_pauli_rotations(qsim_state *s, const uint64_t *c_masks, const uint64_t *x_masks, const uint64_t *z_masks,
+                                          const double *thetas, long num_terms);
+/* Host only, no device: what the call above does with these terms on a register of num_q qubits held in precision_bits (64 or 32)
+ * — sweeps launched, terms queued as gates (2x2 and 4x4 together), and units_visited: the sum over the sweeps of the 16-byte units
+ * (one fp64 amplitude, two fp32 amplitudes) the sweep's loop visits, from the geometry function its launcher uses.  Without
+ * controls the first two are qsim_pauli_rotation_plan's.  QSIM_ERR_ARG as above, and for num_q outside [0, 40], precision_bits
+ * other than 64 or 32, a NULL result pointer. */
+int qsim_controlled_rotation_plan(const uint64_t *c_masks, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms, int num_q,
+                                  int precision_bits, long *sweeps, long *queued_as_gates, uint64_t *units_visited);
 /* ---- adjoint-mode gradients of <H> for circuits of Pauli rotations, on the device (new) ----
  * E = <psi_K|H|psi_K> and grad[k] = dE/dtheta_k for psi_K = prod_k exp(-i thetas[k]/2 P_k) |state>, H = sum_t coeffs[t] Q_t (real
  * coefficients): all num_rot derivatives from one forward pass, one application of H and one backward pass, instead of the two
