@@ -57,6 +57,9 @@ class QsimExchangeRoles(ctypes.Structure):
 
 SCHED_CB = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_double), c_int)
 
+TILE_RECORD_CB = ctypes.CFUNCTYPE(None, c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), c_int,
+                                  POINTER(c_double), c_void_p, c_long)
+
 LOCAL_OP_CB = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int, POINTER(c_double))
 
 # every symbol include/qsim.h declares: name -> (restype, argtypes)
@@ -161,6 +164,7 @@ SIGNATURES = {
     "qsim_launch_log_visited": (c_int, [c_void_p, c_long, _DP]),
     "qsim_launch_log_read_share": (c_int, [c_void_p, c_long, _DP]),
     "qsim_launch_log_blocks": (c_int, [c_void_p, c_long, c_void_p, c_int, POINTER(c_int)]),
+    "qsim_launch_log_block_flags": (c_int, [c_void_p, c_long, c_void_p, c_int, POINTER(c_int)]),
     "qsim_tune_circuit": (c_int, [c_void_p, c_void_p, c_int, c_double, POINTER(QsimTuneReport)]),
     "qsim_choose_schedule": (c_int, [c_void_p, c_void_p]),
     "qsim_choose_schedule_while_allocating": (c_int, [c_void_p, c_void_p]),
@@ -190,6 +194,7 @@ SIGNATURES = {
     "qsim_plan_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimStats)]),
     "qsim_plan_passes": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimPassInfo), c_int, POINTER(c_int)]),
     "qsim_schedule_circuit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p]),
+    "qsim_tile_records": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_uint64, TILE_RECORD_CB, c_void_p]),
 }
 # include/qsim_legacy.h
 LEGACY_SYMBOLS = ("compute_state_vector", "execute_single_qubit_gate", "execute_cnot")

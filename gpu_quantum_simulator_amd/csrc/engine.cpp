@@ -449,8 +449,15 @@ int qsim::launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, b
 
 // cached_geom / cached_ops: replay of a cached plan (the tile pass's order and device-resident TileOps);
 // capture / geom_out: the first run of a plan records them.
+// The five header bytes of an encoded block that say which form of the kernel it runs through (qsim_launch_log_block_flags).
+static void push_head(std::vector<uint8_t> &out, const TileOp &t) {
+    for (uint8_t byte : {t.nq, t.terms, t.nsel, t.flags, t.b[7]}) out.push_back(byte);
+}
+
+// cached_heads: those bytes of the cached records, kept on the host with the plan (kHeadBytes per op).
 static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom = nullptr, const TileOp *cached_ops = nullptr,
-                       std::vector<TileOp> *capture = nullptr, TileGeom *geom_out = nullptr, bool oop = false, PackJob *job = nullptr) {
+                       std::vector<TileOp> *capture = nullptr, TileGeom *geom_out = nullptr, bool oop = false, PackJob *job = nullptr,
+                       const uint8_t *cached_heads = nullptr) {
     const bool from_zero_ket = s->zero_ket_pending && p.kclass == QSIM_K_TILE;
     if ((s->zero_ket_pending || s->partial) && p.kclass != QSIM_K_TILE) { // only tile passes work on a partially written state
         QSIM_TRY(materialize_zero_ket(s));
@@ -525,6 +532,14 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
         const int rc = cached_ops ? launch_tile_prepared(s, geom, cached_ops, (int)p.blocks.size(), from_zero_ket, oop, zero_mask, job)
                                   : launch_tile_pass(s, p, geom, from_zero_ket, capture, oop, zero_mask, job);
         if (rc) return rc;
+        if (scope.on && s->profile >= 2) { // which kernel form each block ran through: out of the records the kernel was given
+            const size_t need = p.blocks.size();
+            const TileOp *h = s->h_ops + (s->ops_used - need); // a fresh pass: launch_tile_pass has just encoded them there
+            for (size_t k = (size_t)geom.n_scale; k < need; k++) {
+                if (!cached_ops) push_head(scope.pe.heads, h[k]);
+                else if (cached_heads) scope.pe.heads.insert(scope.pe.heads.end(), cached_heads + kHeadBytes * k, cached_heads + kHeadBytes * (k + 1));
+            }
+        }
         if (zero_mask) {
             s->support = (from_zero_ket ? 0 : s->support) | tmask;
             s->partial = (s->support & nmask) != nmask;
@@ -648,6 +663,7 @@ static int keep_plan(qsim_state *s, PlanRecorder &rec, uint64_t key, uint64_t ep
             return QSIM_OK;
         }
     }
+    for (const TileOp &t : rec.host_ops) push_head(fresh.op_heads, t); // (the records themselves live on the device only)
     fresh.key = key;
     fresh.wisdom_epoch = epoch;
     fresh.last_use = ++s->plan_clock;
@@ -699,8 +715,8 @@ class PassRouter {
   public:
     // rec: the fresh path's recorder for the plan cache, through which the passes moved in are launched (NULL: nothing is recorded)
     PassRouter(qsim_state *s, PackJob *job, PlanRecorder *rec) : s_(s), job_(job), rec_(rec), home_(s->amps), sup_(current_support(s)) {}
-    void push(Pass &&p) { std::unique_ptr<Pass> own(new Pass(std::move(p))); const Pass *at = own.get(); route({at, nullptr, nullptr, std::move(own)}); }
-    void push(const Pass &p, const TileGeom *geom, const TileOp *d_ops) { route({&p, geom, d_ops, nullptr}); } // of a cached plan: nothing is copied
+    void push(Pass &&p) { std::unique_ptr<Pass> own(new Pass(std::move(p))); const Pass *at = own.get(); route({at, nullptr, nullptr, std::move(own), nullptr}); }
+    void push(const Pass &p, const TileGeom *geom, const TileOp *d_ops, const uint8_t *heads) { route({&p, geom, d_ops, nullptr, heads}); } // of a cached plan: nothing is copied
     int finish() { // the queue has ended
         release(true);
         if (s_->amps != home_) std::swap(s_->amps, s_->spare); // only after a failed launch (rule 5)
@@ -713,6 +729,7 @@ class PassRouter {
         const TileGeom *geom;      // cached plan: the order the tile pass was launched with
         const TileOp *d_ops;       // cached plan: its TileOps on the device
         std::unique_ptr<Pass> own; // a pass the scheduler moved in
+        const uint8_t *heads = nullptr; // cached plan: the header bytes of those TileOps (CachedPlan::op_heads)
         const TileGeom &tile_geom() const { return geom ? *geom : p->geom; }
     };
     qsim_state *s_;
@@ -728,7 +745,7 @@ class PassRouter {
     void launch(Item &it, bool oop, PackJob *pj) {
         if (rc_ != QSIM_OK) return;
         if (it.own && rec_) rc_ = rec_->launch(s_, std::move(*it.own), oop, pj);
-        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj);
+        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj, it.heads);
     }
     void run_group(std::vector<Item> &grp, bool oop, PackJob *pj = nullptr) { // oop / pj: of the tile pass at its head
         for (size_t i = 0; i < grp.size(); i++) launch(grp[i], i == 0 && oop, i == 0 ? pj : nullptr);
@@ -795,7 +812,8 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
         PassRouter router(s, job, nullptr);
         for (size_t i = 0; i < pl->passes.size(); i++) {
             const bool tile = pl->passes[i].kclass == QSIM_K_TILE;
-            router.push(pl->passes[i], tile ? &pl->geoms[i] : nullptr, tile ? pl->d_ops + pl->op_first[i] : nullptr);
+            router.push(pl->passes[i], tile ? &pl->geoms[i] : nullptr, tile ? pl->d_ops + pl->op_first[i] : nullptr,
+                        tile ? pl->op_heads.data() + kHeadBytes * pl->op_first[i] : nullptr);
         }
         return router.finish();
     }

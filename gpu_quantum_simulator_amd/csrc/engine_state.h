@@ -43,8 +43,10 @@ struct ProfEvent {
     double visited;      // tile passes: fraction of the register's tiles the pass works on (the state's support)
     double read_share;   // tile passes: fraction of the register the pass reads (the slots of those tiles inside the support before it)
     std::vector<uint8_t> forms; // tile passes: one byte per block (qsim_launch_log_blocks)
+    std::vector<uint8_t> heads; // ... and five bytes per block out of the header of its encoded TileOp (qsim_launch_log_block_flags)
 };
-struct LaunchRec { int kclass, n_ops; uint64_t high_mask; double ms; uint64_t order_code; double visited, read_share; std::vector<uint8_t> forms; };
+constexpr size_t kHeadBytes = 5;
+struct LaunchRec { int kclass, n_ops; uint64_t high_mask; double ms; uint64_t order_code; double visited, read_share; std::vector<uint8_t> forms, heads; };
 
 // Everything a schedule depends on: the options that shape it, the state's support, the QSIM_SCHED_* overrides and the
 // gates themselves.  A cached plan is only replayed for a queue whose identity EQUALS the one it was built from, field by
@@ -64,6 +66,7 @@ struct CachedPlan {
     std::vector<qsim::TileGeom> geoms;   // per pass; meaningful for tile passes: the geometry in the order it was launched with
     std::vector<size_t> op_first;  // per pass: index of its first TileOp in d_ops
     qsim::TileOp *d_ops = nullptr;
+    std::vector<uint8_t> op_heads; // per TileOp of d_ops: kHeadBytes of its header (nq, terms, nsel, flags, b[7]), for the launch log
 };
 
 struct qsim_state {

@@ -1,6 +1,7 @@
 // planning.cpp — everything the engine knows by MEASUREMENT or by trying schedules, and the API that plans without running:
 // the tile-bit orders measured per pass geometry ("wisdom") with their file format, the schedule choice per circuit and its
-// hints, qsim_tune_circuit*, and the device-free planning calls (qsim_plan_circuit*, qsim_plan_passes, qsim_schedule_circuit).
+// hints, qsim_tune_circuit*, and the device-free planning calls (qsim_plan_circuit*, qsim_plan_passes, qsim_schedule_circuit,
+// qsim_tile_records).
 // The three process-wide tables and their locks are private to this file; engine.cpp reaches them through order_tile_bits,
 // apply_sched_hint, have_sched_hints and wisdom_epoch (engine_state.h).  Calls the scheduler and, for the timed runs of the
 // tuning, the engine's own entry points (qsim_run_circuit, qsim_flush, launch_tile_pass).
@@ -681,6 +682,38 @@ extern "C" int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_b
             for (int a = 0; a < blk.nq; a++) qs[j++] = blk.q[a];
             static const int kinds[9] = {0, QSIM_GATE_U1, QSIM_GATE_U2, QSIM_GATE_U3, QSIM_GATE_U4, QSIM_GATE_U5, QSIM_GATE_U6, QSIM_GATE_U7, QSIM_GATE_U8};
             cb(user, pi, p.kclass, kinds[nq], qs, nq, big.data(), (int)blk.gates);
+        }
+        pi++;
+    }
+    return QSIM_OK;
+}
+
+// The same schedule as the records k_tile would read: every block of every tile pass (the TOP_SCALE factors included) encoded by
+// to_tile_op under the pass's geometry, with that geometry, the block's qubits and its matrix beside it.  order_seed != 0: the
+// high tile bits of every pass are shuffled first (seeded by it and the pass index), as the engine may reorder them
+// (order_tile_bits) — the record then speaks about other tile-local bits while the block stays the same.  What a host-side model
+// of the record contract is checked against (tests/tile_record_ref.py).
+extern "C" int qsim_tile_records(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, int f32, uint64_t order_seed,
+                                 qsim_tile_record_cb cb, void *user) {
+    if (!c || !cb) return fail(QSIM_ERR_ARG, "NULL argument");
+    if (fuse < 0 || fuse > 3) return fail(QSIM_ERR_ARG, "fuse level %d not in 0..3", fuse);
+    const std::vector<Pass> passes = schedule(engine_sched_config(c->num_q, fuse, tile_bits, tile_low_bits, tile_max_ops), queue_of(c));
+    int pi = 0;
+    std::vector<double> big((size_t)2 * 256 * 256);
+    std::vector<cd> full((size_t)256 * 256);
+    std::vector<TileOp> rec(1);
+    for (const Pass &p : passes) {
+        if (p.kclass == QSIM_K_TILE) {
+            TileGeom g = p.geom;
+            if (order_seed) shuffle_high(g, 0x9E3779B97F4A7C15ULL * (order_seed + 1) + 0xD1B54A32D192ED03ULL * (uint64_t)(pi + 1));
+            for (const TileBlock &blk : p.blocks) {
+                if (!to_tile_op(g, blk, rec[0], f32 != 0)) return fail(QSIM_ERR_ARG, "internal: block does not fit its tile pass");
+                const int D = 1 << (blk.ns + blk.nq);
+                blk.full_matrix(full.data());
+                for (int k = 0; k < D * D; k++) { big[2 * k] = full[k].real(); big[2 * k + 1] = full[k].imag(); }
+                const int geom[3] = {g.tile_bits, g.low_bits, g.n_high};
+                cb(user, pi, geom, g.high, blk.s, blk.ns, blk.q, blk.nq, big.data(), &rec[0], (long)sizeof(TileOp));
+            }
         }
         pi++;
     }

@@ -1,5 +1,6 @@
 // profile.cpp — the profiling events recorded around launches (LaunchScope, engine_state.h), the statistics and the launch log
 // they resolve into, and the accessors of both.  Touches qsim_state's stats, events and launch_log only.
+#include <algorithm>
 #include <cstring>
 
 #include "engine_state.h"
@@ -24,7 +25,7 @@ static int resolve_events(qsim_state *s) {
     for (auto &pe : s->events) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, pe.start, pe.stop) == hipSuccess) s->stats.k_ms[pe.kclass] += ms;
-        if (s->launch_log.size() < (1u << 20)) s->launch_log.push_back({pe.kclass, pe.n_ops, pe.high_mask, (double)ms, pe.order_code, pe.visited, pe.read_share, std::move(pe.forms)});
+        if (s->launch_log.size() < (1u << 20)) s->launch_log.push_back({pe.kclass, pe.n_ops, pe.high_mask, (double)ms, pe.order_code, pe.visited, pe.read_share, std::move(pe.forms), std::move(pe.heads)});
         s->event_pool.push_back(pe.start);
         s->event_pool.push_back(pe.stop);
     }
@@ -87,6 +88,16 @@ extern "C" int qsim_launch_log_blocks(qsim_state *s, long index, uint8_t *codes,
     const std::vector<uint8_t> &f = rec->forms;
     *count = (int)f.size();
     for (int j = 0; codes && j < cap && j < (int)f.size(); j++) codes[j] = f[j];
+    return QSIM_OK;
+}
+
+extern "C" int qsim_launch_log_block_flags(qsim_state *s, long index, uint8_t *codes, int cap, int *count) {
+    int err = QSIM_ERR_ARG;
+    const LaunchRec *rec = count ? log_record(s, index, err) : nullptr;
+    if (!rec) return err;
+    const std::vector<uint8_t> &f = rec->heads;
+    *count = (int)(f.size() / kHeadBytes);
+    for (size_t j = 0; codes && j < kHeadBytes * (size_t)std::max(cap, 0) && j < f.size(); j++) codes[j] = f[j];
     return QSIM_OK;
 }
 

@@ -137,6 +137,25 @@ class Circuit:
                                                 _lib.SCHED_CB(cb), None))
         return out
 
+    def tile_records(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, f32: bool = False,
+                     order_seed: int = 0) -> list:
+        """qsim_tile_records: every block of every tile pass of the schedule() with the same arguments, as a dict: pass,
+        tile_bits, low_bits, high (global bit of each high tile-local bit, in order), selectors and qubits (most significant
+        first), matrix (on selectors + qubits) and record, the encoded TileOp as bytes.  order_seed != 0 shuffles each pass's
+        high bits before encoding.  Host only."""
+        out = []
+
+        def cb(_user, pass_i, geom, high, sel, nsel, tq, nq, U, record, nbytes):
+            d = 1 << (nsel + nq)
+            out.append({"pass": pass_i, "tile_bits": geom[0], "low_bits": geom[1], "high": tuple(high[j] for j in range(geom[2])),
+                        "selectors": tuple(sel[a] for a in range(nsel)), "qubits": tuple(tq[a] for a in range(nq)),
+                        "matrix": np.ctypeslib.as_array(U, shape=(2 * d * d,)).copy().view(np.complex128).reshape(d, d),
+                        "record": ctypes.string_at(record, nbytes)})
+
+        check(_lib.load().qsim_tile_records(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, int(bool(f32)), order_seed,
+                                            _lib.TILE_RECORD_CB(cb), None))
+        return out
+
     def close(self) -> None:
         if self._h:
             _lib.load().qsim_circuit_free(self._h)
@@ -540,6 +559,20 @@ class Simulator(_PauliStrings):
             codes, cnt = (c_ubyte * 64)(), c_int()
             check(lib.qsim_launch_log_blocks(self._h, i, codes, 64, byref(cnt)))
             out.append([(1 << (codes[j] & 3), (codes[j] >> 2) & 7, bool(codes[j] & 32), codes[j] >> 6) for j in range(min(cnt.value, 64))])
+        return out
+
+    def launch_log_block_flags(self) -> list:
+        """Per launch since reset_stats: [(nq, terms, nsel, flags, info)] of a tile pass's blocks ([] for other kernels), read from
+        the headers of the records the kernel was given — nq after padding, entries per row, selector qubits, TileOp::flags and
+        b[7] (qsim_launch_log_block_flags; profile = 2)."""
+        from ctypes import c_ubyte
+        lib = _lib.load()
+        n = lib.qsim_launch_log(self._h, -1, None, None, None, None)
+        out = []
+        for i in range(max(n, 0)):
+            codes, cnt = (c_ubyte * (5 * 64))(), c_int()
+            check(lib.qsim_launch_log_block_flags(self._h, i, codes, 64, byref(cnt)))
+            out.append([tuple(codes[5 * j + k] for k in range(5)) for j in range(min(cnt.value, 64))])
         return out
 
     def reset_stats(self) -> None:

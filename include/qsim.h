@@ -515,6 +515,12 @@ int qsim_launch_log_read_share(qsim_state *s, long index, double *read_share);
  * at least half of its rows are identity rows, bits 6-7 its selector qubits outside the tile.  Recorded under QSIM_OPT_PROFILE = 2
  * only (host work per launch).  Data for the pass-time model. */
 int qsim_launch_log_blocks(qsim_state *s, long index, uint8_t *codes, int cap, int *count);
+/* ... and which form of the tile kernel each of those blocks ran through, five bytes per block in the same order, copied from the
+ * header of the record the kernel was given (csrc/qsim_internal.h TileOp; a cached plan keeps these bytes of its records beside
+ * them, so a replayed pass reports what its first run encoded): nq (tile qubits after padding), terms (entries per row), nsel, flags and b[7] (the bits the kernel branches
+ * on: log2 of terms, skipped classes, barrier between reads and writes).  codes needs room for 5 * cap bytes; *count = blocks.
+ * Recorded under QSIM_OPT_PROFILE = 2 only. */
+int qsim_launch_log_block_flags(qsim_state *s, long index, uint8_t *codes, int cap, int *count);
 
 /* ---- circuits: the tokenizer of compute_state_vector (quantum_simulator.c:115-254) ---------------- */
 /* Parses the OPENQASM-3 subset of quantum_simulator.c (two header statements, `qubit[n] q;` or
@@ -567,6 +573,17 @@ typedef void (*qsim_sched_cb)(void *user, int pass, int kernel_class, int kind, 
                               const double *U, int gates_folded);
 int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                           qsim_sched_cb cb, void *user);
+/* The same schedule (same arguments) as the records the tile kernel reads: `cb` is called for every block of every tile pass,
+ * the tile-uniform factors included, with the pass, the geometry the record was encoded under (geom[0..2] = tile bits B, low
+ * bits L, number of high bits; high[j] = global bit of tile-local bit L+j, IN ORDER), the block's qubits outside the tile
+ * (selectors) and inside it (both most significant first), its matrix on (selectors..., tile qubits...) as
+ * qsim_schedule_circuit reports it, and the encoded record itself (record_bytes bytes; layout: csrc/qsim_internal.h TileOp).
+ * f32 != 0: the records of an fp32 state.  order_seed != 0: every pass's high bits are shuffled (seeded) before encoding, as
+ * the engine may reorder them.  Host code, no device: lets a CPU test interpret the records (tests/tile_record_ref.py). */
+typedef void (*qsim_tile_record_cb)(void *user, int pass, const int *geom, const int *high, const int *selectors, int nsel,
+                                    const int *tile_qubits, int nq, const double *U, const void *record, long record_bytes);
+int qsim_tile_records(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, int f32, uint64_t order_seed,
+                      qsim_tile_record_cb cb, void *user);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ import pytest
 from gpu_quantum_simulator_amd import Circuit, Simulator, circuits, gate_matrix, run_qasm
 from gpu_quantum_simulator_amd import _lib
 from helpers import np_apply_1q, np_apply_2q, np_apply_cx, random_unitary
+from tile_forms_ref import CACHE_BLOCKED_CIRCUITS  # (data: the CPU test of the tile records reads the same list)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10  # north_star: "amplitudes within 1e-10 abs for fp64"
@@ -114,16 +115,7 @@ def test_dense_2q_every_pair():
         assert k["gate2"]["launches"] == 15 and k["tile"]["launches"] == 66 - 15
 
 
-@pytest.mark.parametrize("n,depth,seed,vocab,opts", [
-    (14, 400, 21, "all", {}),
-    (16, 600, 22, "clifford_t", {}),
-    (17, 500, 23, "all", {"tile_bits": 10, "tile_low_bits": 6}),
-    (18, 500, 24, "all", {"tile_bits": 13, "tile_low_bits": 6}),
-    (20, 300, 25, "all", {"tile_bits": 11, "tile_low_bits": 5, "tile_max_ops": 3}),
-    (19, 400, 27, "all", {"tile_bits": 9, "tile_low_bits": 2}),
-    (15, 400, 28, "clifford_t", {"tile_bits": 8, "tile_low_bits": 6}),
-    (20, 300, 26, "all", {"grid_cap": 64}),
-])
+@pytest.mark.parametrize("n,depth,seed,vocab,opts", CACHE_BLOCKED_CIRCUITS)
 def test_random_circuits_cache_blocked(oracle, tmp_path, n, depth, seed, vocab, opts):
     path = circuits.random_circuit_file(str(tmp_path / "c.qasm"), n, depth, seed, vocab)
     _, want, _, _ = oracle.run_qasm(path)
@@ -653,7 +645,7 @@ def _perm_phase(rng, dim):
 
 @pytest.mark.parametrize("qubits", [(13, 9, 4), (12, 5, 0), (2, 1, 0), (13, 12, 11), (7, 3, 2), (10, 6, 1)])
 def test_sparse_block_forms_in_tile_passes(qubits):
-    """Every TOP_SP form (2 and 3 qubits; 1, 2 and 4 entries per row; identity rows) on low, mixed and high
+    """Every TOP_PART form at K = 3 (blocks on 2 and 3 qubits; 1, 2 and 4 entries per row; identity rows) on low, mixed and high
     tile-local bits: two-qubit gates with exact-zero structure on overlapping pairs are merged by the scheduler
     into sparse 3-qubit blocks, replayed here with numpy."""
     from helpers import np_apply_kq
