@@ -103,6 +103,10 @@ SIGNATURES = {
     "qsim_pauli_gradient": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, _DP, _DP]),
     "qsim_pauli_sum_into": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, c_void_p]),
     "qsim_pauli_gradient_plan": (c_int, [POINTER(c_uint64), c_long, POINTER(c_uint64), c_long, POINTER(c_long), POINTER(c_long)]),
+    "qsim_controlled_pauli_gradient": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, POINTER(c_uint64), POINTER(c_uint64),
+                                               _DP, c_long, _DP, _DP]),
+    "qsim_controlled_gradient_plan": (c_int, [POINTER(c_uint64), POINTER(c_uint64), c_long, POINTER(c_uint64), c_long, c_int, c_int, POINTER(c_long),
+                                              POINTER(c_long), POINTER(c_uint64)]),
     "qsim_pauli_adjoint_sweeps_launched": (c_uint64, []),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),

@@ -21,16 +21,6 @@ namespace {
 
 constexpr int KT = kMaxPauliTermsPerSweep;
 
-// unit-index bits -> their places in the (even) amplitude index, the fixed bits left zero
-template <typename R>
-__device__ __forceinline__ uint64_t spread(const CtrlGeom &g, uint64_t t) {
-    for (uint64_t f = g.zeros; f != 0; f &= f - 1ULL) { // uniform: the positions come off a scalar register, lowest first
-        const uint64_t low = (f & (0ULL - f)) - 1ULL;
-        t = ((t & ~low) << 1) | (t & low);
-    }
-    return t << (sizeof(R) == 8 ? 0 : 1);
-}
-
 template <typename R, bool PAIRED>
 __global__ __launch_bounds__(kTPB) void k_pauli_crot(R *a, CtrlGeom g, RotTerms<R, KT> terms) {
     using V = typename Vec16<R>::type;

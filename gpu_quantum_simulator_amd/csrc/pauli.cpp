@@ -1,7 +1,7 @@
 // pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values"),
 // rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations"), the same under control qubits
 // (crot.hip; DESIGN "Controlled Pauli rotations") and adjoint-mode gradients of
-// <H> with respect to the angles (adjoint.hip; DESIGN "Adjoint gradients").  pauli_sweep.h has what the sweeps share.  Every
+// <H> with respect to the angles (adjoint.hip, and cadjoint.hip through controlled rotations; DESIGN "Adjoint gradients").  pauli_sweep.h has what the sweeps share.  Every
 // entry point opens with settle() and then only touches qsim_state's buffer, stream and d_expect; expectation values read the
 // buffer, rotations write it, a gradient call writes it and a second buffer of the same size (the spare one, or d_adjoint) and
 // leaves the state as it found it.
@@ -346,12 +346,14 @@ extern "C" int qsim_controlled_rotation_plan(const uint64_t *c_masks, const uint
 static std::atomic<uint64_t> g_adjoint_sweeps{0};
 extern "C" uint64_t qsim_pauli_adjoint_sweeps_launched(void) { return g_adjoint_sweeps.load(); }
 
-// The backward sweeps in FORWARD order: maximal runs of consecutive equal x, cut into pieces of K.  Every term, single X and Y too.
-static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *X, long num) {
+// The backward sweeps in FORWARD order: maximal runs of consecutive equal x and equal control mask (C may be NULL: no controls
+// anywhere), cut into pieces of K.  Every term, single X and Y too.
+static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *C, const uint64_t *X, long num) {
     std::vector<std::pair<long, int>> out;
+    auto c = [&](long t) { return C ? C[t] : 0; };
     for (long t = 0; t < num;) {
         long e = t + 1;
-        while (e < num && X[e] == X[t]) e++;
+        while (e < num && X[e] == X[t] && c(e) == c(t)) e++;
         for (; t < e; t += kPauliRotationsPerSweep) out.emplace_back(t, (int)std::min<long>(kPauliRotationsPerSweep, e - t));
         t = e;
     }
@@ -361,8 +363,30 @@ static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *X, long 
 extern "C" int qsim_pauli_gradient_plan(const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, long *adjoint_sweeps, long *sum_sweeps) {
     if (num_rot < 0 || num_ham < 0) return fail(QSIM_ERR_ARG, "qsim_pauli_gradient_plan: negative term count");
     if (!adjoint_sweeps || !sum_sweeps || (num_rot > 0 && !rot_x) || (num_ham > 0 && !ham_x)) return fail(QSIM_ERR_ARG, "qsim_pauli_gradient_plan: NULL argument");
-    *adjoint_sweeps = (long)adjoint_pieces(rot_x, num_rot).size();
+    *adjoint_sweeps = (long)adjoint_pieces(nullptr, rot_x, num_rot).size();
     *sum_sweeps = (long)pauli_sweeps(ham_x, ~0ULL, num_ham).sweeps.size();
+    return QSIM_OK;
+}
+
+extern "C" int qsim_controlled_gradient_plan(const uint64_t *rot_c, const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, int num_q,
+                                             int precision_bits, long *adjoint_sweeps, long *sum_sweeps, uint64_t *units_visited) {
+    const char *who = "qsim_controlled_gradient_plan";
+    if (!adjoint_sweeps || !sum_sweeps || !units_visited) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
+    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    // the plan knows no z: x stands in for it, so a control that meets x is refused here and one that meets z by the call itself
+    QSIM_TRY(check_pauli_terms(fail, who, num_q, rot_x, rot_x, rot_x, nullptr, num_rot));
+    QSIM_TRY(check_pauli_terms(fail, who, num_q, ham_x, ham_x, ham_x, nullptr, num_ham));
+    QSIM_TRY(check_controls(who, num_q, rot_c, rot_x, rot_x, num_rot));
+    const bool f32 = precision_bits == 32;
+    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(rot_c, rot_x, num_rot);
+    *adjoint_sweeps = (long)pieces.size();
+    *sum_sweeps = (long)pauli_sweeps(ham_x, ~0ULL, num_ham).sweeps.size();
+    *units_visited = 0;
+    for (const std::pair<long, int> &piece : pieces) { // one unit index addresses psi and lambda
+        const uint64_t c = rot_c ? rot_c[piece.first] : 0, x = rot_x[piece.first];
+        *units_visited += c ? ctrl_geom(c, x, f32, num_q).units : sweep_geom(x, false, f32, num_q).units;
+    }
     return QSIM_OK;
 }
 
@@ -400,10 +424,9 @@ extern "C" int qsim_pauli_sum_into(qsim_state *s, const uint64_t *x_masks, const
     return pauli_sum_sweeps(s, x_masks, z_masks, coeffs, num_terms, dst_device);
 }
 
-extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot,
-                                   const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad) {
-    QSIM_TRY(check_terms("qsim_pauli_gradient", s, rot_x, rot_z, thetas, thetas, num_rot));
-    QSIM_TRY(check_terms("qsim_pauli_gradient", s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
+// checked arguments; C may be NULL: no controls anywhere
+static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot, const uint64_t *ham_x,
+                    const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad) {
     if (energy) *energy = 0.0;
     if (grad) std::fill(grad, grad + num_rot, 0.0);
     if (qsim_holds_nothing(s)) return QSIM_OK; // the zero vector: energy 0, gradient 0, no sweep
@@ -417,12 +440,12 @@ extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const u
     }
     QSIM_TRY(alloc_result_rows(s));
 
-    QSIM_TRY(qsim_apply_pauli_rotations(s, rot_x, rot_z, thetas, num_rot));
+    QSIM_TRY(apply_rotations(s, C, rot_x, rot_z, thetas, num_rot));
     QSIM_TRY(settle(s));
     QSIM_TRY(pauli_sum_sweeps(s, ham_x, ham_z, coeffs, num_ham, lam));
 
     // row 0: the energy, Re <lambda|psi>, as one paired expectation sweep over the two buffers; then the pieces, last first
-    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(rot_x, num_rot);
+    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(C, rot_x, num_rot);
     const LaunchCfg cfg{s->stream, s->grid_cap};
     return sweep_result_rows(
         s, 1 + pieces.size(),
@@ -434,8 +457,10 @@ extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const u
                 return launched("expectation", launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row));
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
+            const uint64_t c = C ? C[piece.first] : 0;
             const RotSweep sw = rot_sweep(rot_x[piece.first], rot_z + piece.first, thetas + piece.first, piece.second, -1.0 /* U^+ */, 0, index_mask(s->n), s->n);
-            QSIM_TRY(launched("adjoint", launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row)));
+            if (c) QSIM_TRY(launched("controlled adjoint", launch_pauli_cadjoint(cfg, s->amps, lam, s->f32, s->n, c, sw, s->d_expect, d_row)));
+            else QSIM_TRY(launched("adjoint", launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row)));
             g_adjoint_sweeps++;
             return QSIM_OK;
         },
@@ -449,4 +474,23 @@ extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const u
             for (int k = 0; grad && k < piece.second; k++)
                 grad[piece.first + k] = pauli_phase(__builtin_popcountll(rot_x[piece.first] & rot_z[piece.first + k])) * row[k];
         });
+}
+
+extern "C" int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot,
+                                   const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad) {
+    QSIM_TRY(check_terms("qsim_pauli_gradient", s, rot_x, rot_z, thetas, thetas, num_rot));
+    QSIM_TRY(check_terms("qsim_pauli_gradient", s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
+    return gradient(s, nullptr, rot_x, rot_z, thetas, num_rot, ham_x, ham_z, coeffs, num_ham, energy, grad);
+}
+
+// The same through controlled rotations (cadjoint.hip; DESIGN "Adjoint gradients under controls"): dE/dtheta_k = Im <lambda_k|Pi_k P_k|psi_k>,
+// the pair bracket inside the control subspace, where alone U_k^+ steps psi and lambda back.
+extern "C" int qsim_controlled_pauli_gradient(qsim_state *s, const uint64_t *rot_c, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas,
+                                              long num_rot, const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy,
+                                              double *grad) {
+    const char *who = "qsim_controlled_pauli_gradient";
+    QSIM_TRY(check_terms(who, s, rot_x, rot_z, thetas, thetas, num_rot));
+    QSIM_TRY(check_terms(who, s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
+    QSIM_TRY(check_controls(who, s->n, rot_c, rot_x, rot_z, num_rot));
+    return gradient(s, rot_c, rot_x, rot_z, thetas, num_rot, ham_x, ham_z, coeffs, num_ham, energy, grad);
 }

@@ -1,6 +1,7 @@
 // pauli_sweep.h — how a Pauli sweep walks a state: what expect.hip (<psi|P|psi>, read-only), evolve.hip (exp(-i theta/2 P), in
 // place), adjoint.hip (dE/dtheta: the backward sweep over psi and lambda, and lambda = H psi), crot.hip (the rotation under control
-// qubits: CtrlGeom below) and their host side pauli.cpp share.  DESIGN §7b opens with the same account.
+// qubits: CtrlGeom below), cadjoint.hip (the backward sweep under control qubits) and their host side pauli.cpp share.  DESIGN §7b
+// opens with the same account.
 //
 // A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
 // pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets
@@ -73,6 +74,12 @@ hipError_t launch_pauli_crot(const LaunchCfg &cfg, void *a, bool f32, int n, uin
 // (-1)^ny conj(lambda_j) psi_(j^x)]  (x == 0: sum_j s_k(j) Im conj(lambda_j) psi_j), then term k's 2x2 — c and v as for
 // launch_pauli_rot, of MINUS theta_k — on psi and on lambda.  k < expect_slots(count); d_partial as for launch_expect.
 hipError_t launch_pauli_adjoint(const LaunchCfg &cfg, void *psi, void *lam, bool f32, int n, const RotSweep &sw, double *d_partial, double *d_out);
+// The same backward sweep on the indices whose bits of `controls` are all 1 and nowhere else (cadjoint.hip): the sums
+// run over the pairs inside the control subspace, and psi and lambda are stepped back only there.  sw.full is refused, controls != 0,
+// inside the buffer and disjoint from sw.x — and from every sw.z: a z bit on a control qubit would be a sign of the sum as well as of
+// v, and no caller sends one, so it is refused, not folded.
+hipError_t launch_pauli_cadjoint(const LaunchCfg &cfg, void *psi, void *lam, bool f32, int n, uint64_t controls, const RotSweep &sw, double *d_partial,
+                                 double *d_out);
 // Term k of a sum of strings with one x: c = coefficient times the non-zero component of i^ny times (-1)^ny; bit k of odd_mask: ny
 // is odd, the term belongs to the imaginary part of the weight.
 struct SumSweep : PauliSweep {
@@ -131,7 +138,7 @@ inline SweepGeom sweep_geom(uint64_t x, bool full, bool f32, int n) {
     return g;
 }
 
-// A sweep under controls (k_pauli_crot) visits the indices with every control bit 1 and, for x != 0, the highest bit h of x clear:
+// A sweep under controls (k_pauli_crot, k_pauli_cadjoint) visits the indices with every control bit 1 and, for x != 0, the highest bit h of x clear:
 // 2^-c of what sweep_geom visits.  A unit index is expanded by inserting one fixed bit per set bit of `zeros` — the list of
 // insertion positions in the unit index, as a bit set, taken lowest first (each insertion leaves the bits below its position and the
 // bits inserted before it where they are).  Every inserted bit is a zero, so the expansion stays linear over OR, and the control
@@ -182,7 +189,7 @@ int resident_grid() {
     return grid;
 }
 
-// The grid of a sweep that REDUCES (k_expect, k_pauli_adjoint): the resident grid, at most kExpectGrid workgroups because the
+// The grid of a sweep that REDUCES (k_expect, k_pauli_adjoint, k_pauli_cadjoint): the resident grid, at most kExpectGrid workgroups because the
 // partial-sum buffer has that many rows, whatever LaunchCfg::grid_cap says — the sums are added row by row, so their bits depend on
 // the grid, and equal calls must return equal bits whatever the option says.  (k_pauli_adjoint writes amplitudes too; each is
 // written by one thread and would not care.)  The 32-slot instantiations of k_expect hold 3 workgroups per CU, the others 4 and more.
@@ -227,7 +234,8 @@ hipError_t for_term_slots(int count, F &&f) {
 
 // ---- term records: what a kernel gets of a RotSweep or SumSweep, by value (scalar loads) -------------------------------------------
 static_assert(kMaxPauliTermsPerSweep <= 32, "one bit per term in a record's `odd` and in a thread's parity mask");
-// k_pauli_rot (KT = kMaxPauliTermsPerSweep, terms of +theta) and k_pauli_adjoint (KT = expect_slots(count), terms of -theta)
+// k_pauli_rot, k_pauli_crot (KT = kMaxPauliTermsPerSweep, terms of +theta) and k_pauli_adjoint, k_pauli_cadjoint (KT =
+// expect_slots(count), terms of -theta)
 template <typename R, int KT>
 struct RotTerms {
     uint64_t z[KT];     // unused slots: 0
@@ -265,6 +273,16 @@ __device__ __forceinline__ float flip(float v, uint32_t sign_bit31) { return __u
 template <typename R>
 __device__ __forceinline__ uint64_t expand(const SweepGeom &g, uint64_t t) {
     return (((t & ~g.low) << 1) | (t & g.low)) << (sizeof(R) == 8 ? 0 : 1);
+}
+// the same under controls (k_pauli_crot, k_pauli_cadjoint): unit-index bits -> their places in the (even) amplitude index, the fixed
+// bits left zero
+template <typename R>
+__device__ __forceinline__ uint64_t spread(const CtrlGeom &g, uint64_t t) {
+    for (uint64_t f = g.zeros; f != 0; f &= f - 1ULL) { // uniform: the positions come off a scalar register, lowest first
+        const uint64_t low = (f & (0ULL - f)) - 1ULL;
+        t = ((t & ~low) << 1) | (t & low);
+    }
+    return t << (sizeof(R) == 8 ? 0 : 1);
 }
 // the unit that holds amplitude `amp` (even for fp32)
 template <typename R>

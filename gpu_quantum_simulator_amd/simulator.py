@@ -321,11 +321,22 @@ class Simulator(_PauliStrings):
         """(E, grad): E = <psi|H|psi> after the rotations and grad[k] = dE/dtheta_k, for `rotations` as apply_pauli_rotations
         takes them and H = `terms` as expectation takes them, real coefficients (ValueError for a complex one).  Adjoint
         differentiation on the device (qsim_pauli_gradient): one forward pass, one application of H, one backward pass.  The
-        state is left as the call found it, to rounding."""
-        rxs, rzs, thetas, rxp, rzp, tp = _rotation_arrays(rotations, self.num_qubits)
+        state is left as the call found it, to rounding.
+        Entries may be (theta, string, controls), mixed with plain ones, as apply_pauli_rotations takes them, with the same
+        ValueErrors (qsim_controlled_pauli_gradient): the derivative with respect to the angle of a controlled rotation, which the
+        two-term shift rule gets wrong; its backward sweep touches 2^-c of the state and of lambda for c controls."""
+        pairs, controls = _split_controls(rotations)
+        rxs, rzs, thetas, rxp, rzp, tp = _rotation_arrays(pairs, self.num_qubits)
         hxs, hzs, coeffs, hxp, hzp, cp = _hamiltonian_arrays(terms, self.num_qubits)
         energy, grad = c_double(0.0), np.zeros(rxs.size, dtype=np.float64)
-        check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
+        if any(controls):
+            from ctypes import c_uint64
+            from .pauli import control_mask
+            cs = np.array([control_mask(c, self.num_qubits, text) for (_, text), c in zip(pairs, controls)], dtype=np.uint64)
+            check(_lib.load().qsim_controlled_pauli_gradient(self._h, cs.ctypes.data_as(ctypes.POINTER(c_uint64)), rxp, rzp, tp, rxs.size, hxp, hzp, cp,
+                                                             hxs.size, byref(energy), _dp(grad)))
+        else:
+            check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
         return float(energy.value), grad
 
     # -- controlled rotations (single states only)

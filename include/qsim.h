@@ -205,8 +205,9 @@ int qsim_pauli_rotations_per_sweep(void); /* K: 32, the one-bit-per-term masks' 
  * num_terms == 0 does nothing, a lazily held |0...0> or a partial state is settled first and the support is dense afterwards.
  * QSIM_ERR_ARG, with the state unchanged: everything qsim_apply_pauli_rotations refuses, a control bit at or above the register's
  * qubit count, and a control mask that overlaps the term's x_mask | z_mask (a control qubit carries a Pauli factor).
- * Out of scope: controls in qsim_pauli_gradient, controls on clusters or shards (no qsim_cluster_* counterpart), controlled terms
- * in product formulas (Simulator.evolve), and a QASM spelling — the parser's grammar is the reference's. */
+ * Gradients through controlled terms: qsim_controlled_pauli_gradient below.
+ * Out of scope: controls on clusters or shards (no qsim_cluster_* counterpart), controlled terms in product formulas
+ * (Simulator.evolve), and a QASM spelling — the parser's grammar is the reference's. */
 int qsim_apply_controlled_pauli_rotations(qsim_state *s, const uint64_t *c_masks, const uint64_t *x_masks, const uint64_t *z_masks,
                                           const double *thetas, long num_terms);
 /* Host only, no device: what the call above does with these terms on a register of num_q qubits held in precision_bits (64 or 32)
@@ -245,6 +246,36 @@ int qsim_pauli_gradient(qsim_state *s, const uint64_t *rot_x, const uint64_t *ro
 int qsim_pauli_sum_into(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *coeffs, long num_terms, void *dst_device);
 /* Host only: sweeps the gradient call makes after its forward pass. */
 int qsim_pauli_gradient_plan(const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, long *adjoint_sweeps, long *sum_sweeps);
+/* ---- adjoint-mode gradients through controlled Pauli rotations (new) ----
+ * qsim_pauli_gradient with a control mask per rotation: U_k = (1 - Pi_k) + Pi_k exp(-i thetas[k]/2 P_k), Pi_k the projector on
+ * "every qubit of rot_c[k] is 1" (qsim_apply_controlled_pauli_rotations' terms).  dU_k/dtheta_k = -(i/2) Pi_k P_k U_k, so
+ * grad[k] = Im <lambda_k| Pi_k P_k |psi_k>: the pair sums of qsim_pauli_gradient taken inside the control subspace only.  The generator
+ * Pi P / 2 has the eigenvalues 0 and +-1/2, so the two-term shift rule gives a WRONG derivative for a controlled term and the exact
+ * rule needs four circuit executions per parameter; this call needs one forward and one backward pass for all of them.
+ * rot_c == NULL: no controls anywhere — qsim_pauli_gradient is this call with NULL, and a call without any control returns the bits
+ * that call returns for energy, gradient and state.
+ * Forward: the routing of qsim_apply_controlled_pauli_rotations (one control on a single X or Y through the gate queue as its 4x4).
+ * Backward: EVERY term goes through a sweep; the pieces are maximal runs of consecutive equal x_mask AND equal control mask, cut into
+ * qsim_pauli_rotations_per_sweep(), last first.  A piece without controls is qsim_pauli_gradient's sweep; a piece with c controls
+ * reads and writes the 2^-c of psi and of lambda that the subspace holds and leaves every other amplitude's bits alone.  Both count in
+ * qsim_pauli_adjoint_sweeps_launched().
+ * Everything else is as qsim_pauli_gradient promises: where lambda lives, allocation before the state is touched (QSIM_ERR_ALLOC),
+ * fp64 sums in a fixed order (equal calls return equal bits, QSIM_OPT_GRID_CAP does not apply), 128 result rows per copy, the state
+ * left as found to rounding, energy or grad may be NULL, num_rot == 0 gives the energy alone, a shard that holds nothing gives energy
+ * 0, zero gradient and no sweep, a lazily held |0...0> is settled first.
+ * QSIM_ERR_ARG, with the state unchanged: whatever qsim_pauli_gradient or qsim_apply_controlled_pauli_rotations refuses — a control bit
+ * at or above the register's qubit count and a control mask that overlaps the term's x_mask | z_mask included.
+ * Single states only, fp64 and fp32. */
+int qsim_controlled_pauli_gradient(qsim_state *s, const uint64_t *rot_c, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas,
+                                   long num_rot, const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy,
+                                   double *grad);
+/* Host only, no device: the sweeps the call above makes after its forward pass on a register of num_q qubits held in precision_bits
+ * (64 or 32), and units_visited: the sum over the BACKWARD sweeps of the 16-byte units the sweep's loop visits, from the geometry
+ * function its launcher uses — multiplied by nothing: one unit index addresses psi and lambda.  Without controls (rot_c NULL or all
+ * zero) the first two are qsim_pauli_gradient_plan's.  The plan knows no z_mask: a control that meets the term's x_mask is refused
+ * here, one that meets its z_mask by the call itself.  Otherwise QSIM_ERR_ARG as for qsim_controlled_rotation_plan. */
+int qsim_controlled_gradient_plan(const uint64_t *rot_c, const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, int num_q,
+                                  int precision_bits, long *adjoint_sweeps, long *sum_sweeps, uint64_t *units_visited);
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
@@ -494,7 +525,7 @@ int qsim_reset_stats(qsim_state *s);
  * cluster's) launched by this process so far.  One process-wide counter for all states and shards together, which qsim_stats
  * does not have and qsim_reset_stats does not clear: take differences, and only where one thread applies rotations. */
 uint64_t qsim_pauli_rotation_sweeps_launched(void);
-uint64_t qsim_pauli_adjoint_sweeps_launched(void); /* the same for the backward sweeps of qsim_pauli_gradient */
+uint64_t qsim_pauli_adjoint_sweeps_launched(void); /* the same for the backward sweeps of qsim_pauli_gradient and qsim_controlled_pauli_gradient */
 /* Per-launch record (QSIM_OPT_PROFILE=1) since the last qsim_reset_stats: returns the number of records and,
  * for 0 <= index < count, fills the kernel class, the fused blocks in that launch, the tile's high-qubit
  * mask and the HIP-event time. */
