@@ -8,6 +8,8 @@
 //                                                                           (controlled ones too) and adjoint gradients (the host
 //                                                                           side of expect.hip, evolve.hip, crot.hip and
 //                                                                           adjoint.hip; pauli_sweep.h)
+//   state_algebra.cpp  calls on several states: copy, inner product, linear combination (the host side of combine.hip)
+//   lanczos.cpp        the Lanczos ground-state solver on top of pauli.cpp's H application and the two above
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 
@@ -198,6 +200,13 @@ void apply_sched_hint(uint64_t key, SchedConfig &cfg); // the schedule choice re
 
 // ---- profile.cpp -----------------------------------------------------------------------------------------------------------
 hipEvent_t take_event(qsim_state *s);
+
+// ---- state_algebra.cpp (also used by lanczos.cpp) ----------------------------------------------------------------------------
+// s->d_expect, allocated on first use: the partial sums of a reducing sweep, then result rows (pauli.cpp allocates the same).
+int alloc_sweep_scratch(qsim_state *s);
+double *sweep_result_row(qsim_state *s); // where the calls of these two files have a sweep leave its sums: the first result row
+// out[0..count) = the first `count` sums of that row; waits for the state's stream
+int fetch_sweep_results(qsim_state *s, int count, double *out);
 
 } // namespace qsim
 

@@ -391,7 +391,7 @@ extern "C" int qsim_controlled_gradient_plan(const uint64_t *rot_c, const uint64
 }
 
 // dst = sum_t C[t] Q_t |state> for a settled state and checked arguments: one sweep per piece of an x group, the first stores.
-static int pauli_sum_sweeps(qsim_state *s, const uint64_t *X, const uint64_t *Z, const double *C, long num, void *dst) {
+int qsim::pauli_sum_sweeps(qsim_state *s, const uint64_t *X, const uint64_t *Z, const double *C, long num, void *dst) {
     if (num == 0) { // the empty sum
         HIP_TRY(hipMemsetAsync(dst, 0, s->amp_bytes() << s->n, s->stream));
         return QSIM_OK;

@@ -1,7 +1,8 @@
 // pauli_sweep.h — how a Pauli sweep walks a state: what expect.hip (<psi|P|psi>, read-only), evolve.hip (exp(-i theta/2 P), in
 // place), adjoint.hip (dE/dtheta: the backward sweep over psi and lambda, and lambda = H psi), crot.hip (the rotation under control
 // qubits: CtrlGeom below), cadjoint.hip (the backward sweep under control qubits) and their host side pauli.cpp share.  DESIGN §7b
-// opens with the same account.
+// opens with the same account.  combine.hip (linear combinations of whole states) is no Pauli sweep; it borrows the
+// x == 0 geometry, the unit loads and the reducing grid.
 //
 // A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
 // pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets
@@ -89,6 +90,11 @@ struct SumSweep : PauliSweep {
 };
 // dst_i (=|+=) src_(i^x) (sum_even c_k s_k(i) + i sum_odd c_k s_k(i)), out of place: src and dst are different buffers.
 hipError_t launch_pauli_sum(const LaunchCfg &cfg, const void *src, void *dst, bool f32, int n, const SumSweep &sw);
+// dst_i <- d dst_i + a p_i + b q_i and d_out[0] = sum_i |dst_i|^2 of the values as stored (combine.hip).  d, a, b: (re, im),
+// rounded once to the state's precision.  p != dst, q != dst; q == NULL: no third stream (b is not looked at); d == NULL or d == 0: dst
+// is not loaded, whatever it holds.  A reducing sweep: d_partial as for launch_expect, cfg.grid_cap does not apply.
+hipError_t launch_combine(const LaunchCfg &cfg, void *dst, const double *d, const void *p, const double *a, const void *q, const double *b, bool f32,
+                          int n, double *d_partial, double *d_out);
 
 // the partner index and every z must stay inside the buffer of 2^n amplitudes
 inline bool check_sweep(const PauliSweep &sw, int n) {

@@ -207,6 +207,10 @@ long rotation_sweeps(long run_length); // ceil(run_length / K)
 int pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x, const uint64_t *z_masks, const double *thetas, long count);
 // The 2x2 of exp(-i theta/2 X) (y == false) or exp(-i theta/2 Y) as qsim_apply_1q takes it.
 void pauli_rot_1q(bool y, double theta, double *U);
+// dst = sum_t coeffs[t] Q_t |s->amps> for a settled state and checked arguments, on the state's stream: one out-of-place sweep per
+// piece of an x group (qsim_pauli_sweeps counts them), the first stores, the others accumulate; num_terms == 0 writes zeros.  The
+// gradient's lambda = H psi and the H of a Lanczos step (lanczos.cpp).
+__attribute__((visibility("hidden"))) int pauli_sum_sweeps(qsim_state *s, const uint64_t *x_masks, const uint64_t *z_masks, const double *coeffs, long num_terms, void *dst);
 
 } // namespace qsim
 #endif

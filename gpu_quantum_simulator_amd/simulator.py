@@ -339,6 +339,47 @@ class Simulator(_PauliStrings):
             check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
         return float(energy.value), grad
 
+    # -- state algebra and the Lanczos solver (single states only: a Cluster has no counterpart)
+    def copy_from(self, other: "Simulator") -> None:
+        """This state <- `other`, bit for bit (qsim_copy_state); same qubit count, precision and device.  Not waited for."""
+        check(_lib.load().qsim_copy_state(self._h, other._h))
+
+    def inner(self, other: "Simulator") -> complex:
+        """<self|other> = sum_i conj(self_i) other_i, one sweep on the device (qsim_inner); inner(self) is the squared norm."""
+        re, im = c_double(), c_double()
+        check(_lib.load().qsim_inner(self._h, other._h, byref(re), byref(im)))
+        return complex(re.value, im.value)
+
+    def combine(self, d, ap, bq=None, norm: bool = False):
+        """self <- d self + a p + b q for ap = (a, p) and bq = (b, q) or None, complex numbers and Simulators other than self
+        (qsim_combine).  d == 0: self is overwritten without being read.  norm=True returns the squared norm of the result from
+        the same sweep (and waits for it); otherwise None, not waited for."""
+        def pair(z):
+            z = complex(z)
+            return np.array([z.real, z.imag], dtype=np.float64)
+
+        dd, aa = pair(d), pair(ap[0])
+        bb = pair(bq[0]) if bq is not None else None
+        out = c_double()
+        check(_lib.load().qsim_combine(self._h, _dp(dd), ap[1]._h, _dp(aa), bq[1]._h if bq is not None else None,
+                                       _dp(bb) if bb is not None else None, byref(out) if norm else None))
+        return float(out.value) if norm else None
+
+    def ground_state(self, terms, tol: float, max_steps: int = 200, vector: bool = True) -> dict:
+        """The lowest eigenvalue of H = `terms` (as expectation takes them, real coefficients: ValueError for a complex one) by
+        Lanczos iteration from the current state (qsim_lanczos_ground): keys energy, residual, steps, converged, alphas, betas.
+        `tol` bounds |H y - E y| for the unit Ritz vector y.  vector=True leaves the state as y and returns the MEASURED residual;
+        vector=False leaves the state's bits alone and returns the estimate.  converged: the iteration stopped before max_steps
+        (the residual estimate met tol, or the start vector's Krylov space was exhausted) or the returned residual meets tol."""
+        xs, zs, coeffs, xp, zp, cp = _hamiltonian_arrays(terms, self.num_qubits)
+        energy, residual, steps = c_double(), c_double(), c_int()
+        alphas, betas = np.zeros(max(int(max_steps), 1)), np.zeros(max(int(max_steps), 1))
+        check(_lib.load().qsim_lanczos_ground(self._h, xp, zp, cp, xs.size, int(max_steps), float(tol), 1 if vector else 0, byref(energy),
+                                              byref(residual), byref(steps), _dp(alphas), _dp(betas)))
+        m = steps.value
+        return {"energy": float(energy.value), "residual": float(residual.value), "steps": m,
+                "converged": bool(m < max_steps or residual.value <= tol), "alphas": alphas[:m].copy(), "betas": betas[:m].copy()}
+
     # -- controlled rotations (single states only)
     def _apply_controlled(self, pairs, controls, xp, zp, tp) -> None:
         from ctypes import c_uint64

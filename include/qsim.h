@@ -276,6 +276,52 @@ int qsim_controlled_pauli_gradient(qsim_state *s, const uint64_t *rot_c, const u
  * here, one that meets its z_mask by the call itself.  Otherwise QSIM_ERR_ARG as for qsim_controlled_rotation_plan. */
 int qsim_controlled_gradient_plan(const uint64_t *rot_c, const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, int num_q,
                                   int precision_bits, long *adjoint_sweeps, long *sum_sweeps, uint64_t *units_visited);
+/* ---- state algebra: calls that take more than one state (new) ----
+ * All states of a call have the same qubit count, the same precision and the same device, else QSIM_ERR_ARG.  Every state involved is
+ * settled first: queued gates launched, a lazily held |0...0> or a partly written support written out; a shard that holds nothing
+ * counts as zeros.  A destination that is overwritten without being read gets no zeros first (its queued gates are dropped with
+ * it); afterwards it is an ordinary dense state.  The work runs on the destination's stream (the inner product: on a's), after an
+ * event recorded on every source's stream, and every source's stream waits for an event recorded behind it: a gate queued on a
+ * source afterwards cannot overtake the read. */
+/* dst <- src, bit for bit.  dst != src.  Not waited for. */
+int qsim_copy_state(qsim_state *dst, qsim_state *src);
+/* <a|b> = sum_i conj(a_i) b_i: one read-only sweep over both buffers, real and imaginary part from the same loads, fp64 sums in a
+ * fixed order (equal calls return equal bits).  a == b is allowed and gives (the squared norm, 0).  Waits for its result. */
+int qsim_inner(qsim_state *a, qsim_state *b, double *re, double *im);
+/* dst <- d dst + a p + b q, complex coefficients as (re, im); q (and b) may be NULL: no third state.  *norm2 (may be NULL) = the squared
+ * norm of dst as stored, from the same sweep: what the norm call would return afterwards up to the order of summation, formed in a
+ * fixed order whatever QSIM_OPT_GRID_CAP says.  The coefficients are rounded once to the states' precision and the multiply-adds run
+ * in it.  d == 0: dst is NOT read — it may hold anything, NaN included; with q == NULL that is the scaled copy dst <- a p.  Waits for
+ * the device only when norm2 is asked for.  QSIM_ERR_ARG, nothing touched: dst is p or q, a NULL dst, d, p or a, a non-finite
+ * coefficient, states that differ in shape. */
+int qsim_combine(qsim_state *dst, const double d[2], qsim_state *p, const double a[2], qsim_state *q, const double b[2], double *norm2);
+/* ---- the lowest eigenvalue of a Pauli-sum Hamiltonian by Lanczos iteration, on the device (new) ----
+ * H = sum_t coeffs[t] Q_t as for the gradient call.  From v_0 = state / |state|, step j = 0, 1, ...: w = H v_j, alpha_j = Re <v_j|w>,
+ * w <- w - alpha_j v_j - beta_(j-1) v_(j-1), beta_j = |w| (from the same sweep), v_(j+1) = w / beta_j — no reorthogonalisation, which
+ * the LOWEST Ritz value does not need (interior eigenvalues are not offered for that reason).  After every step the host solves the
+ * tridiagonal of the alphas and betas for its lowest eigenvalue theta and unit eigenvector t; beta_j |t_last| estimates the residual
+ * |H y - theta y| of the unit Ritz vector y.  The call stops when that is <= tol (an absolute bound), at max_steps, or when
+ * beta_j <= 64 eps sum_t |coeffs[t]| (eps = 2^-53 or 2^-24 with the precision): the Krylov space of the start vector is exhausted.
+ * All three return QSIM_OK with *steps = steps done, *energy = theta and alphas[0..steps), betas[0..steps) filled (NULL, or max_steps
+ * entries each).  want_vector == 0: *residual = the estimate, and the state keeps the bits it had (its buffer is only read).
+ * want_vector != 0: a second pass re-runs the recurrence with the recorded alphas and betas and accumulates y = sum_j t_j v_j in the
+ * state's own buffer; one more application of H then MEASURES *residual = |H y - theta y|, and the state ends as y at unit norm.
+ * Cost of a step: the sweeps of one H application (3 G - 1 state volumes for G sweeps), one paired read-only sweep for alpha (2) and
+ * the update (4); two small host synchronisations (alpha, then beta).  Memory: three work buffers of the state's size — the idle spare
+ * buffer and the gradient's lambda buffer where the state has them, the rest allocated before anything is touched (QSIM_ERR_ALLOC
+ * leaves the state untouched) and freed before returning.  Sums are fp64 in a fixed order: equal calls return equal bits.
+ * num_ham == 0 is H = 0: one step, energy 0.  QSIM_ERR_ARG, with the state unchanged: everything the Pauli-sum call refuses,
+ * max_steps < 1, a negative or non-finite tol, a state of norm zero or a shard that holds nothing.
+ * Single states only, fp64 and fp32: there is NO cluster counterpart. */
+int qsim_lanczos_ground(qsim_state *s, const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham, int max_steps, double tol,
+                        int want_vector, double *energy, double *residual, int *steps, double *alphas, double *betas);
+/* Host only: the lowest eigenvalue *theta of the symmetric tridiagonal with diagonal alphas[0..m) and off-diagonal betas[0..m-1)
+ * (bisection), and its unit eigenvector vec[0..m) (inverse iteration; NULL: not wanted; largest component positive). */
+int qsim_tridiag_lowest(const double *alphas, const double *betas, int m, double *theta, double *vec);
+/* Host only: what ONE step of the call above costs for these terms — the sweeps of the H application (the Pauli-sum grouping), the
+ * other sweeps (2: alpha and the update) and the state volumes read and written by all of them.  QSIM_ERR_ARG for max_steps < 1. */
+int qsim_lanczos_plan(const uint64_t *ham_x, long num_ham, int max_steps, int want_vector, long *sum_sweeps_per_step, long *other_sweeps_per_step,
+                      double *volumes_per_step);
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
