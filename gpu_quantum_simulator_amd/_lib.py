@@ -19,6 +19,7 @@ OPT_PLAN_CACHE = 13
 OPT_PINGPONG = 14
 OPT_SPARSE_START = 15
 OPT_DEBUG_PLAN_KEY = 16
+OPT_DEFER_FLIPS = 17
 K_NAMES = ("init", "gate1", "gate1_lo", "phase", "cx", "gate2", "tile", "pack")
 K_COUNT = len(K_NAMES)
 
@@ -85,6 +86,7 @@ SIGNATURES = {
     "qsim_flush": (c_int, [c_void_p]),
     "qsim_sync": (c_int, [c_void_p]),
     "qsim_plan_cache_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "qsim_deferred_flip_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "qsim_read": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
     "qsim_write": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
     "qsim_norm2": (c_int, [c_void_p, _DP]),
@@ -204,6 +206,7 @@ SIGNATURES = {
     "qsim_plan_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimStats)]),
     "qsim_plan_passes": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimPassInfo), c_int, POINTER(c_int)]),
     "qsim_schedule_circuit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p]),
+    "qsim_schedule_circuit_deferred": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p, POINTER(c_uint64)]),
     "qsim_tile_records": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_uint64, TILE_RECORD_CB, c_void_p]),
 }
 # include/qsim_legacy.h

@@ -93,6 +93,7 @@ extern "C" int qsim_cluster_create(qsim_cluster **out, int num_q, int num_shards
         qsim_state *s = nullptr;
         int rc = c->pool[0] ? qsim_create_external(&s, c->m, dev, c->pool[0] + ((size_t)r * 16 << c->m)) : qsim_create(&s, c->m, dev);
         c->shard.push_back(s);
+        if (rc == QSIM_OK) rc = qsim_set_option(s, QSIM_OPT_DEFER_FLIPS, 0); // a shard's last pass may have to do an exchange's re-layout
         c->scratch.push_back(c->pool[1] ? (double2 *)(c->pool[1] + ((size_t)r * 16 << c->m)) : nullptr);
         if (rc == QSIM_OK && p > 0 && !c->pool[0]) {
             (void)hipSetDevice(dev);

@@ -204,6 +204,10 @@ extern "C" int qsim_set_option(qsim_state *s, int option, long value) {
     case QSIM_OPT_DEBUG_PLAN_KEY:
         s->debug_plan_key = value;
         break;
+    case QSIM_OPT_DEFER_FLIPS:
+        if (value < 0 || value > 2) return fail(QSIM_ERR_ARG, "defer_flips must be 0 (never), 1 (where the planned schedule says so) or 2 (wherever possible)");
+        s->defer_flips = (int)value;
+        break;
     case QSIM_OPT_PINGPONG:
         if (value < 0 || value > 2) return fail(QSIM_ERR_ARG, "pingpong must be 0 (never), 1 (auto) or 2 (always)");
         s->pingpong = (int)value;
@@ -237,6 +241,7 @@ extern "C" long qsim_get_option(const qsim_state *s, int option) {
     case QSIM_OPT_PINGPONG: return s->pingpong;
     case QSIM_OPT_SPARSE_START: return s->sparse_start;
     case QSIM_OPT_DEBUG_PLAN_KEY: return s->debug_plan_key;
+    case QSIM_OPT_DEFER_FLIPS: return s->defer_flips;
     default: return -1;
     }
 }
@@ -409,8 +414,9 @@ void *qsim::spare_buffer(qsim_state *s) {
 // Launches a tile pass whose TileOps are already on the device (no statistics, no profiling events).  oop: write the
 // state to the spare buffer and make that the state (the caller checked spare_buffer()).  job: the pass writes the state,
 // re-laid-out, to job->out (or the buffer the state is not in) and records where.
+// flip (with oop, without job): deferred X gates — the amplitude of index i is stored at i ^ flip of the spare buffer.
 static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileOp *d, int need, bool from_zero_ket, bool oop = false, uint64_t zero_mask = 0,
-                                PackJob *job = nullptr) {
+                                PackJob *job = nullptr, uint64_t flip = 0) {
     LaunchCfg cfg{s->stream, s->grid_cap};
     const int threads = s->tile_threads; // 0: default for the tile size
     if (job) {
@@ -421,7 +427,10 @@ static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileO
         job->packed_at = dst;
         return QSIM_OK;
     }
-    const hipError_t e = launch_tile(cfg, s->amps, oop ? s->spare : s->amps, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask);
+    PackMap flips = identity_pack_map();
+    flips.flip = flip;
+    if (flip && (!oop || !s->spare || s->spare == s->amps)) return fail(QSIM_ERR_ARG, "internal: deferred flips need an out-of-place pass");
+    const hipError_t e = launch_tile(cfg, s->amps, oop ? s->spare : s->amps, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, flip ? &flips : nullptr);
     if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     if (oop) std::swap(s->amps, s->spare);
     return QSIM_OK;
@@ -430,7 +439,7 @@ static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileO
 // Prepares the blocks of a tile pass for the given bit order in the pinned ring, uploads and launches them; `capture`
 // (optional) receives a copy of the prepared TileOps for the plan cache.
 int qsim::launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, bool from_zero_ket, std::vector<TileOp> *capture, bool oop, uint64_t zero_mask,
-                           PackJob *job) {
+                           PackJob *job, uint64_t flip) {
     const size_t need = p.blocks.size();
     if (need > s->ops_cap) return fail(QSIM_ERR_ARG, "tile pass with %zu ops exceeds the op buffer", need);
     if (s->ops_used + need > s->ops_cap) { // ring is full: wait until earlier passes have read their ops
@@ -444,7 +453,7 @@ int qsim::launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, b
     TileOp *d = s->d_ops + s->ops_used;
     HIP_TRY(hipMemcpyAsync(d, h, need * sizeof(TileOp), hipMemcpyHostToDevice, s->stream));
     s->ops_used += need;
-    return launch_tile_prepared(s, geom, d, (int)need, from_zero_ket, oop, zero_mask, job);
+    return launch_tile_prepared(s, geom, d, (int)need, from_zero_ket, oop, zero_mask, job, flip);
 }
 
 // cached_geom / cached_ops: replay of a cached plan (the tile pass's order and device-resident TileOps);
@@ -457,7 +466,7 @@ static void push_head(std::vector<uint8_t> &out, const TileOp &t) {
 // cached_heads: those bytes of the cached records, kept on the host with the plan (kHeadBytes per op).
 static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom = nullptr, const TileOp *cached_ops = nullptr,
                        std::vector<TileOp> *capture = nullptr, TileGeom *geom_out = nullptr, bool oop = false, PackJob *job = nullptr,
-                       const uint8_t *cached_heads = nullptr) {
+                       const uint8_t *cached_heads = nullptr, uint64_t flip = 0) {
     const bool from_zero_ket = s->zero_ket_pending && p.kclass == QSIM_K_TILE;
     if ((s->zero_ket_pending || s->partial) && p.kclass != QSIM_K_TILE) { // only tile passes work on a partially written state
         QSIM_TRY(materialize_zero_ket(s));
@@ -529,8 +538,8 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
                 }
                 scope.pe.forms.push_back((uint8_t)((T == 4 ? 2 : T == 2 ? 1 : 0) | (b.nq << 2) | (2 * ident >= b.dim() ? 32 : 0) | (b.ns << 6)));
             }
-        const int rc = cached_ops ? launch_tile_prepared(s, geom, cached_ops, (int)p.blocks.size(), from_zero_ket, oop, zero_mask, job)
-                                  : launch_tile_pass(s, p, geom, from_zero_ket, capture, oop, zero_mask, job);
+        const int rc = cached_ops ? launch_tile_prepared(s, geom, cached_ops, (int)p.blocks.size(), from_zero_ket, oop, zero_mask, job, flip)
+                                  : launch_tile_pass(s, p, geom, from_zero_ket, capture, oop, zero_mask, job, flip);
         if (rc) return rc;
         if (scope.on && s->profile >= 2) { // which kernel form each block ran through: out of the records the kernel was given
             const size_t need = p.blocks.size();
@@ -599,7 +608,7 @@ static bool same_gates(const QueuedGate *a, const QueuedGate *b, size_t count) {
     return true;
 }
 static bool plan_matches(const PlanIdentity &have, const PlanIdentity &want, const QueuedGate *gates, size_t count) {
-    return memcmp(have.opts, want.opts, sizeof have.opts) == 0 && have.support == want.support && have.env == want.env &&
+    return memcmp(have.opts, want.opts, sizeof have.opts) == 0 && have.support == want.support && have.env == want.env && have.defer == want.defer &&
            have.gates.size() == count && same_gates(have.gates.data(), gates, count);
 }
 
@@ -647,7 +656,7 @@ namespace {
 struct PlanRecorder {
     CachedPlan plan;
     std::vector<TileOp> host_ops;
-    int launch(qsim_state *s, Pass &&p, bool oop, PackJob *job);
+    int launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip);
 };
 
 // Keeps the recorded plan: its TileOps move to a device buffer of their own (one copy, ordered behind the launches).  A stale plan
@@ -687,10 +696,10 @@ static int keep_plan(qsim_state *s, PlanRecorder &rec, uint64_t key, uint64_t ep
     return QSIM_OK;
 }
 
-int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job) {
+int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip) {
     TileGeom g = p.geom;
     plan.op_first.push_back(host_ops.size());
-    const int rc = launch_pass(s, p, nullptr, nullptr, &host_ops, &g, oop, job);
+    const int rc = launch_pass(s, p, nullptr, nullptr, &host_ops, &g, oop, job, nullptr, flip);
     plan.geoms.push_back(g);
     plan.passes.push_back(std::move(p));
     return rc;
@@ -711,10 +720,22 @@ int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job) {
 //      where; the state's own buffers are left holding stale data).  The tile passes before it follow rule 3 among themselves, so
 //      the one before it leads home — which is why TWO groups wait then.  Otherwise rule 3 applies to all and packed_at stays NULL.
 //   5. After a failed launch the buffers keep their roles.
+//   6. With deferred X gates (flip != 0, never together with a PackJob; SchedConfig::defer_flips): the very last pass stores the
+//      state at index ^ flip, which only an out-of-place pass can do, and the state must still end at home.  So two groups wait as
+//      under rule 4, and the tile pass before the last leads AWAY from home (in place if the state is away already).  flip_ok() says,
+//      once every pass has been pushed, whether that works out: the queue ends in a tile pass that has the PACK variant, with a
+//      tile pass before it, a second buffer, and every flipped bit inside the support the state then has (a flipped bit outside it
+//      would be a qubit in |1> that no zero_mask can express).  If not, the caller drops the flip and pushes the X gates as passes.
 class PassRouter {
   public:
     // rec: the fresh path's recorder for the plan cache, through which the passes moved in are launched (NULL: nothing is recorded)
-    PassRouter(qsim_state *s, PackJob *job, PlanRecorder *rec) : s_(s), job_(job), rec_(rec), home_(s->amps), sup_(current_support(s)) {}
+    PassRouter(qsim_state *s, PackJob *job, PlanRecorder *rec, uint64_t flip = 0)
+        : s_(s), job_(job), rec_(rec), home_(s->amps), flip_(job ? 0 : flip), two_(job != nullptr || flip_ != 0), sup_(current_support(s)) {}
+    bool flip_ok() const {
+        return flip_ != 0 && rc_ == QSIM_OK && pp_ > 0 && held_.size() == 1 && !prev_.empty() && held_[0].p->kclass == QSIM_K_TILE &&
+               launch_tile_can_pack(s_->f32, held_[0].tile_geom(), s_->tile_threads) && (flip_ & index_mask(s_->n) & ~sup_) == 0;
+    }
+    void drop_flip() { flip_ = 0; }
     void push(Pass &&p) { std::unique_ptr<Pass> own(new Pass(std::move(p))); const Pass *at = own.get(); route({at, nullptr, nullptr, std::move(own), nullptr}); }
     void push(const Pass &p, const TileGeom *geom, const TileOp *d_ops, const uint8_t *heads) { route({&p, geom, d_ops, nullptr, heads}); } // of a cached plan: nothing is copied
     int finish() { // the queue has ended
@@ -736,19 +757,21 @@ class PassRouter {
     PackJob *job_;
     PlanRecorder *rec_;
     void *const home_;
+    uint64_t flip_;  // rule 6
+    const bool two_; // two groups wait (rules 4 and 6)
     int rc_ = QSIM_OK;
     int pp_ = -1;  // second buffer available?  -1: not asked yet
     uint64_t sup_; // where the state can be non-zero once every pass pushed so far has run ...
     uint64_t sup_before_last_ = 0; // ... and once every pass but the most recent one has
     std::vector<Item> held_, prev_; // the most recent group; with a PackJob also the one before it
 
-    void launch(Item &it, bool oop, PackJob *pj) {
+    void launch(Item &it, bool oop, PackJob *pj, uint64_t flip = 0) {
         if (rc_ != QSIM_OK) return;
-        if (it.own && rec_) rc_ = rec_->launch(s_, std::move(*it.own), oop, pj);
-        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj, it.heads);
+        if (it.own && rec_) rc_ = rec_->launch(s_, std::move(*it.own), oop, pj, flip);
+        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj, it.heads, flip);
     }
-    void run_group(std::vector<Item> &grp, bool oop, PackJob *pj = nullptr) { // oop / pj: of the tile pass at its head
-        for (size_t i = 0; i < grp.size(); i++) launch(grp[i], i == 0 && oop, i == 0 ? pj : nullptr);
+    void run_group(std::vector<Item> &grp, bool oop, PackJob *pj = nullptr, uint64_t flip = 0) { // oop / pj / flip: of the tile pass at its head
+        for (size_t i = 0; i < grp.size(); i++) launch(grp[i], i == 0 && oop, i == 0 ? pj : nullptr, i == 0 ? flip : 0);
         grp.clear();
     }
     void route(Item &&it) {
@@ -757,7 +780,7 @@ class PassRouter {
         sup_before_last_ = sup_;
         sup_ = tile ? sup_ | tile_mask(it.tile_geom()) : ~0ULL; // anything but a tile pass has the zeros written out first
         if (tile && pp_ < 0) pp_ = spare_buffer(s_) != nullptr ? 1 : 0;
-        if (pp_ <= 0 && !job_) { launch(it, false, nullptr); return; } // rule 2
+        if (pp_ <= 0 && !two_) { launch(it, false, nullptr); return; } // rule 2
         if (tile) release(false);
         if (tile || !held_.empty()) held_.push_back(std::move(it));
         else launch(it, false, nullptr); // no tile pass seen yet
@@ -765,10 +788,17 @@ class PassRouter {
     // last = false: a newer tile pass has arrived, so the oldest group held is not the last (rule 3); true: the end of the queue
     void release(bool last) {
         if (!last) {
-            run_group(job_ ? prev_ : held_, pp_ > 0);
-            if (job_) prev_.swap(held_);
+            run_group(two_ ? prev_ : held_, pp_ > 0);
+            if (two_) prev_.swap(held_);
             return;
         }
+        if (flip_ok()) { // rule 6
+            run_group(prev_, s_->amps == home_); // must lead away: the flipping pass is out of place and ends at home
+            run_group(held_, true, nullptr, flip_);
+            if (rc_ == QSIM_OK) s_->flips_applied++;
+            return;
+        }
+        if (flip_ != 0 && rc_ == QSIM_OK) rc_ = fail(QSIM_ERR_ARG, "internal: deferred flips were neither applied nor dropped");
         const Item *very_last = held_.size() == 1 ? &held_[0] : nullptr; // a tile pass with nothing behind it
         if (job_ && pass_can_pack(s_, very_last ? very_last->p : nullptr, very_last ? very_last->tile_geom() : TileGeom{}, job_, sup_before_last_)) { // rule 4
             run_group(prev_, pp_ > 0 && s_->amps != home_); // must lead home: the packing pass reads the state's own buffer
@@ -802,32 +832,60 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
     const bool hinted = s->fuse >= 3 && have_sched_hints();
     PlanRecorder rec;
     uint64_t key = 0;
+    // only a plain single-state flush defers X gates, and by default only where the planning step chose a schedule that does
+    const int defer = !job && (s->defer_flips == 2 || (s->defer_flips == 1 && hinted)) && may_defer_flips(s) ? s->defer_flips : 0;
     if (cacheable || hinted) {
         rec.plan.id = plan_identity(s, s->queue.size(), current_support(s));
+        rec.plan.id.defer = defer;
         key = gates_key(s, rec.plan.id, s->queue.data(), s->queue.size());
     }
     const uint64_t epoch = wisdom_epoch();
+    // The flips the router could not hand to the last tile pass (PassRouter rule 6) run as X gates in passes of their own,
+    // scheduled the ordinary way and pushed behind the others: right, at the price of one more pass, and counted.
+    auto settle_flips = [&](PassRouter &router, uint64_t flip) {
+        if (flip == 0 || router.flip_ok()) return;
+        router.drop_flip();
+        s->flip_fallbacks++;
+        static const cd kX[4] = {cd(0, 0), cd(1, 0), cd(1, 0), cd(0, 0)};
+        Scheduler xs(state_sched_config(s, ~0ULL)); // (dense: the gates behind these X gates may have made any support)
+        for (int q = 0; q < s->n; q++)
+            if (flip >> q & 1ULL) xs.add_1q(kX, q);
+        xs.finish([&](Pass &&p) { router.push(std::move(p)); });
+    };
     if (const CachedPlan *pl = cacheable ? find_plan(s, key, epoch, rec.plan.id) : nullptr) { // replay: no scheduling, no block preparation, no H2D copy
         s->queue.clear();
-        PassRouter router(s, job, nullptr);
+        PassRouter router(s, job, nullptr, pl->flip);
         for (size_t i = 0; i < pl->passes.size(); i++) {
             const bool tile = pl->passes[i].kclass == QSIM_K_TILE;
             router.push(pl->passes[i], tile ? &pl->geoms[i] : nullptr, tile ? pl->d_ops + pl->op_first[i] : nullptr,
                         tile ? pl->op_heads.data() + kHeadBytes * pl->op_first[i] : nullptr);
         }
+        settle_flips(router, pl->flip); // (a plan is recorded with the flip its last pass took, so this finds nothing to do)
         return router.finish();
     }
     SchedConfig scfg = state_sched_config(s, current_support(s));
     if (hinted) apply_sched_hint(key, scfg);
+    scfg.defer_flips = defer == 2 || (defer == 1 && scfg.defer_flips) ? 1 : 0;
     Scheduler sched(scfg);
     feed(sched, s->queue);
+    const uint64_t flip = sched.residual_flips(); // known before the first pass is built
     if (cacheable) rec.plan.id.gates = std::move(s->queue); // the plan remembers what it was built from
     s->queue.clear();
     // passes are launched as they are scheduled, as far as the routing allows (PassRouter, rules 2 and 3)
-    PassRouter router(s, job, cacheable ? &rec : nullptr);
+    PassRouter router(s, job, cacheable ? &rec : nullptr, flip);
     sched.finish([&](Pass &&p) { router.push(std::move(p)); });
+    rec.plan.flip = router.flip_ok() ? flip : 0;
+    settle_flips(router, flip);
     const int rc = router.finish();
     return rc != QSIM_OK || !cacheable ? rc : keep_plan(s, rec, key, epoch);
+}
+
+bool qsim::may_defer_flips(qsim_state *s) {
+    if (s->defer_flips == 0 || s->fuse < 3 || s->f32 || !s->owns) return false;
+    TileGeom g{};
+    g.tile_bits = std::min(s->tile_bits, s->n);
+    if (!launch_tile_can_pack(false, g, s->tile_threads)) return false;
+    return spare_buffer(s) != nullptr && s->owns_spare;
 }
 
 int qsim::written(qsim_state *s, bool keep_partial) {
@@ -848,6 +906,13 @@ extern "C" int qsim_plan_cache_stats(const qsim_state *s, uint64_t *plans, uint6
     if (plans) *plans = s->plans.size();
     if (replays) *replays = s->plan_hits;
     if (key_collisions) *key_collisions = s->plan_key_collisions;
+    return QSIM_OK;
+}
+
+extern "C" int qsim_deferred_flip_stats(const qsim_state *s, uint64_t *applied, uint64_t *fallbacks) {
+    if (!s) return fail(QSIM_ERR_ARG, "NULL state");
+    if (applied) *applied = s->flips_applied;
+    if (fallbacks) *fallbacks = s->flip_fallbacks;
     return QSIM_OK;
 }
 

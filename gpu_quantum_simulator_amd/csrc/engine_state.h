@@ -58,6 +58,7 @@ struct PlanIdentity {
     int opts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t support = 0;
     qsim::SchedEnv env;
+    int defer = 0; // QSIM_OPT_DEFER_FLIPS as it applies to this flush (0: the flush may not defer X gates at all)
     std::vector<QueuedGate> gates;
 };
 
@@ -68,6 +69,7 @@ struct CachedPlan {
     std::vector<qsim::TileGeom> geoms;   // per pass; meaningful for tile passes: the geometry in the order it was launched with
     std::vector<size_t> op_first;  // per pass: index of its first TileOp in d_ops
     qsim::TileOp *d_ops = nullptr;
+    uint64_t flip = 0;             // deferred X gates: the index flip the stores of the last tile pass apply (SchedConfig::defer_flips)
     std::vector<uint8_t> op_heads; // per TileOp of d_ops: kHeadBytes of its header (nq, terms, nsel, flags, b[7]), for the launch log
 };
 
@@ -103,6 +105,8 @@ struct qsim_state {
     bool partial = false;
     uint64_t support = 0; // qubits some tile pass has had inside its tile since the reset
     int sparse_start = 1; // QSIM_OPT_SPARSE_START
+    int defer_flips = 1;  // QSIM_OPT_DEFER_FLIPS
+    uint64_t flips_applied = 0, flip_fallbacks = 0; // flushes whose last tile pass stored the state flipped; flushes that had to run the X gates as a pass of their own
     // op ring for tile passes
     qsim::TileOp *d_ops = nullptr, *h_ops = nullptr;
     size_t ops_cap = 0, ops_used = 0;
@@ -181,9 +185,12 @@ PlanIdentity plan_identity(const qsim_state *s, size_t count, uint64_t support);
 uint64_t gates_key(const qsim_state *s, const PlanIdentity &id, const QueuedGate *gates, size_t count);
 // The second buffer for out-of-place tile passes, or NULL when the passes of this state run in place.
 void *spare_buffer(qsim_state *s);
+// Whether a plain flush of this state may leave its X gates to the stores of the last tile pass (QSIM_OPT_DEFER_FLIPS): level 3,
+// fp64 in the tile shape that has the PACK variant, passes out of place between two buffers of the state's own.
+bool may_defer_flips(qsim_state *s);
 // Prepares the blocks of a tile pass for the given bit order in the pinned ring, uploads and launches them.
 int launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, bool from_zero_ket, std::vector<TileOp> *capture = nullptr, bool oop = false,
-                     uint64_t zero_mask = 0, PackJob *job = nullptr);
+                     uint64_t zero_mask = 0, PackJob *job = nullptr, uint64_t flip = 0);
 // qsim_flush; job != NULL: the last pass may write the state re-laid-out instead (PackJob, the comment at the definition).
 int flush_impl(qsim_state *s, PackJob *job);
 bool trace_pack(); // QSIM_TRACE_PACK is set: stderr says why a re-layout got a sweep of its own

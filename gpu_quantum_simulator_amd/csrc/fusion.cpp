@@ -204,7 +204,25 @@ void Scheduler::close(int idx) {
     op.kind = 0;
 }
 
-void Scheduler::add_1q(const cd U[4], int q) {
+// SchedConfig::defer_flips: out = X^f U X^f for the flips `fm` on the gate's qubits, as a bit mask of its row index.  Entries are
+// moved, never multiplied: exact zeros and the diagonal stay what they are (selector_mask and the merge conditions read them).
+static void conjugate_by_flips(const cd *U, int dim, int fm, cd *out) {
+    for (int r = 0; r < dim; r++)
+        for (int c = 0; c < dim; c++) out[dim * r + c] = U[dim * (r ^ fm) + (c ^ fm)];
+}
+
+void Scheduler::add_1q(const cd Uin[4], int q) {
+    const cd *U = Uin;
+    cd conj[4], diag[4];
+    if (deferring()) {
+        if (flips_ >> q & 1ULL) { conjugate_by_flips(Uin, 2, 1, conj); U = conj; }
+        if (is_zero(U[0]) && is_zero(U[3])) { // anti-diagonal: A = X (X A), and X A = diag(A[1][0], A[0][1]) — the X is owed from here on
+            flips_ ^= 1ULL << q;
+            if (is_one(U[1]) && is_one(U[2])) { deferred_.push_back((uint32_t)gates_++); return; } // X itself: nothing is left to schedule
+            diag[0] = U[2]; diag[1] = diag[2] = cd(0, 0); diag[3] = U[1];
+            U = diag;
+        }
+    }
     const uint32_t g = (uint32_t)gates_++;
     const FusedOp op = make_op(OP_G1, q, -1, U);
     if (cfg_.fuse == 0) { append_closed(op, g); return; }
@@ -242,7 +260,13 @@ void Scheduler::add_cx(int control, int target) {
     }
     cd m[16];
     cx4(control > target, m);
-    fold_2q(m, std::max(control, target), std::min(control, target), 1, g);
+    const int q_hi = std::max(control, target), q_lo = std::min(control, target);
+    if (const int fm = deferring() ? flips_on(q_hi, q_lo) : 0) { // a flipped target changes nothing, a flipped control gives "control = 0"
+        cd conj[16];
+        conjugate_by_flips(m, 4, fm, conj);
+        std::copy(conj, conj + 16, m);
+    }
+    fold_2q(m, q_hi, q_lo, 1, g);
 }
 
 void Scheduler::add_2q(const cd U[16], int q_hi, int q_lo) {
@@ -252,6 +276,8 @@ void Scheduler::add_2q(const cd U[16], int q_hi, int q_lo) {
         append_closed(make_op(OP_G2, q_hi, q_lo, U), g);
         return;
     }
+    cd conj[16];
+    if (const int fm = deferring() ? flips_on(q_hi, q_lo) : 0) { conjugate_by_flips(U, 4, fm, conj); U = conj; }
     fold_2q(U, q_hi, q_lo, 1, g);
 }
 
@@ -296,7 +322,22 @@ void Scheduler::finish(const PassSink &sink) {
     for (int q = 0; q < cfg_.n; q++) close(open_[q]);
     pool_.clear();
     pool_src_.clear();
-    build_passes(sink);
+    if (deferred_.empty()) build_passes(sink);
+    else { // the deferred X statements count with the last pass, so that one is held back until the end is seen
+        Pass last;
+        bool have = false;
+        build_passes([&](Pass &&p) {
+            if (have) sink(std::move(last));
+            last = std::move(p);
+            have = true;
+        });
+        if (have) {
+            (last.blocks.empty() ? last.ops.back().gates : last.blocks.back().gates) += (uint32_t)deferred_.size();
+            if (cfg_.track) last.src.insert(last.src.end(), deferred_.begin(), deferred_.end());
+            sink(std::move(last));
+        }
+        deferred_.clear();
+    }
     closed_.clear();
     closed_src_.clear();
 }

@@ -100,6 +100,17 @@ static int tile_live_regs(const TileGeom &g, int threads, uint64_t zero_mask) {
     return live;
 }
 
+// PackMap::flip split by who owns each output bit: the lanes of a workgroup walk the low bits and the first log2(THREADS) - L
+// high bits of the order, a lane's registers the rest of the tile, and perm carries each of those input bits to one output bit.
+// (Only shapes without tail guards have the PACK variant: 2^L <= THREADS <= 2^B.)
+static void split_flip(PackMap &pm, const TileGeom &g, int threads) {
+    const int lane_high = __builtin_ctz((unsigned)threads) - g.low_bits; // high bits of the order that the lanes walk
+    uint64_t lane_in = (1ULL << g.low_bits) - 1ULL, reg_in = 0;
+    for (int j = 0; j < g.n_high; j++) (j < lane_high ? lane_in : reg_in) |= 1ULL << g.high[j];
+    pm.flip_lane = pm.flip & pack_perm(pm, lane_in);
+    pm.flip_reg = pm.flip & pack_perm(pm, reg_in);
+}
+
 template <int B, int THREADS>
 static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops,
                                 bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
@@ -107,7 +118,7 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     const uint64_t ntiles = 1ULL << __builtin_popcountll(index_mask(g.n) & ~tile_mask(g) & ~zero_mask); // tiles whose base index may be non-zero
     const int lds = ((int)sizeof(amp_t) << g.tile_bits) + (8 << g.n_high); // the tile, then k_tile's hoff table
     constexpr bool kHasPack = tile_has_pack(B, THREADS);
-    const bool packed = pack != nullptr && pack->k > 0;
+    const bool packed = pack != nullptr && (pack->k > 0 || pack->flip != 0); // flips alone: the identity permutation (identity_pack_map)
     if (packed && !kHasPack) return hipErrorNotSupported;
     const bool sparse = zero_mask != 0 && !from_zero_ket; // a pass over a partially written state: k_tile<SPARSE>
     // four instantiations at most (PACK x SPARSE), all of one signature: the variant is chosen here, once, as an index and a pointer
@@ -153,8 +164,13 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
     const uint64_t grid = (ntiles + tpw - 1) / (uint64_t)tpw;
     // d_ops: g.n_scale tile-uniform factors first, then the blocks
     const int n_scale = n_ops > 0 ? g.n_scale : 0;
+    PackMap pm = packed ? *pack : PackMap{};
+    if (pm.flip) {
+        if ((pm.flip & ~index_mask(g.n)) != 0 || v == vout) return hipErrorInvalidValue; // a store outside the buffer / over amplitudes not read yet
+        split_flip(pm, g, THREADS);
+    }
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, n_ops - n_scale, ntiles, tpw,
-                       n_scale, packed ? *pack : PackMap{});
+                       n_scale, pm);
     return hipGetLastError();
 }
 

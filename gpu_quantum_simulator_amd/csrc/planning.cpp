@@ -91,12 +91,13 @@ void qsim::order_tile_bits(qsim_state *s, TileGeom &g, uint64_t zero_mask) {
 // that were never planned use the default.
 // The table is found by key alone: a colliding circuit would be scheduled with another circuit's variant — a valid schedule
 // either way (every variant is; the results never depend on it).  Bounded: beyond kMaxSchedHints circuits it starts afresh.
-struct SchedHint { int commute; double cheap_margin; int lookahead; int cap; /* clusters per pass; 0: the configuration's own */ uint64_t seed; /* SchedConfig::seed */ };
+struct SchedHint { int commute; double cheap_margin; int lookahead; int cap; /* clusters per pass; 0: the configuration's own */ uint64_t seed; /* SchedConfig::seed */
+                   int defer; /* SchedConfig::defer_flips (the engine still asks whether the flush at hand may: may_defer_flips) */ };
 static std::mutex g_hints_mu;
 static std::map<uint64_t, SchedHint> g_sched_hints;
 constexpr size_t kMaxSchedHints = 4096;
 static SchedConfig with_hint(SchedConfig v, const SchedHint &h) {
-    v.commute = h.commute; v.cheap_margin = h.cheap_margin; v.lookahead = h.lookahead; v.seed = h.seed;
+    v.commute = h.commute; v.cheap_margin = h.cheap_margin; v.lookahead = h.lookahead; v.seed = h.seed; v.defer_flips = h.defer;
     if (h.cap > 0) { v.tile_max_ops = h.cap; v.tail_max_ops = std::max(v.tail_max_ops, h.cap); }
     return v;
 }
@@ -117,7 +118,7 @@ static std::map<uint64_t, RankedVariant> g_sched_measured; // guarded by g_hints
 static void set_sched_hint(uint64_t key, const SchedHint &now, bool is_default, const SchedConfig &scfg) {
     std::lock_guard<std::mutex> lock(g_hints_mu);
     const auto it = g_sched_hints.find(key);
-    const SchedHint dflt{scfg.commute, scfg.cheap_margin, scfg.lookahead, 0, 0};
+    const SchedHint dflt{scfg.commute, scfg.cheap_margin, scfg.lookahead, 0, 0, 0};
     const SchedHint before = it == g_sched_hints.end() ? dflt : it->second;
     if (is_default) g_sched_hints.erase(key);
     else {
@@ -131,7 +132,7 @@ static void set_sched_hint(uint64_t key, const SchedHint &now, bool is_default, 
         }
         g_sched_hints[key] = now;
     }
-    if (before.commute != now.commute || before.cheap_margin != now.cheap_margin || before.lookahead != now.lookahead || before.cap != now.cap || before.seed != now.seed)
+    if (before.commute != now.commute || before.cheap_margin != now.cheap_margin || before.lookahead != now.lookahead || before.cap != now.cap || before.seed != now.seed || before.defer != now.defer)
         g_wisdom_epoch++; // cached plans of this circuit were scheduled another way
 }
 
@@ -196,7 +197,16 @@ static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedCon
     for (int com = 1; com >= 0; com--)
         for (int cap : caps)
             for (double mar : {scfg.cheap_margin, 2.0 * scfg.cheap_margin})
-                for (int la = scfg.lookahead; la <= scfg.lookahead + (scfg.lookahead >= 1 ? 1 : 0); la++) variants.push_back({com, mar, la, cap, 0});
+                for (int la = scfg.lookahead; la <= scfg.lookahead + (scfg.lookahead >= 1 ? 1 : 0); la++) variants.push_back({com, mar, la, cap, 0, 0});
+    // ... and every one of them with the X gates left to the stores of the last tile pass (SchedConfig::defer_flips), where a flush
+    // of this state may do that.  Fewer qubits are forced into tiles, but the greedy packing does not gain from it on every circuit.
+    // (Not on the cold path: the second buffer that out-of-place passes need cannot be asked for while the first is being allocated.)
+    if (!stop && s->defer_flips != 0 && may_defer_flips(s))
+        for (size_t vi = 0, nv = variants.size(); vi < nv; vi++) {
+            SchedHint h = variants[vi];
+            h.defer = 1;
+            variants.push_back(h);
+        }
     // Every candidate is an independent run of the scheduler on the same gates: they are evaluated on up to 16 host threads
     // (80 schedules at n = 30: 0.9-1.3 s on one thread) and REDUCED in candidate order with the same rule as before — the default
     // first, a later one only when it is at least 0.5 % cheaper — so the choice does not depend on the thread count.  `stop`
@@ -316,9 +326,10 @@ extern "C" int qsim_support_after(qsim_state *s, const qsim_circuit *c, uint64_t
     SchedConfig scfg = state_sched_config(s, support);
     const std::vector<QueuedGate> q = queue_of(c);
     if (s->fuse >= 3 && have_sched_hints()) apply_sched_hint(gates_key(s, plan_identity(s, q.size(), support), q.data(), q.size()), scfg);
+    scfg.defer_flips = (s->defer_flips == 2 || (s->defer_flips == 1 && scfg.defer_flips)) && may_defer_flips(s) ? 1 : 0; // as qsim_flush decides (a shard never defers)
     Scheduler sv(scfg);
     feed(sv, q);
-    uint64_t sup = support;
+    uint64_t sup = support | sv.residual_flips(); // a flipped qubit is inside the support afterwards, whichever pass applies the flip
     sv.finish([&](Pass &&p) {
         if (p.kclass != QSIM_K_TILE) { sup = nmask; return; } // the engine writes the zeros out first (materialize_zero_ket)
         sup |= tile_mask(p.geom);
@@ -351,11 +362,17 @@ static int keep_fastest_schedule(qsim_state *s, const qsim_circuit *c, const Sch
     std::stable_sort(ranked.begin(), ranked.end(), [](const RankedVariant &a, const RankedVariant &b) { return a.cost < b.cost; });
     std::vector<RankedVariant> tries;
     if (const char *v = getenv("QSIM_TUNE_SCHEDULES")) s->tune_schedules = std::max(1, std::min(80, atoi(v)));
-    for (const RankedVariant &v : ranked) { // distinct predicted costs = (almost surely) distinct schedules
-        bool dup = false;
-        for (const RankedVariant &t : tries) dup = dup || t.cost == v.cost;
-        if (!dup) tries.push_back(v);
-        if (tries.size() == (size_t)s->tune_schedules) break;
+    // ... of the schedules without deferred X gates and of those with them alike: the model prices the flipping pass like any other and
+    // ranks the two families against each other only roughly, so the best of the first family is always among the ones run
+    for (int defer = 0; defer < 2; defer++) {
+        size_t taken = 0;
+        for (const RankedVariant &v : ranked) { // distinct predicted costs = (almost surely) distinct schedules
+            if (v.hint.defer != defer) continue;
+            bool dup = false;
+            for (const RankedVariant &t : tries) dup = dup || t.cost == v.cost;
+            if (!dup) { tries.push_back(v); taken++; }
+            if (taken == (size_t)s->tune_schedules) break;
+        }
     }
     hipEvent_t t0 = nullptr, t1 = nullptr;
     HIP_TRY(hipEventCreate(&t0));
@@ -527,8 +544,9 @@ extern "C" int qsim_tune_table_save(const char *path) {
     {   // measured schedule choices: "sched <key> <commute> <cheap_margin> <lookahead> <cap> <is_default>"
         std::lock_guard<std::mutex> lock(g_hints_mu);
         for (const auto &kv : g_sched_measured)
-            fprintf(f, "sched %llx %d %.17g %d %d %d %llu\n", (unsigned long long)kv.first, kv.second.hint.commute, kv.second.hint.cheap_margin,
-                    kv.second.hint.lookahead, kv.second.hint.cap, kv.second.is_default ? 1 : 0, (unsigned long long)kv.second.hint.seed);
+            fprintf(f, "sched %llx %d %.17g %d %d %d %llu%s\n", (unsigned long long)kv.first, kv.second.hint.commute, kv.second.hint.cheap_margin,
+                    kv.second.hint.lookahead, kv.second.hint.cap, kv.second.is_default ? 1 : 0, (unsigned long long)kv.second.hint.seed,
+                    kv.second.hint.defer ? " 1" : ""); // an eighth field only where X gates are deferred: other lines stay what older files hold
     }
     std::lock_guard<std::mutex> lock(g_wisdom_mu);
     for (const auto &kv : g_wisdom) {
@@ -554,7 +572,8 @@ extern "C" long qsim_tune_table_load(const char *path) {
             unsigned long long key = 0, seed = 0;
             RankedVariant rv{};
             int isd = 0;
-            if (sscanf(line + 6, "%llx %d %lf %d %d %d %llu", &key, &rv.hint.commute, &rv.hint.cheap_margin, &rv.hint.lookahead, &rv.hint.cap, &isd, &seed) >= 6 &&
+            if (sscanf(line + 6, "%llx %d %lf %d %d %d %llu %d", &key, &rv.hint.commute, &rv.hint.cheap_margin, &rv.hint.lookahead, &rv.hint.cap, &isd, &seed, &rv.hint.defer) >= 6 &&
+                (rv.hint.defer == 0 || rv.hint.defer == 1) &&
                 rv.hint.cheap_margin > 0 && rv.hint.lookahead >= 0 && rv.hint.lookahead <= 8 && rv.hint.cap >= 0 && rv.hint.cap <= 512) {
                 rv.is_default = isd != 0;
                 rv.hint.seed = seed;
@@ -654,11 +673,30 @@ extern "C" int qsim_plan_passes(const qsim_circuit *c, int fuse, int tile_bits, 
     return QSIM_OK;
 }
 
+static int report_schedule(const std::vector<Pass> &passes, qsim_sched_cb cb, void *user);
+
 extern "C" int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                                      qsim_sched_cb cb, void *user) {
     if (!c || !cb) return fail(QSIM_ERR_ARG, "NULL argument");
     if (fuse < 0 || fuse > 3) return fail(QSIM_ERR_ARG, "fuse level %d not in 0..3", fuse);
-    const std::vector<Pass> passes = schedule(engine_sched_config(c->num_q, fuse, tile_bits, tile_low_bits, tile_max_ops), queue_of(c));
+    return report_schedule(schedule(engine_sched_config(c->num_q, fuse, tile_bits, tile_low_bits, tile_max_ops), queue_of(c)), cb, user);
+}
+
+extern "C" int qsim_schedule_circuit_deferred(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
+                                              qsim_sched_cb cb, void *user, uint64_t *flip_mask) {
+    if (!c || !cb || !flip_mask) return fail(QSIM_ERR_ARG, "NULL argument");
+    if (fuse < 0 || fuse > 3) return fail(QSIM_ERR_ARG, "fuse level %d not in 0..3", fuse);
+    SchedConfig cfg = engine_sched_config(c->num_q, fuse, tile_bits, tile_low_bits, tile_max_ops);
+    cfg.defer_flips = 1;
+    Scheduler sv(cfg);
+    feed(sv, queue_of(c));
+    std::vector<Pass> passes;
+    sv.finish(passes);
+    *flip_mask = sv.residual_flips();
+    return report_schedule(passes, cb, user);
+}
+
+static int report_schedule(const std::vector<Pass> &passes, qsim_sched_cb cb, void *user) {
     int pi = 0;
     std::vector<double> big((size_t)2 * 256 * 256);
     std::vector<cd> full((size_t)256 * 256);

@@ -144,7 +144,18 @@ struct PackMap {
     uint64_t konst;
     int32_t sel[3], to[3];
     int32_t k; // 0: no re-layout
+    // Deferred X gates (SchedConfig::defer_flips): the store goes to perm(x) ^ flip, a mask of OUTPUT index bits the caller sets.
+    // perm(x) is the OR of a per-lane, a per-register and a per-tile part that share no output bit, so the launcher splits the
+    // mask by which part owns each bit (flip_lane, flip_reg; the rest is the tile's) and the kernel XORs each piece once into
+    // that part: nothing is added per amplitude.
+    uint64_t flip, flip_lane, flip_reg;
 };
+// the identity permutation of n index bits: what a pass that only owes flips stores through
+inline PackMap identity_pack_map() {
+    PackMap pm{};
+    pm.seg[0] = ~0ULL;
+    return pm;
+}
 
 struct LaunchCfg {
     hipStream_t stream;

@@ -56,6 +56,7 @@ extern "C" int qsim_rank_comm_create(qsim_rank_comm **out, qsim_state *shard, in
         if (hipMalloc(&c->scratch, (size_t)16 << qsim_num_qubits(shard)) != hipSuccess) { delete c; return cfail(QSIM_ERR_ALLOC, "Malloc error"); }
         c->owns_scratch = true;
     }
+    (void)qsim_set_option(shard, QSIM_OPT_DEFER_FLIPS, 0); // a shard's last pass may have to do an exchange's re-layout
     (void)qsim_set_spare_buffer(shard, c->scratch); // idle between exchanges: the second buffer of the shard's out-of-place passes
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);

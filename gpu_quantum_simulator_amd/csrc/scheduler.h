@@ -175,6 +175,14 @@ struct SchedConfig {
     int commute = 1;
     uint64_t seed = 0; // != 0: ties between equally good candidates (which cluster to admit next, which qubit to swap) are broken pseudo-randomly
                        // instead of in index order — another valid schedule of the same circuit per seed, for the planning step to choose among
+    // Level 3: 1 = X gates are not scheduled at all.  X only relabels the index, and it moves past any later gate exactly
+    // (U X_q = X_q (X_q U X_q), the conjugate being U with rows and columns permuted), so the feed keeps a flip bit per qubit:
+    // an exact X toggles it, an anti-diagonal 2x2 A is fed as the diagonal X A and toggles it, every other gate is fed conjugated
+    // by the flips on its qubits.  What is left at the end is one mask m (Scheduler::residual_flips): the state is
+    // psi[i] = psi'[i ^ m], which the caller owes — the engine has the stores of the last tile pass do it (k_tile PACK).  The X
+    // gates then force no qubit into any tile.  Off by default: the constraints only ever shrink, but the greedy packing does
+    // not turn that into fewer sweeps on every circuit, so it is one more variant for the planning step to price.
+    int defer_flips = 0;
     int track = 0; // 1: every pass lists the gates it absorbed (Pass::src) — the shard planner asks which gates a segment's last pass holds
 };
 
@@ -224,6 +232,9 @@ class Scheduler {
     void finish(const PassSink &sink);
     void finish(std::vector<Pass> &out);
     uint64_t gates_seen() const { return gates_; }
+    // SchedConfig::defer_flips: the index bits still flipped after everything added so far — the caller applies i -> i ^ mask to the
+    // state the passes leave (0 when the option is off).  The deferred statements count with the last pass finish() hands out.
+    uint64_t residual_flips() const { return flips_; }
 
     // fusion algebra, exposed for tests
     static void mul2(const cd a[4], const cd b[4], cd out[4]);     // out = a*b
@@ -240,6 +251,10 @@ class Scheduler {
     std::vector<FusedOp> closed_; // fused ops in a valid execution order
     std::vector<std::vector<uint32_t>> pool_src_, closed_src_; // SchedConfig::track: the gates behind pool_[i] / closed_[i]
     mutable std::vector<uint32_t> cur_src_;                     // ... and behind the pass being emitted
+    uint64_t flips_ = 0;             // SchedConfig::defer_flips: qubits whose X is still owed
+    std::vector<uint32_t> deferred_; // ... and the X statements that produced no cluster, by their order of arrival
+    bool deferring() const { return cfg_.defer_flips != 0 && cfg_.fuse >= 3; }
+    int flips_on(int q_hi, int q_lo) const { return (int)((flips_ >> q_hi & 1ULL) << 1 | (flips_ >> q_lo & 1ULL)); } // as a mask of a 4x4's row index
 
     class PassBuilder; // pass_builder.cpp: the state and the steps of build_passes
     void close(int idx);

@@ -440,7 +440,9 @@ __device__ __forceinline__ void tile_apply_ops(amp_t *lds, uint32_t lds_base, Co
 // and write of the state per exchange) disappears.  perm is a permutation of index BITS, so it splits like the index itself
 // into a per-lane part, a per-register part and a per-tile part, each permuted once; the stores keep their 128-byte runs
 // unless one of the three lowest index bits leaves.
-__device__ __forceinline__ uint64_t pack_perm(const PackMap &pm, uint64_t x) {
+// Deferred X gates ride on the same stores (PackMap::flip): each part is XORed once with its share of the mask.  A flip of
+// index bits 0..2 reverses 16-byte elements inside a 128-byte run; the run stays whole.
+__host__ __device__ __forceinline__ uint64_t pack_perm(const PackMap &pm, uint64_t x) {
     uint64_t o = (x & pm.seg[0]) | ((x & pm.seg[1]) >> 1) | ((x & pm.seg[2]) >> 2) | ((x & pm.seg[3]) >> 3);
 #pragma unroll
     for (int j = 0; j < 3; j++)
@@ -528,6 +530,9 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
         lane_out = pack_perm(pm, lane_off >> kAmpShift) << kAmpShift;
 #pragma unroll
         for (int k = 0; k < APT; k++) k_out[k] = pack_perm(pm, k_off[k] >> kAmpShift) << kAmpShift;
+        lane_out ^= pm.flip_lane << kAmpShift;
+#pragma unroll
+        for (int k = 0; k < APT; k++) k_out[k] ^= pm.flip_reg << kAmpShift; // wave-uniform
     }
     amp_t pf[APT];
     const bool generate = g.from_zero_ket != 0; // wave-uniform
@@ -592,7 +597,7 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
         for (int k = 0; k < APT; k++)
             if (live(k)) so[k] = lds[stage_slot(k)];
         if (PACK) { // (two loops on purpose: one loop over a PACK ? : address leaves the guarded small tiles with other code)
-            const uint64_t sbase = (pack_perm(pm, base) | pm.konst) << kAmpShift; // wave-uniform
+            const uint64_t sbase = ((pack_perm(pm, base) | pm.konst) ^ (pm.flip & ~(pm.flip_lane | pm.flip_reg))) << kAmpShift; // wave-uniform
 #pragma unroll
             for (int k = 0; k < APT; k++)
                 if (live(k)) *reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(vout) + lane_out + (sbase + k_out[k])) = so[k];

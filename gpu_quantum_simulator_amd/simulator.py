@@ -120,9 +120,10 @@ class Circuit:
                  "visited": float(buf[i].visited), "bytes": float(buf[i].bytes), "cost_bytes": float(buf[i].cost_bytes)}
                 for i in range(min(n.value, cap))]
 
-    def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32) -> list:
+    def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, flips: list = None) -> list:
         """Fused blocks in launch order: (pass, kernel_class, kind, qubits, matrix|None, gates_folded); kind is
-        "u1" / "cx" / "u2" ... "u8", qubits most significant first (cx: control, target)."""
+        "u1" / "cx" / "u2" ... "u8", qubits most significant first (cx: control, target).  flips: a list — the schedule with
+        the X gates deferred (qsim_schedule_circuit_deferred); the residual index mask is appended to it."""
         out = []
 
         def cb(_user, pass_i, kclass, kind, qubits, nq, U, folded):
@@ -133,8 +134,13 @@ class Circuit:
                 m = np.ctypeslib.as_array(U, shape=(2 * d * d,)).copy().view(np.complex128).reshape(d, d)
             out.append((pass_i, _lib.K_NAMES[kclass], {1: "u1", 2: "cx", 3: "u2", 4: "u3", 5: "u4", 6: "u5", 7: "u6", 8: "u7", 9: "u8"}[kind], qs, m, folded))
 
-        check(_lib.load().qsim_schedule_circuit(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops,
-                                                _lib.SCHED_CB(cb), None))
+        if flips is None:
+            check(_lib.load().qsim_schedule_circuit(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, _lib.SCHED_CB(cb), None))
+            return out
+        mask = ctypes.c_uint64()
+        check(_lib.load().qsim_schedule_circuit_deferred(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, _lib.SCHED_CB(cb), None,
+                                                         byref(mask)))
+        flips.append(int(mask.value))
         return out
 
     def tile_records(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, f32: bool = False,
@@ -307,7 +313,8 @@ class Simulator(_PauliStrings):
                  "max_pending": _lib.OPT_MAX_PENDING, "tile_max_ops": _lib.OPT_TILE_MAX_OPS,
                  "grid_cap": _lib.OPT_GRID_CAP, "tile_threads": _lib.OPT_TILE_THREADS,
                  "tile_pad_from": _lib.OPT_TILE_PAD_FROM, "debug_tile_order": _lib.OPT_DEBUG_TILE_ORDER, "plan_cache": _lib.OPT_PLAN_CACHE,
-                 "pingpong": _lib.OPT_PINGPONG, "sparse_start": _lib.OPT_SPARSE_START, "debug_plan_key": _lib.OPT_DEBUG_PLAN_KEY}
+                 "pingpong": _lib.OPT_PINGPONG, "sparse_start": _lib.OPT_SPARSE_START, "debug_plan_key": _lib.OPT_DEBUG_PLAN_KEY,
+                 "defer_flips": _lib.OPT_DEFER_FLIPS}
         # tile_low_bits first when shrinking, tile_bits first when growing: keep every intermediate valid
         for key in sorted(options, key=lambda k: k != "tile_low_bits"):
             self.set_option(names[key], options[key])
@@ -458,6 +465,14 @@ class Simulator(_PauliStrings):
         a, b, c = c_uint64(), c_uint64(), c_uint64()
         check(_lib.load().qsim_plan_cache_stats(self._h, byref(a), byref(b), byref(c)))
         return {"plans": int(a.value), "replays": int(b.value), "key_collisions": int(c.value)}
+
+    def deferred_flip_stats(self) -> dict:
+        """qsim_deferred_flip_stats: flushes whose last tile pass applied the deferred X gates' index flip, and flushes that
+        had to run them in a pass of their own."""
+        from ctypes import c_uint64
+        a, b = c_uint64(), c_uint64()
+        check(_lib.load().qsim_deferred_flip_stats(self._h, byref(a), byref(b)))
+        return {"applied": int(a.value), "fallbacks": int(b.value)}
 
     def choose_schedule(self, circuit: Circuit) -> None:
         """qsim_choose_schedule: the schedule choice of the planning step alone (no timing)."""

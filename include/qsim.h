@@ -73,6 +73,13 @@ enum {
     QSIM_OPT_DEBUG_PLAN_KEY = 16,/* test aid, default 0: k != 0 = every flushed queue gets the plan-cache key k, i.e. all circuits collide;
                                   * results must not change — a cached plan is only replayed after its gate list, options and
                                   * support have been compared with the queue's (qsim_plan_cache_stats counts the collisions) */
+    QSIM_OPT_DEFER_FLIPS = 17, /* X gates as an index flip in the stores of a flush's last tile pass instead of scheduled gates: an X moves
+                                * past every later gate exactly (the gate's matrix with rows and columns permuted), so the X gates of a
+                                * queue, and the X factor of every anti-diagonal 2x2, collapse into one mask at its end and force no
+                                * qubit into any tile.  Only a plain flush of an fp64 state in the default tile shape (2^12 amplitudes,
+                                * 512 threads) whose passes run out of place between two buffers of its own can do that; every other
+                                * flush schedules the X gates as before.  0 never, 1 (default) where the planning step chose such a
+                                * schedule for the circuit, 2 wherever possible.  qsim_deferred_flip_stats counts */
     QSIM_OPT_DEBUG_TILE_ORDER = 12,/* measurement aid, default 0: k > 0 = every tile pass walks its high tile bits in a pseudo-random
                                   * order seeded by k (results are unchanged: the order only decides which bits lanes, waves and
                                   * registers walk) */
@@ -147,6 +154,10 @@ int qsim_flush(qsim_state *s); /* schedule + launch everything queued; returns w
  * the cached plan's gate list / options / support differed from the queue's (the key only finds candidates). */
 int qsim_plan_cache_stats(const qsim_state *s, uint64_t *plans, uint64_t *replays, uint64_t *key_collisions);
 int qsim_sync(qsim_state *s);  /* flush, then wait for the stream */
+/* QSIM_OPT_DEFER_FLIPS: *applied = flushes whose last tile pass stored the state with the deferred X gates' index flip; *fallbacks =
+ * flushes that were scheduled with deferred X gates but could not end that way (no tile pass at the end or none before it, a
+ * flipped qubit outside the state's support) and ran the X gates in a pass of their own.  Since the state was created. */
+int qsim_deferred_flip_stats(const qsim_state *s, uint64_t *applied, uint64_t *fallbacks);
 
 /* ---- amplitudes in / out (the reference's final cudaMemcpy D2H, quantum_simulator_naive.cu:193-194) -- */
 int qsim_read(qsim_state *s, uint64_t first, uint64_t count, double *out_re_im);
@@ -650,6 +661,11 @@ typedef void (*qsim_sched_cb)(void *user, int pass, int kernel_class, int kind, 
                               const double *U, int gates_folded);
 int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                           qsim_sched_cb cb, void *user);
+/* The same with the X gates deferred (QSIM_OPT_DEFER_FLIPS; level 3 only): the blocks of a schedule without them, and in *flip_mask
+ * the index bits still flipped at the end — the circuit's state is the replayed one with amplitude i moved to i ^ *flip_mask.  The
+ * deferred statements are counted in gates_folded of the last block reported. */
+int qsim_schedule_circuit_deferred(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
+                                   qsim_sched_cb cb, void *user, uint64_t *flip_mask);
 /* The same schedule (same arguments) as the records the tile kernel reads: `cb` is called for every block of every tile pass,
  * the tile-uniform factors included, with the pass, the geometry the record was encoded under (geom[0..2] = tile bits B, low
  * bits L, number of high bits; high[j] = global bit of tile-local bit L+j, IN ORDER), the block's qubits outside the tile
