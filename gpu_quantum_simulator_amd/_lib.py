@@ -116,6 +116,11 @@ SIGNATURES = {
     "qsim_lanczos_ground": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), _DP, c_long, c_int, c_double, c_int, _DP, _DP, POINTER(c_int), _DP, _DP]),
     "qsim_tridiag_lowest": (c_int, [_DP, _DP, c_int, _DP, _DP]),
     "qsim_lanczos_plan": (c_int, [POINTER(c_uint64), c_long, c_int, c_int, POINTER(c_long), POINTER(c_long), _DP]),
+    "qsim_reduced_density": (c_int, [c_void_p, POINTER(c_int), c_int, _DP]),
+    "qsim_reduced_density_max_qubits": (c_int, []),
+    "qsim_reduced_density_plan": (c_int, [POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64),
+                                          POINTER(c_long)]),
+    "qsim_density_sweeps_launched": (c_uint64, []),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

@@ -542,6 +542,45 @@ class Simulator(_PauliStrings):
         check(_lib.load().qsim_gather_masked(self._h, base, lo_mask, _dp(out)))
         return out.view(np.complex128)
 
+    # -- subsystems (single states only: a Cluster has no counterpart)
+    def reduced_density_matrix(self, qubits) -> np.ndarray:
+        """rho_A = Tr_B |psi><psi| for A = `qubits` (at most 5, distinct, any order) as a (2^k, 2^k) complex128 array; bit j of a
+        row or column index is qubits[j].  One read-only sweep of the state on the device (qsim_reduced_density); exactly
+        Hermitian, fp64 sums in both precisions, equal calls return equal bits.  Not normalised: its trace is norm2()."""
+        qs = [int(q) for q in qubits]
+        arr = (c_int * max(len(qs), 1))(*qs)
+        out = np.zeros(2 << (2 * len(qs)) if len(qs) <= 5 else 2, dtype=np.float64)  # more than 5: the library refuses
+        check(_lib.load().qsim_reduced_density(self._h, arr, len(qs), _dp(out)))
+        return out.view(np.complex128).reshape(1 << len(qs), 1 << len(qs))
+
+    def marginal_probabilities(self, qubits) -> np.ndarray:
+        """The joint distribution of `qubits` (distinct, any order) as 2^k float64, bit j of an outcome being qubits[j].  Up to 5
+        qubits: the diagonal of reduced_density_matrix; more: block_prob_masked over the subset, reordered here."""
+        qs = [int(q) for q in qubits]
+        k = len(qs)
+        if k <= 5:
+            return np.ascontiguousarray(np.real(np.diagonal(self.reduced_density_matrix(qs))))
+        if len(set(qs)) != k or any(q < 0 or q >= self.num_qubits for q in qs):
+            raise ValueError(f"marginal_probabilities: {qs} are not distinct qubits of a register of {self.num_qubits}")
+        mask = sum(1 << q for q in qs)
+        p = self.block_prob_masked(mask, ((1 << self.num_qubits) - 1) & ~mask)  # outcome bits in ascending qubit order
+        rank = {q: r for r, q in enumerate(sorted(qs))}
+        return np.ascontiguousarray(p.reshape((2,) * k).transpose([k - 1 - rank[q] for q in reversed(qs)]).reshape(-1))
+
+    def purity(self, qubits) -> float:
+        """Tr rho_A^2 for the reduced density matrix of `qubits`, normalised by its trace (1 for a pure product, 2^-k fully mixed)."""
+        rho = self.reduced_density_matrix(qubits)
+        tr = float(np.real(np.trace(rho)))
+        return float(np.real(np.sum(rho * rho.T))) / (tr * tr)  # Tr rho^2 = sum |rho_ab|^2 for a Hermitian rho
+
+    def entanglement_entropy(self, qubits, base: float = 2) -> float:
+        """The von Neumann entropy -Tr rho_A log rho_A of `qubits` against the rest, in units of log `base` (bits by default), from
+        the eigenvalues of the small matrix (normalised by its trace); eigenvalues <= 0 are rounding and are left out."""
+        rho = self.reduced_density_matrix(qubits)
+        w = np.linalg.eigvalsh(rho / np.real(np.trace(rho)))
+        w = w[w > 0.0]
+        return float(-np.sum(w * np.log(w)) / np.log(base))
+
     def pack_bits(self, bits: Sequence[int], dst_ptr: int) -> None:
         """Shard re-layout ahead of a global<->local qubit exchange (qsim_pack_bits)."""
         arr = (c_int * len(bits))(*bits)

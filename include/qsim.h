@@ -333,6 +333,35 @@ int qsim_tridiag_lowest(const double *alphas, const double *betas, int m, double
  * other sweeps (2: alpha and the update) and the state volumes read and written by all of them.  QSIM_ERR_ARG for max_steps < 1. */
 int qsim_lanczos_plan(const uint64_t *ham_x, long num_ham, int max_steps, int want_vector, long *sum_sweeps_per_step, long *other_sweeps_per_step,
                       double *volumes_per_step);
+/* ---- reduced density matrices of qubit subsets, one read-only sweep (new) ----
+ * rho[a][a'] = sum_b psi(a,b) conj(psi(a',b)); out: 4^k complex, row-major, (re, im).  Bit j of a row/column index is qubit qubits[j]
+ * (qubits[0] = LSB), any order, distinct.  k = 0: the 1x1 matrix (norm^2).  k <= qsim_reduced_density_max_qubits().
+ * The call settles the state first (queued gates are launched, a lazily held |0...0> or a partial support is written out), leaves
+ * the state's bits alone and waits for its result.  One sweep reads the state once, whatever the subset: the 4^k sums are the
+ * accumulator tiles of the fp64 matrix instruction, on a sorted subset of three to five qubits — fewer are padded with the lowest
+ * index bits not in the subset and the padding is traced out on the host, which also permutes rows and columns into the caller's
+ * order.  A register too small for a tile (fewer than five qubits, or fewer than four environments) takes a plain one-workgroup
+ * kernel instead; qsim_reduced_density_plan says which.  The scratch of a sweep is allocated per call, before anything is launched.
+ * The sums are fp64 in both precisions — fp32 amplitudes are widened on load, so a product of two floats is exact — and are added in
+ * a fixed order: equal calls return equal bits.  The grid follows the rule of the other reducing sweeps and QSIM_OPT_GRID_CAP does
+ * not apply (it would change the order).  The output is Hermitian bit for bit: the lower triangle is filled from the upper one and
+ * the diagonal's imaginary parts are exactly 0.  Sweeps are NOT counted in the qsim_stats record (no QSIM_K_* class of their own);
+ * qsim_density_sweeps_launched() counts them.  A shard that holds nothing (qsim_holds_nothing) gives zeros and launches no sweep.
+ * QSIM_ERR_ARG, nothing launched: a NULL state or output, qubits NULL with k > 0, k < 0, k above the maximum or above the register's
+ * qubit count, a qubit outside the register, a repeated qubit.
+ * Single states only, fp64 and fp32: there is NO cluster counterpart.  Out of scope: more than five qubits (the accumulators no
+ * longer fit one wave) and any call that writes the state (collapse). */
+int qsim_reduced_density(qsim_state *s, const int *qubits, int k, double *out_re_im);
+int qsim_reduced_density_max_qubits(void);   /* 5 */
+/* Host only, no device: what the call above does on a register of num_q qubits held in precision_bits (64 or 32) — *path 1: the
+ * matrix path, 0: the plain kernel; *padded_k and *kernel_mask: the subset the kernel works on (path 0: the caller's, nothing is
+ * padded); *units_visited: the 16-byte units (one fp64 amplitude, two fp32 amplitudes) the sweep reads, the whole state once;
+ * *trips_per_workgroup_at_grid_cap: the trips of a workgroup's loop when the grid is at its cap of 1024 workgroups (a device that
+ * holds fewer at once makes more).  QSIM_ERR_ARG as above, and for num_q outside [0, 40], precision_bits other than 64 or 32, a NULL
+ * result pointer. */
+int qsim_reduced_density_plan(const int *qubits, int k, int num_q, int precision_bits, int *path, int *padded_k, uint64_t *kernel_mask,
+                              uint64_t *units_visited, long *trips_per_workgroup_at_grid_cap);
+uint64_t qsim_density_sweeps_launched(void); /* process-wide counter, as qsim_pauli_rotation_sweeps_launched */
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */

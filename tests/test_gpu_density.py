@@ -1,0 +1,286 @@
+"""Reduced density matrices of qubit subsets on the device (Simulator.reduced_density_matrix, qsim_reduced_density;
+csrc/density.hip, csrc/density.cpp).
+
+The checker is density_ref.reduced_density (a tensordot, pinned on the CPU by tests/test_density_cpu.py) on the amplitudes READ
+BACK from the same state — for an fp32 state `read()` is the exact widened contents.  Tolerance 1e-10 absolute, the project's
+parity tolerance, in both precisions, by the argument of tests/test_gpu_expectation.py: a unit-norm state, products exact (fp32
+amplitudes, widened) or once rounded (fp64), only the order of the fp64 additions differs from numpy's, and any index or pairing
+mistake shows at 1e-2.  Every comparison also asks for exact Hermiticity, an exactly zero imaginary diagonal and the trace of
+norm2().  Sizes: the plain path (n <= 4), both sides of the switch to the matrix path for each padded subset size (taken from the
+plan call), n = 13 for the matrix path's subsets, and n = 22 (fp64) / 23 (fp32), where the plan call reports at least two trips
+per workgroup."""
+import ctypes
+from ctypes import byref, c_int, c_long, c_uint64
+
+import numpy as np
+import pytest
+
+import density_ref
+from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd._lib import QsimError
+from helpers import np_apply_1q, np_apply_cx, random_unitary
+from pauli_rot_ref import rand_state
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-10
+PRECISIONS = [64, 32]
+H = np.array([[1, 1], [1, -1]]) / np.sqrt(2.0)
+
+
+def _plan(qubits, n, precision):
+    arr = (c_int * max(len(qubits), 1))(*qubits)
+    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
+    rc = _lib.load().qsim_reduced_density_plan(arr, len(qubits), n, precision, byref(path), byref(padded), byref(mask), byref(units), byref(trips))
+    assert rc == _lib.QSIM_OK
+    return dict(path=path.value, padded_k=padded.value, mask=mask.value, trips=trips.value)
+
+
+def _check(sim, psi, qubits, label=""):
+    """rho of `qubits` against the checker on psi (the state as read back), and what every result owes."""
+    got = sim.reduced_density_matrix(qubits)
+    want = density_ref.reduced_density(psi, qubits)
+    k = len(qubits)
+    assert got.shape == (1 << k, 1 << k) and got.dtype == np.complex128
+    worst = float(np.max(np.abs(got - want)))
+    print(f"{label} n={sim.num_qubits} p{sim.precision} qubits={list(qubits)}: max abs err {worst:.3e}")
+    assert worst < TOL
+    assert np.array_equal(got, got.conj().T) and np.array_equal(np.imag(np.diagonal(got)), np.zeros(1 << k))
+    assert not np.any(np.signbit(np.imag(np.diagonal(got))))
+    assert abs(float(np.real(np.trace(got))) - sim.norm2()) < TOL
+    return got
+
+
+def _sim_with(n, precision, seed):
+    sim = Simulator(n, precision=precision)
+    sim.write(rand_state(n, seed))
+    return sim, sim.read()
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 4])
+def test_plain_path_every_subset(n, precision):
+    sim, psi = _sim_with(n, precision, 300 + n)
+    with sim:
+        for k in range(0, n + 1):
+            for qs in density_ref.subsets(n, k):
+                assert _plan(qs, n, precision)["path"] == 0
+                _check(sim, psi, qs, "plain")
+                if k > 1:
+                    _check(sim, psi, qs[::-1], "plain")
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("k", [0, 3, 4, 5])
+def test_path_switch(k, precision):
+    """The smallest register the matrix path takes for this subset size, and the one below it: both from the plan call."""
+    first = next(n for n in range(max(k, 1), 16) if _plan(list(range(k)), n, precision)["path"] == 1)
+    assert first - 1 >= k and _plan(list(range(k)), first - 1, precision)["path"] == 0
+    for n in (first - 1, first):
+        sim, psi = _sim_with(n, precision, 320 + n)
+        with sim:
+            for qs in {tuple(range(k)), tuple(range(n - k, n)), tuple(range(n - 1, n - 1 - k, -1))}:
+                assert _plan(list(qs), n, precision)["path"] == (1 if n == first else 0)
+                _check(sim, psi, list(qs), "switch")
+
+
+N13_SUBSETS = [
+    [],
+    [0], [12], [5],
+    [0, 1], [12, 11], [6, 1], [3, 0],
+    [0, 1, 2], [10, 11, 12], [1, 6, 12], [12, 6, 1], [6, 12, 1], [0, 7, 11], [11, 0, 7],
+    [0, 1, 2, 3], [9, 10, 11, 12], [1, 4, 8, 12], [12, 8, 4, 1], [8, 0, 12, 5], [3, 2, 1, 4],
+    [0, 1, 2, 3, 4], [8, 9, 10, 11, 12], [1, 3, 6, 9, 12], [12, 9, 6, 3, 1], [9, 0, 12, 4, 7], [2, 5, 1, 4, 3],
+]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_matrix_path_subsets(precision):
+    """n = 13, every k: the lowest bits, the highest, spread subsets, descending and shuffled orders, with qubit 0 (the fp32 slot is a
+    row bit) and without (it is an environment bit)."""
+    n = 13
+    sim, psi = _sim_with(n, precision, 313)
+    with sim:
+        for qs in N13_SUBSETS:
+            assert _plan(qs, n, precision)["path"] == 1
+            _check(sim, psi, qs, "matrix")
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_looping(precision):
+    """Every workgroup walks its loop at least twice, whatever the device holds at once."""
+    n = 22 if precision == 64 else 23
+    sim, psi = _sim_with(n, precision, 322)
+    with sim:
+        for qs in ([0, 1, 2], [n - 3, n - 2, n - 1], [0, 1, 2, 3, 4], [n - 5, n - 4, n - 3, n - 2, n - 1], [n - 2, 3, n - 1, 7, 1]):
+            p = _plan(qs, n, precision)
+            assert p["path"] == 1 and p["trips"] >= 2
+            _check(sim, psi, qs, "looping")
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_equal_bits_and_state_untouched(precision):
+    n = 16
+    sim, _ = _sim_with(n, precision, 316)
+    with sim:
+        before = sim.read().view(np.uint64).copy()
+        for qs in ([2, 9, 15], [0, 5, 6, 11, 14], [1]):
+            first = sim.reduced_density_matrix(qs)
+            second = sim.reduced_density_matrix(qs)
+            assert np.array_equal(first.view(np.uint64), second.view(np.uint64))
+            for cap in (1, 7):                                   # the option does not apply: the sums keep their order
+                sim.set_option(_lib.OPT_GRID_CAP, cap)
+                assert np.array_equal(sim.reduced_density_matrix(qs).view(np.uint64), first.view(np.uint64))
+            sim.set_option(_lib.OPT_GRID_CAP, 0)
+            assert np.max(np.abs(first)) > 1e-3
+        assert np.array_equal(sim.read().view(np.uint64), before)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_fresh_state_then_a_circuit(precision):
+    n = 13
+    with Simulator(n, precision=precision) as sim:               # never touched: |0...0> is still held lazily
+        for qs in ([0], [3, 12], [12, 0, 5, 6]):
+            want = np.zeros((1 << len(qs), 1 << len(qs)), dtype=np.complex128)
+            want[0, 0] = 1.0
+            assert np.array_equal(sim.reduced_density_matrix(qs), want)
+        rng = np.random.default_rng(8)
+        us = [random_unitary(2, rng) for _ in range(n)]
+        for q in range(n):
+            sim.apply_1q(us[q], q)
+        sim.apply_cx(0, 12)
+        psi = np.zeros(1 << n, dtype=np.complex128)
+        psi[0] = 1.0
+        for q in range(n):
+            psi = np_apply_1q(psi, n, us[q], q)
+        psi = np_apply_cx(psi, n, 0, 12)
+        got = sim.read()
+        assert np.max(np.abs(got - psi)) < (TOL if precision == 64 else 1e-5)
+        _check(sim, got, [12, 0, 5, 6], "after the circuit")
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_queued_gates_are_applied_first(precision):
+    n = 13
+    sim, _ = _sim_with(n, precision, 331)
+    with sim:
+        rng = np.random.default_rng(9)
+        for q in (0, 4, 12):
+            sim.apply_1q(random_unitary(2, rng), q)
+        sim.apply_cx(12, 3)                                      # queued: nothing has been flushed or waited for
+        got = sim.reduced_density_matrix([12, 3, 0])
+        psi = sim.read()                                         # the state with the gates applied
+        assert np.max(np.abs(got - density_ref.reduced_density(psi, [12, 3, 0]))) < TOL
+        _check(sim, psi, [4, 12], "queued")
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_partial_support(precision):
+    """A few h on low qubits of a fresh state: the support is partial when the call settles it; rho outside the support is |0><0|."""
+    n = 13
+    with Simulator(n, precision=precision) as sim:
+        for q in (0, 1, 2):
+            sim.apply_1q(H, q)
+        sim.flush()
+        got = sim.reduced_density_matrix([9, 12, 10])
+        psi = sim.read()
+        assert np.max(np.abs(got - density_ref.reduced_density(psi, [9, 12, 10]))) < TOL
+        assert abs(got[0, 0] - 1.0) < 1e-6 and np.count_nonzero(got) == 1  # three h in fp32 leave the norm a few 1e-8 off 1
+        _check(sim, psi, [1, 11, 0], "partial")
+        _check(sim, psi, [12, 11, 10, 9, 8], "partial")
+    with Simulator(n, precision=precision) as sim:               # the same with the subset asked for while the support is still partial
+        for q in (0, 1, 2):
+            sim.apply_1q(H, q)
+        sim.flush()
+        got = sim.reduced_density_matrix([1, 11, 0])
+        assert np.max(np.abs(got - density_ref.reduced_density(sim.read(), [1, 11, 0]))) < TOL
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_a_shard_that_holds_nothing(precision):
+    lib = _lib.load()
+    with Simulator(13, precision=precision) as sim:
+        sim.reset(holds_index0=False)
+        before = lib.qsim_density_sweeps_launched()
+        for qs in ([], [0], [12, 3, 4], [0, 1, 2, 3, 4]):
+            assert np.array_equal(sim.reduced_density_matrix(qs), np.zeros((1 << len(qs), 1 << len(qs))))
+        assert lib.qsim_density_sweeps_launched() == before
+        sim.reset()
+        sim.reduced_density_matrix([12, 3, 4])
+        assert lib.qsim_density_sweeps_launched() == before + 1
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_ghz_and_product_states(precision):
+    n = 6
+    with Simulator(n, precision=precision) as sim:               # GHZ: any proper subset is half |0..0><0..0|, half |1..1><1..1|
+        sim.apply_1q(H, 0)
+        for q in range(1, n):
+            sim.apply_cx(0, q)
+        for k in range(1, 6):
+            for qs in (list(range(k)), list(range(n - k, n)), [5, 2, 0, 3, 1][:k]):
+                assert abs(sim.entanglement_entropy(qs) - 1.0) < 1e-6 and abs(sim.purity(qs) - 0.5) < 1e-6
+                assert abs(sim.entanglement_entropy(qs, base=np.e) - np.log(2.0)) < 1e-6
+    n = 13
+    rng = np.random.default_rng(21)
+    with Simulator(n, precision=precision) as sim:
+        for q in range(n):
+            sim.apply_1q(random_unitary(2, rng), q)
+        for qs in ([0], [12, 5], [3, 4, 9], [0, 11, 2, 7, 12]):
+            assert abs(sim.purity(qs) - 1.0) < 1e-5 and abs(sim.entanglement_entropy(qs)) < 1e-3
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_two_qubits_from_pauli_expectations(precision):
+    """rho = 2^-k sum_P <P> P over the 16 strings on the subset, <P> from expectation_terms on the same state."""
+    n = 13
+    sigma = {"I": np.eye(2), "X": np.array([[0, 1], [1, 0]]), "Y": np.array([[0, -1j], [1j, 0]]), "Z": np.diag([1.0, -1.0])}
+    sim, _ = _sim_with(n, precision, 341)
+    with sim:
+        for q0, q1 in ((0, 1), (12, 4), (7, 0)):
+            letters = [(a, b) for a in "IXYZ" for b in "IXYZ"]
+            texts = [" ".join(f"{l}{q}" for l, q in ((a, q0), (b, q1)) if l != "I") for a, b in letters]
+            values = sim.expectation_terms(texts)
+            want = sum(v * np.kron(sigma[b], sigma[a]) for v, (a, b) in zip(values, letters)) / 4.0  # qubits[0] is the low bit
+            got = sim.reduced_density_matrix([q0, q1])
+            assert np.max(np.abs(got - want)) < TOL
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_marginal_probabilities(precision):
+    n = 13
+    sim, psi = _sim_with(n, precision, 351)
+    with sim:
+        for qs in ([4, 0, 12], [1, 2, 3], [11, 0, 7, 3, 12, 5, 9, 2], [0, 1, 2, 3, 4, 5, 6, 7], [12, 11, 10, 9, 8, 7, 6, 5]):
+            got = sim.marginal_probabilities(qs)
+            idx = np.arange(1 << n)
+            outcome = sum(((idx >> q) & 1) << j for j, q in enumerate(qs))  # bit j of an outcome is qubit qs[j]
+            want = np.bincount(outcome, weights=np.abs(psi) ** 2, minlength=1 << len(qs))
+            assert got.shape == (1 << len(qs),) and got.dtype == np.float64
+            assert np.max(np.abs(got - density_ref.marginal(psi, qs))) < TOL
+            assert np.max(np.abs(got - want)) < TOL
+        with pytest.raises(ValueError):
+            sim.marginal_probabilities([0, 1, 2, 3, 4, 5, 5])
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_errors(precision):
+    lib = _lib.load()
+    out = (ctypes.c_double * 2048)()
+    with Simulator(6, precision=precision) as sim:
+        sim.write(rand_state(6, 1))
+        before = lib.qsim_density_sweeps_launched()
+        call = lambda qs, k=None: lib.qsim_reduced_density(sim._h, (c_int * max(len(qs), 1))(*qs), len(qs) if k is None else k, out)
+        assert call([0, 1]) == _lib.QSIM_OK
+        assert lib.qsim_density_sweeps_launched() == before + 1
+        for qs in ([0, 0], [6], [-1], [2, 5, 2], [0, 1, 2, 3, 4, 5]):
+            assert call(qs) == _lib.ERR_ARG
+        assert call([0], -1) == _lib.ERR_ARG
+        assert lib.qsim_reduced_density(sim._h, None, 1, out) == _lib.ERR_ARG
+        assert lib.qsim_reduced_density(sim._h, None, 0, out) == _lib.QSIM_OK
+        assert lib.qsim_reduced_density(sim._h, (c_int * 1)(0), 1, None) == _lib.ERR_ARG
+        assert lib.qsim_reduced_density(None, (c_int * 1)(0), 1, out) == _lib.ERR_ARG
+        assert lib.qsim_density_sweeps_launched() == before + 2  # nothing was launched for a refused call
+        with pytest.raises(QsimError):
+            sim.reduced_density_matrix([0, 1, 2, 3, 4, 5])
+    with Simulator(2, precision=precision) as sim:
+        assert lib.qsim_reduced_density(sim._h, (c_int * 3)(0, 1, 1), 3, out) == _lib.ERR_ARG  # k > n
