@@ -121,6 +121,13 @@ SIGNATURES = {
     "qsim_reduced_density_plan": (c_int, [POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64),
                                           POINTER(c_long)]),
     "qsim_density_sweeps_launched": (c_uint64, []),
+    "qsim_apply_matrix": (c_int, [c_void_p, _DP, POINTER(c_int), c_int, POINTER(c_int), c_int]),
+    "qsim_apply_matrix_max_qubits": (c_int, []),
+    "qsim_apply_matrix_plan": (c_int, [POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64),
+                                       POINTER(c_uint64), POINTER(c_long)]),
+    "qsim_apply_matrix_operand": (c_int, [_DP, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, _DP, POINTER(c_int), POINTER(c_int),
+                                          POINTER(c_int)]),
+    "qsim_matrix_sweeps_launched": (c_uint64, []),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

@@ -11,6 +11,7 @@
 //   state_algebra.cpp  calls on several states: copy, inner product, linear combination (the host side of combine.hip)
 //   lanczos.cpp        the Lanczos ground-state solver on top of pauli.cpp's H application and the two above
 //   density.cpp        reduced density matrices of qubit subsets: the plan, the call, from tiles to rho (the host side of density.hip; density.h)
+//   matrix.cpp         dense matrices on up to five targets under controls: the plan, the operand, the call (the host side of matrix.hip; matrix.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 

@@ -453,6 +453,21 @@ class Simulator(_PauliStrings):
     def apply_2q(self, U, q_hi: int, q_lo: int) -> None:
         check(_lib.load().qsim_apply_2q(self._h, _dp(_mat(U, 4)), q_hi, q_lo))
 
+    def apply_matrix(self, U, targets, controls=()) -> None:
+        """The (2^k, 2^k) matrix `U` on `targets` (at most 5, distinct, any order; bit j of a row or column index is targets[j])
+        where every qubit of `controls` (any number, disjoint from the targets) is 1, the identity elsewhere.  Any complex matrix:
+        a unitary, a Kraus operator, a projector — nothing checks unitarity; k = 0: a complex scalar on the control subspace.
+        One in-place sweep of 2^-len(controls) of the state on the device (qsim_apply_matrix), launched after the queued gates
+        and not waited for; it does not pass through the gate queue.  Single states only: a Cluster has no such method, sharded
+        states have no controlled operations."""
+        ts, cs = [int(q) for q in targets], [int(q) for q in controls]
+        m = np.asarray(U, dtype=np.complex128)
+        dim = 1 << min(len(ts), 5)
+        if len(ts) > 5 or m.size != dim * dim or m.ndim > 2 or (m.ndim == 2 and m.shape != (dim, dim)):
+            raise ValueError(f"apply_matrix: at most 5 targets and a matrix of shape (2^k, 2^k); got {len(ts)} targets and shape {m.shape}")
+        flat = np.ascontiguousarray(m.reshape(-1)).view(np.float64)
+        check(_lib.load().qsim_apply_matrix(self._h, _dp(flat), (c_int * max(len(ts), 1))(*ts), len(ts), (c_int * max(len(cs), 1))(*cs), len(cs)))
+
     def run(self, circuit: Circuit, first: int = 0, count: int = -1) -> None:
         check(_lib.load().qsim_run_circuit(self._h, circuit._h, first, count))
 

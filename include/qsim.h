@@ -362,6 +362,44 @@ int qsim_reduced_density_max_qubits(void);   /* 5 */
 int qsim_reduced_density_plan(const int *qubits, int k, int num_q, int precision_bits, int *path, int *padded_k, uint64_t *kernel_mask,
                               uint64_t *units_visited, long *trips_per_workgroup_at_grid_cap);
 uint64_t qsim_density_sweeps_launched(void); /* process-wide counter, as qsim_pauli_rotation_sweeps_launched */
+/* ---- dense matrices on up to five target qubits, under controls, one in-place sweep (new) ----
+ * psi <- (1 - Pi) psi + Pi (U on targets) psi, Pi = the projector on "every control qubit is 1".
+ * U: 2^k x 2^k, row-major, (re, im) doubles; bit j of a row/column index is targets[j] (targets[0] = LSB, any order, as
+ * qsim_reduced_density).  Any complex matrix: nothing checks unitarity (a Kraus operator, a projector).  k in [0, 5]
+ * (qsim_apply_matrix_max_qubits); k == 0 is the complex scalar U[0] on the control subspace.  controls: any number of qubits, disjoint
+ * from the targets; num_controls == 0 is the plain gate.  Control values of 0 are out of scope (conjugate with X).
+ * The call settles the state first (queued gates are launched, a lazily held |0...0> or a partial support is written out), launches
+ * ONE sweep on the state's stream that reads and writes 2^-c of the state once for c controls, and returns without waiting.  It does
+ * not go through the gate queue or the fusion scheduler.  The sweep runs on the matrix cores: on a sorted subset of three to five
+ * qubits (fewer targets are padded with the lowest index bits that are neither targets nor controls, U (x) 1 on the host) the real
+ * matrix [[Re U, -Im U], [Im U, Re U]] meets [Re psi; Im psi] of 16 environments per fp64 matrix instruction; every lane stores the
+ * rows it loaded, so there is no shared memory and no barrier, and every amplitude is written by one wave in a fixed order: equal
+ * calls give equal bits whatever QSIM_OPT_GRID_CAP is.  fp32 amplitudes are widened, the sums are fp64 and each result is rounded
+ * once.  A register with fewer than 16 environment units takes a plain one-workgroup kernel instead; qsim_apply_matrix_plan says
+ * which.  Amplitudes outside the control subspace keep their bits.  Sweeps are NOT counted in the qsim_stats record;
+ * qsim_matrix_sweeps_launched counts them.  A shard that holds nothing (qsim_holds_nothing) stays as it is and launches no sweep.
+ * QSIM_ERR_ARG, nothing launched: a NULL state or U, targets NULL with k > 0, controls NULL with num_controls > 0, a negative count,
+ * k above the maximum or above the register's qubit count, a qubit outside the register, a repeated qubit, a control among the
+ * targets, a non-finite entry of U.
+ * Single states only, fp64 and fp32: there is NO cluster counterpart (sharded states have no controlled operations).  Out of scope:
+ * more than five targets, gradients through these gates. */
+int qsim_apply_matrix(qsim_state *s, const double *U, const int *targets, int k, const int *controls, int num_controls);
+int qsim_apply_matrix_max_qubits(void);      /* 5 */
+/* Host only, no device: what the call above does on a register of num_q qubits held in precision_bits (64 or 32) — *path 1: the
+ * matrix path, 0: the plain kernel; *padded_k and *kernel_mask: the sorted subset the kernel works on (path 0: the targets, nothing
+ * is padded); *units: the 16-byte units (one fp64 amplitude, two fp32 amplitudes) the sweep reads and writes, 2^-c of the state
+ * (fp32 with a control on qubit 0: the odd amplitude of 2^(1-c) of the units); *trips_per_workgroup: the trips of a workgroup's loop
+ * at the default grid's cap (1024 workgroups, 512 for five qubits; a device that holds fewer at once makes more).  QSIM_ERR_ARG as
+ * above, and for num_q outside [0, 40], precision_bits other than 64 or 32, a NULL result pointer. */
+int qsim_apply_matrix_plan(const int *targets, int k, const int *controls, int num_controls, int num_q, int precision_bits, int *path,
+                           int *padded_k, uint64_t *kernel_mask, uint64_t *units, long *trips_per_workgroup);
+/* Host only: the real operand M the matrix path's kernel is handed for this call (*rows x *rows, row-major, *rows = 2^(padded_k + 1),
+ * at most 64) and which row of [Re psi; Im psi] each of its rows and columns is: row_amp[r] an index over the sorted kernel_mask,
+ * row_part[r] 0 Re, 1 Im.  Lane l of a wave supplies and receives the rows r with r mod 4 == l / 16.  The plain path has no operand:
+ * *rows = 0.  QSIM_ERR_ARG as above. */
+int qsim_apply_matrix_operand(const double *U, const int *targets, int k, const int *controls, int num_controls, int num_q,
+                              int precision_bits, double *M, int *row_amp, int *row_part, int *rows);
+uint64_t qsim_matrix_sweeps_launched(void);  /* process-wide counter, as qsim_density_sweeps_launched */
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */

@@ -1,0 +1,262 @@
+"""Dense matrices on target qubits under controls, checked on the CPU: the checker of tests/test_gpu_matrix.py (matrix_ref.apply_matrix)
+against dense Kronecker operators and the helpers of the 1q / 2q / cx tests, the host-only plan call (qsim_apply_matrix_plan) against
+its rules, and the operand the kernel is handed (qsim_apply_matrix_operand) pushed through a numpy emulation of the matrix
+instruction's documented operand and result maps."""
+import itertools
+from ctypes import POINTER, byref, c_double, c_int, c_long, c_uint64
+
+import numpy as np
+import pytest
+
+import matrix_ref
+from gpu_quantum_simulator_amd import _lib
+from helpers import np_apply_1q, np_apply_2q, np_apply_cx, random_unitary
+from pauli_rot_ref import rand_state
+
+NEW_NAMES = ("qsim_apply_matrix", "qsim_apply_matrix_max_qubits", "qsim_apply_matrix_plan", "qsim_apply_matrix_operand", "qsim_matrix_sweeps_launched")
+X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
+P1 = np.diag([0.0, 1.0]).astype(np.complex128)
+
+
+def _ints(values):
+    return (c_int * max(len(values), 1))(*values)
+
+
+def _c_plan(targets, controls, n, bits, k=None, c=None, null_targets=False, null_controls=False):
+    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
+    rc = _lib.load().qsim_apply_matrix_plan(None if null_targets else _ints(targets), len(targets) if k is None else k,
+                                            None if null_controls else _ints(controls), len(controls) if c is None else c, n, bits,
+                                            byref(path), byref(padded), byref(mask), byref(units), byref(trips))
+    return rc, dict(path=path.value, padded_k=padded.value, mask=mask.value, units=units.value, trips=trips.value)
+
+
+def _model(targets, controls, n, f32):
+    """The plan's rules, restated: pad to 3 qubits with the lowest bits that are free, the matrix path with 16 environment units."""
+    k, c = len(targets), len(controls)
+    kk = max(k, 3)
+    free = [q for q in range(n) if q not in targets and q not in controls]
+    subset = sorted(list(targets) + free[:kk - k])
+    path = 0
+    if len(subset) == kk:
+        slot_is_env = f32 and 0 not in subset and 0 not in controls
+        path = 1 if n - kk - c - (1 if slot_is_env else 0) >= 4 else 0
+    if not path:
+        subset = sorted(targets)
+    units = max(1, (1 << (n - c)) >> (1 if f32 and 0 not in controls else 0))
+    return dict(path=path, padded_k=len(subset), mask=sum(1 << q for q in subset), units=units)
+
+
+def test_signatures_have_the_new_names():
+    for name in NEW_NAMES:
+        assert name in _lib.SIGNATURES
+    assert _lib.load().qsim_apply_matrix_max_qubits() == 5
+
+
+# ---- the checker ----------------------------------------------------------------------------------------------------------------------
+def test_checker_against_kronecker_operators():
+    """U = u_(k-1) (x) ... (x) u_0 on targets in every order is the kron over the register of u_j on qubit targets[j]; under controls
+    the operator is (1 - Pi) + Pi K with Pi the kron of |1><1| on the controls."""
+    rng = np.random.default_rng(41)
+    for n in range(0, 6):
+        psi = rand_state(n, 400 + n)
+        for k in range(0, n + 1):
+            for targets in itertools.permutations(range(n), k):
+                us = [random_unitary(2, rng) for _ in range(k)]
+                U = np.array([[1.0 + 0j]])
+                for u in us:                                     # later factors are higher bits of the matrix index
+                    U = np.kron(u, U)
+                rest = [q for q in range(n) if q not in targets]
+                for controls in ([], rest[:1], rest[-2:]):
+                    K, Pi = np.array([[1.0 + 0j]]), np.array([[1.0 + 0j]])
+                    for q in range(n):                           # qubit q = index bit q: later factors are higher bits
+                        K = np.kron(us[targets.index(q)] if q in targets else np.eye(2), K)
+                        Pi = np.kron(P1 if q in controls else np.eye(2), Pi)
+                    want = (np.eye(1 << n) - Pi + Pi @ K) @ psi
+                    for checker in (matrix_ref.apply_matrix, matrix_ref.apply_matrix_gather):
+                        assert np.max(np.abs(checker(psi, U, targets, controls) - want)) < 1e-13, (n, targets, controls)
+
+
+def test_checker_against_dense_operator_for_entangling_matrices():
+    rng = np.random.default_rng(42)
+    for n in range(1, 6):
+        psi = rand_state(n, 410 + n)
+        for k in range(0, n + 1):
+            for targets in itertools.permutations(range(n), k):
+                U = rng.standard_normal((1 << k, 1 << k)) + 1j * rng.standard_normal((1 << k, 1 << k))   # not unitary
+                rest = [q for q in range(n) if q not in targets]
+                for controls in ([], rest[:1], rest):
+                    want = matrix_ref.dense_operator(n, U, targets, controls) @ psi
+                    for checker in (matrix_ref.apply_matrix, matrix_ref.apply_matrix_gather):
+                        assert np.max(np.abs(checker(psi, U, targets, controls) - want)) < 1e-12, (n, targets, controls)
+    # the two checkers on a larger register, in both precisions
+    psi = rand_state(12, 430)
+    for targets, controls in (([11, 0, 5], [3]), ([2, 9, 4, 7, 1], []), ([], [0, 11]), ([6], [5, 7]), ([10, 11], [0])):
+        U = rng.standard_normal((1 << len(targets), 1 << len(targets))) + 1j * rng.standard_normal((1 << len(targets), 1 << len(targets)))
+        U /= np.linalg.norm(U, 2)
+        assert np.max(np.abs(matrix_ref.apply_matrix(psi, U, targets, controls) - matrix_ref.apply_matrix_gather(psi, U, targets, controls))) < 1e-14
+        a32, b32 = (f(psi, U, targets, controls, dtype=np.complex64) for f in (matrix_ref.apply_matrix, matrix_ref.apply_matrix_gather))
+        assert a32.dtype == np.complex64 and np.max(np.abs(a32 - b32)) < 1e-6
+
+
+def test_checker_against_the_gate_helpers():
+    rng = np.random.default_rng(43)
+    n = 5
+    psi = rand_state(n, 420)
+    for q in range(n):
+        u = random_unitary(2, rng)
+        assert np.max(np.abs(matrix_ref.apply_matrix(psi, u, [q]) - np_apply_1q(psi, n, u, q))) < 1e-14
+    for q_lo, q_hi in itertools.combinations(range(n), 2):
+        u = random_unitary(4, rng)
+        assert np.max(np.abs(matrix_ref.apply_matrix(psi, u, [q_lo, q_hi]) - np_apply_2q(psi, n, u, q_hi, q_lo))) < 1e-14
+    cx = np.eye(4)[[0, 3, 2, 1]]                                 # on [control, target]: the control is bit 0 of the matrix index
+    for control, target in itertools.permutations(range(n), 2):
+        want = np_apply_cx(psi, n, control, target)
+        assert np.array_equal(matrix_ref.apply_matrix(psi, X, [target], [control]), want)
+        assert np.array_equal(matrix_ref.apply_matrix(psi, cx, [control, target]), want)
+    # complex64: the matrix and the state are rounded, everything outside the control subspace keeps its bits
+    psi32 = psi.astype(np.complex64)
+    got = matrix_ref.apply_matrix(psi32, random_unitary(4, rng), [3, 0], [2], dtype=np.complex64)
+    assert got.dtype == np.complex64
+    outside = [j for j in range(1 << n) if not j >> 2 & 1]
+    assert np.array_equal(got[outside], psi32[outside]) and not np.array_equal(got, psi32)
+
+
+# ---- the plan call --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bits", [64, 32])
+def test_plan_call_path_padding_and_mask(bits):
+    f32 = bits == 32
+    for n in range(0, 11):
+        for k in range(0, min(n, 5) + 1):
+            sets = list(itertools.combinations(range(n), k))
+            if len(sets) > 6:
+                sets = [sets[0], sets[-1], sets[len(sets) // 2], sets[len(sets) // 3], sets[1], sets[-2]]
+            for ts in sets:
+                rest = [q for q in range(n) if q not in ts]
+                for controls in ([], rest[:1], rest[-1:], rest[:2], rest[1:4]):
+                    for targets in (list(ts), list(ts)[::-1]):
+                        rc, got = _c_plan(targets, controls, n, bits)
+                        want = _model(targets, controls, n, f32)
+                        assert rc == _lib.QSIM_OK, (n, targets, controls)
+                        assert {key: got[key] for key in want} == want, (n, targets, controls, got, want)
+                        pad = [q for q in range(n) if got["mask"] >> q & 1 and q not in targets]
+                        free = [q for q in range(n) if q not in targets and q not in controls]
+                        assert pad == free[:len(pad)] and len(pad) == got["padded_k"] - k   # the lowest free bits, never a control
+                        assert got["trips"] >= 1
+
+
+def test_plan_call_k_from_0_to_5():
+    """n = 12, fp64: every k takes the matrix path on a subset of max(k, 3) qubits."""
+    for k in range(0, 6):
+        targets = list(range(4, 4 + k))
+        rc, got = _c_plan(targets, [], 12, 64)
+        assert rc == _lib.QSIM_OK and got["path"] == 1 and got["padded_k"] == max(k, 3)
+        pad = list(range(0, max(3 - k, 0)))
+        assert got["mask"] == sum(1 << q for q in targets + pad) and got["units"] == 1 << 12
+    assert _c_plan([0, 1], [2, 3], 12, 64)[1]["mask"] == 0b10011  # the padding steps over the controls
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_plan_call_both_sides_of_the_switch(bits):
+    for k in (3, 4, 5):
+        for targets, shift in ((list(range(k)), 0), (list(range(1, k + 1)), 1 if bits == 32 else 0)):
+            first = k + 4 + shift                                # 16 environment units; fp32 without qubit 0: a unit is two environments
+            assert _c_plan(targets, [], first, bits)[1]["path"] == 1 and _c_plan(targets, [], first - 1, bits)[1]["path"] == 0
+            # every control takes a factor of two of environments away
+            assert _c_plan(targets, [first], first + 1, bits)[1]["path"] == 1 and _c_plan(targets, [first - 1], first, bits)[1]["path"] == 0
+    assert _c_plan([1, 2, 3], [0], 8, 32)[1]["path"] == 1        # fp32, the control on qubit 0: the odd slot of 16 units
+    assert _c_plan([1, 2, 3], [0], 7, 32)[1]["path"] == 0
+
+
+def test_plan_call_trips_at_the_looping_sizes():
+    """Where tests/test_gpu_matrix.py expects every workgroup to walk its loop more than once."""
+    for bits, n in ((64, 22), (32, 23)):
+        for targets in ([0, 1, 2], [n - 4, n - 3, n - 2], [0, 1, 2, 3, 4], [n - 6, n - 5, n - 4, n - 3, n - 2], [n - 2, 3, 9, 7, 1], [n - 2, 3, 9]):
+            for controls in ([], [n - 1]):
+                rc, got = _c_plan(targets, controls, n, bits)
+                assert rc == _lib.QSIM_OK and got["path"] == 1 and got["trips"] >= 2, (bits, targets, controls, got)
+    assert _c_plan([0, 1, 2], [], 12, 64)[1]["trips"] == 1
+
+
+def test_plan_call_refusals():
+    ok = lambda *a, **kw: _c_plan(*a, **kw)[0]
+    assert ok([0, 1], [2], 6, 64) == _lib.QSIM_OK
+    assert ok([0, 0], [], 6, 64) == _lib.ERR_ARG                 # a repeated target
+    assert ok([0], [2, 2], 6, 64) == _lib.ERR_ARG                # a repeated control
+    assert ok([0, 1], [1], 6, 64) == _lib.ERR_ARG                # a control among the targets
+    assert ok([0, 6], [], 6, 64) == _lib.ERR_ARG and ok([-1], [], 6, 64) == _lib.ERR_ARG
+    assert ok([0], [6], 6, 64) == _lib.ERR_ARG and ok([0], [-1], 6, 64) == _lib.ERR_ARG
+    assert ok([0, 1, 2, 3, 4, 5], [], 8, 64) == _lib.ERR_ARG     # k > 5
+    assert ok([0, 1, 2], [], 2, 64) == _lib.ERR_ARG              # k > n
+    assert ok([0], [], 6, 64, k=-1) == _lib.ERR_ARG and ok([0], [1], 6, 64, c=-1) == _lib.ERR_ARG
+    assert ok([0], [], 6, 64, null_targets=True) == _lib.ERR_ARG and ok([0], [1], 6, 64, null_controls=True) == _lib.ERR_ARG
+    assert ok([], [], 6, 64, null_targets=True, null_controls=True) == _lib.QSIM_OK
+    assert ok([0], [], -1, 64) == _lib.ERR_ARG and ok([0], [], 41, 64) == _lib.ERR_ARG
+    assert ok([0], [], 40, 64) == _lib.QSIM_OK and ok([], [], 0, 32) == _lib.QSIM_OK
+    assert ok([0], [], 6, 16) == _lib.ERR_ARG                    # precision_bits
+    lib = _lib.load()
+    padded, mask, units, trips = c_int(), c_uint64(), c_uint64(), c_long()
+    assert lib.qsim_apply_matrix_plan(_ints([0]), 1, None, 0, 6, 64, None, byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG
+    # the call itself refuses a NULL state before it looks at anything else
+    u = np.eye(2, dtype=np.complex128).view(np.float64)
+    assert lib.qsim_apply_matrix(None, u.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, None, 0) == _lib.ERR_ARG
+
+
+# ---- the operand ------------------------------------------------------------------------------------------------------------------------
+def _operand(U, targets, controls, n, bits):
+    m = np.zeros(64 * 64)
+    amp, part, rows = (c_int * 64)(), (c_int * 64)(), c_int(-1)
+    flat = np.ascontiguousarray(np.asarray(U, dtype=np.complex128).reshape(-1)).view(np.float64)
+    rc = _lib.load().qsim_apply_matrix_operand(flat.ctypes.data_as(POINTER(c_double)), _ints(targets), len(targets), _ints(controls), len(controls), n,
+                                               bits, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows))
+    assert rc == _lib.QSIM_OK
+    r = rows.value
+    return m[:r * r].reshape(r, r).copy(), list(amp[:r]), list(part[:r])
+
+
+OPERAND_CASES = [  # (targets, controls): K = 3, 4, 5 with and without qubit 0 in the kernel's subset, padded and not, any order
+    ([0, 1, 2], []), ([3, 1, 2], []), ([5, 2, 8], [0]), ([4], []), ([4], [0, 1]), ([], [3]), ([6, 0], [1]),
+    ([0, 1, 2, 3], []), ([4, 3, 2, 1], []), ([7, 0, 3, 5], [2]), ([1, 9, 4, 6], [0]),
+    ([0, 1, 2, 3, 4], []), ([5, 4, 3, 2, 1], []), ([9, 0, 7, 2, 4], [10]), ([3, 8, 1, 6, 10], [0, 11]),
+]
+
+
+@pytest.mark.parametrize("bits", [64, 32])
+def test_operand_through_the_instruction_maps(bits):
+    """For each case: M is [[Re, -Im], [Im, Re]] of U (x) 1 in one row order; pushed through the A / B / D maps with random columns
+    every lane receives the rows it supplied, they are whole units, and the result equals (U (x) 1) @ columns."""
+    rng = np.random.default_rng(44)
+    n = 12
+    for targets, controls in OPERAND_CASES:
+        k = len(targets)
+        U = rng.standard_normal((1 << k, 1 << k)) + 1j * rng.standard_normal((1 << k, 1 << k))
+        rc, plan = _c_plan(targets, controls, n, bits)
+        assert rc == _lib.QSIM_OK and plan["path"] == 1
+        M, amp, part = _operand(U, targets, controls, n, bits)
+        kk = plan["padded_k"]
+        assert M.shape == (2 << kk, 2 << kk)
+        subset = [q for q in range(n) if plan["mask"] >> q & 1]
+        # U (x) 1 over the sorted subset, from the checker: column b of it is the image of basis state b
+        dense = np.stack([matrix_ref.apply_matrix(np.eye(1 << kk)[b], U, [subset.index(q) for q in targets]) for b in range(1 << kk)], axis=1)
+        cols = rng.standard_normal((1 << kk, 16)) + 1j * rng.standard_normal((1 << kk, 16))
+        got = matrix_ref.emulate_operand(M, amp, part, cols, bits == 32, 0 in subset)
+        assert np.max(np.abs(got - dense @ cols)) < 1e-12, (targets, controls)
+        # the two lowest unit-row bits of the subset are the lane group: rows r with equal r mod 4 share them
+        low = 1 if bits == 32 and 0 in subset else 0
+        for r in range(2 << kk):
+            assert (amp[r] >> low) & 3 == r & 3
+
+
+def test_operand_of_the_plain_path_and_refusals():
+    lib = _lib.load()
+    m, amp, part, rows = np.zeros(64 * 64), (c_int * 64)(), (c_int * 64)(), c_int(-1)
+    u = np.eye(2, dtype=np.complex128).reshape(-1).view(np.float64).copy()
+    args =lambda uu, n: (uu.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, None, 0, n, 64, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows))
+    assert lib.qsim_apply_matrix_operand(*args(u, 3)) == _lib.QSIM_OK and rows.value == 0     # the plain kernel takes U as it is
+    assert lib.qsim_apply_matrix_operand(*args(u, 8)) == _lib.QSIM_OK and rows.value == 16
+    for bad in (np.nan, np.inf, -np.inf):
+        v = u.copy()
+        v[3] = bad
+        assert lib.qsim_apply_matrix_operand(*args(v, 8)) == _lib.ERR_ARG
+    assert lib.qsim_apply_matrix_operand(None, _ints([0]), 1, None, 0, 8, 64, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows)) == _lib.ERR_ARG
+    assert lib.qsim_apply_matrix_operand(u.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, _ints([0]), 1, 8, 64, m.ctypes.data_as(POINTER(c_double)), amp,
+                                         part, byref(rows)) == _lib.ERR_ARG
