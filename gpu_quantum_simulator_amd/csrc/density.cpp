@@ -12,12 +12,8 @@ using namespace qsim;
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------------
 bool qsim::density_plan(const int *qubits, int k, int n, bool f32, DensityPlan *out) {
-    if (n < 0 || n > 40 || k < 0 || k > kDensityMaxQubits || k > n || (k > 0 && !qubits)) return false;
-    uint64_t mask = 0;
-    for (int j = 0; j < k; j++) {
-        if (qubits[j] < 0 || qubits[j] >= n || (mask >> qubits[j] & 1ULL)) return false;
-        mask |= 1ULL << qubits[j];
-    }
+    uint64_t mask;
+    if (n < 0 || n > 40 || k > kDensityMaxQubits || !qubit_list_mask(qubits, k, n, 0, &mask)) return false;
     DensityPlan p{};
     p.n = n, p.k = k, p.f32 = f32;
     p.units = (1ULL << n) >> (f32 ? 1 : 0);
@@ -26,15 +22,13 @@ bool qsim::density_plan(const int *qubits, int k, int n, bool f32, DensityPlan *
     // the matrix path: a tile of 16 rows of R and four environments per instruction
     p.path = n >= kDensityMinKernelQubits && n - kk >= 2 ? 1 : 0;
     p.padded_k = p.path ? kk : k;
-    for (int q = 0; p.path && __builtin_popcountll(mask) < kk; q++) mask |= 1ULL << q; // pad with the lowest bits that are free
-    p.mask = mask;
-    p.q0_in = mask & 1ULL;
+    p.mask = p.path ? pad_subset(mask, 0, kk, n) : mask;
+    p.q0_in = p.mask & 1ULL;
     p.trips_at_cap = 1;
     if (p.path) {
-        p.env_units = ctrl_geom(mask, 0, f32, n).units;
+        p.env_units = ctrl_geom(p.mask, 0, f32, n).units;
         const uint64_t per_trip = (uint64_t)kDensityWaves * density_steps_per_trip(density_loads(density_row_units(f32, kk, p.q0_in)));
-        const uint64_t steps = (p.env_units + 3) >> 2, per_round = per_trip * kExpectGrid;
-        p.trips_at_cap = (long)((steps + per_round - 1) / per_round);
+        p.trips_at_cap = trips_at_cap((p.env_units + 3) >> 2, per_trip, kExpectGrid);
     }
     *out = p;
     return true;
@@ -46,16 +40,11 @@ extern "C" int qsim_reduced_density_plan(const int *qubits, int k, int num_q, in
                                          uint64_t *units_visited, long *trips_per_workgroup_at_grid_cap) {
     const char *who = "qsim_reduced_density_plan";
     if (!path || !padded_k || !kernel_mask || !units_visited || !trips_per_workgroup_at_grid_cap) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
-    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
     DensityPlan p;
     if (!density_plan(qubits, k, num_q, precision_bits == 32, &p))
         return fail(QSIM_ERR_ARG, "%s: 0 to %d distinct qubits inside the register, not more than it has", who, kDensityMaxQubits);
-    *path = p.path;
-    *padded_k = p.padded_k;
-    *kernel_mask = p.mask;
-    *units_visited = p.units;
-    *trips_per_workgroup_at_grid_cap = p.trips_at_cap;
+    subset_probe_outputs(p, path, padded_k, kernel_mask, units_visited, trips_per_workgroup_at_grid_cap);
     return QSIM_OK;
 }
 
@@ -93,15 +82,10 @@ static std::vector<cplx> rho_from_tiles(const DensityPlan &p, const double *g) {
 // conjugate and the diagonal is real.
 static void to_callers_order(const DensityPlan &p, const int *qubits, const std::vector<cplx> &rho, double *out) {
     const int kdim = 1 << p.padded_k, dim = 1 << p.k;
-    auto position = [&](int q) { return __builtin_popcountll(p.mask & ((1ULL << q) - 1ULL)); }; // of qubit q in the sorted subset
-    uint32_t own = 0;
-    std::vector<uint32_t> base(dim, 0);
-    for (int j = 0; j < p.k; j++) {
-        own |= 1u << position(qubits[j]);
-        for (int c = 0; c < dim; c++)
-            if (c >> j & 1) base[c] |= 1u << position(qubits[j]);
-    }
-    std::vector<uint32_t> pad;
+    const SubsetOrder order{p.mask, qubits, p.k};
+    const uint32_t own = order.own();
+    std::vector<uint32_t> base(dim), pad;
+    for (int c = 0; c < dim; c++) base[c] = order.to_subset(c);
     for (uint32_t v = 0; v < (uint32_t)kdim; v++)
         if (!(v & own)) pad.push_back(v);
     for (int a = 0; a < dim; a++)
@@ -132,7 +116,7 @@ extern "C" int qsim_reduced_density(qsim_state *s, const int *qubits, int k, dou
     }
     QSIM_TRY(await_buffer(s));
     HIP_TRY(hipSetDevice(s->device));
-    double *d_scratch = nullptr; // larger than kExpectPartialDoubles: per call, before anything is launched
+    double *d_scratch = nullptr; // up to 1025 rows of 9216 doubles, far above kSweepScratchDoubles: per call, before anything is launched
     HIP_TRY(hipMalloc((void **)&d_scratch, density_scratch_doubles(p) * sizeof(double)));
     const size_t count = p.path ? (size_t)density_row_doubles(p.padded_k) : 2 * entries;
     std::vector<double> res(count);

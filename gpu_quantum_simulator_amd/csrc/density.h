@@ -18,7 +18,7 @@
 #ifndef QSIM_DENSITY_H
 #define QSIM_DENSITY_H
 
-#include "pauli_sweep.h"
+#include "subset_sweep.h"
 
 namespace qsim {
 
@@ -35,14 +35,9 @@ constexpr int density_tiles(int kk) { return (2 << kk) / 16; }                  
 constexpr int density_upper_tiles(int kk) { return density_tiles(kk) * (density_tiles(kk) + 1) / 2; }
 constexpr int density_row_doubles(int kk) { return density_upper_tiles(kk) * 256; }         // one partial row = one result
 
-struct DensityPlan {
-    int path;            // 0: the plain one-workgroup kernel (registers too small for a tile), 1: the matrix path
-    int n, k, padded_k;  // padded_k: the qubits of the kernel's subset (path 0: k, nothing is padded)
-    bool f32, q0_in;     // q0_in: qubit 0 is in the kernel's subset
-    uint64_t mask;       // the kernel's subset
-    uint64_t units;      // 16-byte units the sweep reads: the state, once
-    uint64_t env_units;  // path 1: units per row unit
-    long trips_at_cap;   // trips of a workgroup's loop when the grid is kExpectGrid workgroups
+// path 0: registers too small for a tile; units: the state, read once; env_units: units per row unit; trips_at_cap: at kExpectGrid
+struct DensityPlan : SubsetPlan {
+    bool q0_in; // qubit 0 is in the kernel's subset
 };
 // The single place that decides.  false: k outside [0, 5] or above n, n outside [0, 40], a qubit outside [0, n) or repeated.
 bool density_plan(const int *qubits, int k, int n, bool f32, DensityPlan *out);

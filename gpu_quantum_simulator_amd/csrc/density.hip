@@ -1,6 +1,6 @@
 // density.hip — reduced density matrices of up to five qubits as ONE read-only sweep on the matrix cores (gfx950).  Its own object,
 // like the Pauli sweeps: nothing here is compiled into kernels.hip.  density.h has the decomposition (rho from G = R R^T, the
-// shapes, which row of R a lane row is) and density.cpp the host side; this file has the two kernels.
+// shapes, which row of R a lane row is), subset_sweep.h what matrix.hip uses too, and density.cpp the host side; this file has the two kernels.
 //
 // k_density (the matrix path).  A wave works on its own: lane l loads the unit of (row unit l & 15, environment unit e0 + (l >> 4)),
 // and a component of that unit IS the lane's element of an operand of v_mfma_f64_16x16x4_f64 — A[l & 15][l >> 4] and B[l >> 4][l & 15]
@@ -18,20 +18,6 @@
 
 namespace qsim {
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// bit j of v -> the j-th lowest set bit of mask
-__device__ __forceinline__ uint64_t deposit(uint32_t v, uint64_t mask) {
-    uint64_t r = 0;
-    for (uint64_t m = mask; m != 0; m &= m - 1ULL, v >>= 1) // uniform: the mask comes off a scalar register
-        if (v & 1u) r |= m & (0ULL - m);
-    return r;
-}
-
-// component k of a unit, widened; k is a constant once the loops are unrolled
-__device__ __forceinline__ double pick(const double2 &v, int k) { return k == 0 ? v.x : v.y; }
-__device__ __forceinline__ double pick(const float4 &v, int k) { return (double)(k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w); }
 
 template <typename R, int KK, bool Q0IN>
 __global__ __launch_bounds__(kTPB) void k_density(const R *__restrict__ amp, CtrlGeom g, uint64_t row_mask, double *__restrict__ partial) {
@@ -186,12 +172,7 @@ hipError_t launch_shape(hipStream_t stream, const void *amps, const DensityPlan 
 
 template <typename R, bool Q0IN>
 hipError_t launch_prec(hipStream_t stream, const void *amps, const DensityPlan &p, double *d_scratch) {
-    switch (p.padded_k) {
-    case 3: return launch_shape<R, 3, Q0IN>(stream, amps, p, d_scratch);
-    case 4: return launch_shape<R, 4, Q0IN>(stream, amps, p, d_scratch);
-    case 5: return launch_shape<R, 5, Q0IN>(stream, amps, p, d_scratch);
-    default: return hipErrorInvalidValue;
-    }
+    return for_subset_size(p.padded_k, [&](auto kk) { return launch_shape<R, decltype(kk)::value, Q0IN>(stream, amps, p, d_scratch); });
 }
 
 } // namespace

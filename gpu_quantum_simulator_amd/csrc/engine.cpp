@@ -31,6 +31,17 @@ int qsim::fail(int code, const char *fmt, ...) {
     return code;
 }
 
+int qsim::launched(const char *what, hipError_t e) {
+    if (e == hipSuccess) return QSIM_OK;
+    return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+
+int qsim::check_register_args(const char *who, int num_q, int precision_bits) {
+    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
+    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    return QSIM_OK;
+}
+
 extern "C" const char *qsim_last_error(void) { return g_err.c_str(); }
 
 extern "C" int qsim_device_count(void) {

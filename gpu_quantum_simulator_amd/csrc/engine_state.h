@@ -7,7 +7,8 @@
 //   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values, rotations
 //                                                                           (controlled ones too) and adjoint gradients (the host
 //                                                                           side of expect.hip, evolve.hip, crot.hip and
-//                                                                           adjoint.hip; pauli_sweep.h)
+//                                                                           adjoint.hip; pauli_sweep.h), and the one owner of the
+//                                                                           state's sweep scratch
 //   state_algebra.cpp  calls on several states: copy, inner product, linear combination (the host side of combine.hip)
 //   lanczos.cpp        the Lanczos ground-state solver on top of pauli.cpp's H application and the two above
 //   density.cpp        reduced density matrices of qubit subsets: the plan, the call, from tiles to rho (the host side of density.hip; density.h)
@@ -113,7 +114,7 @@ struct qsim_state {
     qsim::TileOp *d_ops = nullptr, *h_ops = nullptr;
     size_t ops_cap = 0, ops_used = 0;
     double *d_scalar = nullptr;
-    double *d_expect = nullptr; // qsim_expect_paulis: partial sums of a sweep, then the results of a batch of sweeps; allocated on first use
+    double *d_expect = nullptr; // the sweep scratch: partial sums of a sweep, then the results of a batch of sweeps (alloc_sweep_scratch and the accessors below)
     void *d_adjoint = nullptr;  // qsim_pauli_gradient: lambda's 2^n amplitudes for a state without a spare buffer; allocated on first use, the state's own
     // stats
     qsim_stats stats{};
@@ -164,6 +165,10 @@ int fail(int code, const char *fmt, ...);
         const int rc_ = (expr);                                                                             \
         if (rc_) return rc_;                                                                                \
     } while (0)
+// What a kernel launcher returned, as the call's result: "<what> launch failed: <HIP's text>", out of memory as QSIM_ERR_ALLOC
+int launched(const char *what, hipError_t e);
+// The register a host-only plan probe is asked about: 0 to 40 qubits, precision_bits 64 or 32
+int check_register_args(const char *who, int num_q, int precision_bits);
 // QSIM_OK when both are there and the circuit has the state's number of qubits
 int check_circuit(const qsim_state *s, const qsim_circuit *c);
 // Joins the allocation of an asynchronously created state; QSIM_ERR_ALLOC ("Malloc error", quantum_simulator.c:170) if it failed.
@@ -210,11 +215,13 @@ void apply_sched_hint(uint64_t key, SchedConfig &cfg); // the schedule choice re
 // ---- profile.cpp -----------------------------------------------------------------------------------------------------------
 hipEvent_t take_event(qsim_state *s);
 
-// ---- state_algebra.cpp (also used by lanczos.cpp) ----------------------------------------------------------------------------
-// s->d_expect, allocated on first use: the partial sums of a reducing sweep, then result rows (pauli.cpp allocates the same).
+// ---- pauli.cpp: the state's sweep scratch, s->d_expect (pauli_sweep.h has its layout) -------------------------------------------
+// Allocates it on first use, whoever calls first; qsim_destroy frees it.  The accessors want it allocated.
 int alloc_sweep_scratch(qsim_state *s);
-double *sweep_result_row(qsim_state *s); // where the calls of these two files have a sweep leave its sums: the first result row
-// out[0..count) = the first `count` sums of that row; waits for the state's stream
+double *sweep_partials(qsim_state *s);      // kExpectPartialDoubles: what a reducing sweep takes as d_partial
+double *sweep_result_row(qsim_state *s);    // the first of kResultRowBatch rows of kResultRowSlots sums: where a call of one sweep has it leave them
+double *sweep_coef_staging(qsim_state *s);  // kMatrixCoefDoubles: the operand of qsim_apply_matrix (the definition says where it lies)
+// out[0..count) = the first `count` sums of the first result row; waits for the state's stream
 int fetch_sweep_results(qsim_state *s, int count, double *out);
 
 } // namespace qsim

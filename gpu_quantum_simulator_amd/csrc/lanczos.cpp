@@ -150,11 +150,6 @@ extern "C" int qsim_lanczos_plan(const uint64_t *ham_x, long num_ham, int max_st
 // ---- the solver ----------------------------------------------------------------------------------------------------------------------
 namespace {
 
-static int launched(const char *what, hipError_t e) {
-    if (e == hipSuccess) return QSIM_OK;
-    return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
 struct WorkBuffers { // three buffers of the state's size: the idle spare buffer and d_adjoint where they exist, the rest allocated here
     void *buf[3] = {nullptr, nullptr, nullptr};
     void *mine[3] = {nullptr, nullptr, nullptr};
@@ -198,7 +193,7 @@ struct Run {
     }
     int combine(void *dst, double d, const void *p, double a, const void *q, double b) {
         const double dd[2] = {d, 0.0}, aa[2] = {a, 0.0}, bb[2] = {b, 0.0};
-        return launched("combine", launch_combine(cfg, dst, dd, p, aa, q, bb, s->f32, s->n, s->d_expect, sweep_result_row(s)));
+        return launched("combine", launch_combine(cfg, dst, dd, p, aa, q, bb, s->f32, s->n, sweep_partials(s), sweep_result_row(s)));
     }
     int result(double *out) { return fetch_sweep_results(s, 1, out); }
 };
@@ -230,7 +225,7 @@ extern "C" int qsim_lanczos_ground(qsim_state *s, const uint64_t *ham_x, const u
     {
         ExpectSweep sw{};
         sw.count = 1;
-        QSIM_TRY(launched("norm", launch_expect(run.cfg, s->amps, s->amps, s->f32, s->n, sw, s->d_expect, sweep_result_row(s))));
+        QSIM_TRY(launched("norm", launch_expect(run.cfg, s->amps, s->amps, s->f32, s->n, sw, sweep_partials(s), sweep_result_row(s))));
         QSIM_TRY(run.result(&nu0));
         if (!(nu0 > 0.0) || !std::isfinite(nu0)) return fail(QSIM_ERR_ARG, "%s: the state has norm zero (or is not finite)", who);
         nu0 = std::sqrt(nu0);
@@ -247,7 +242,7 @@ extern "C" int qsim_lanczos_ground(qsim_state *s, const uint64_t *ham_x, const u
         sw.full = true; // x == 0 over two buffers
         sw.count = 1;
         double a_raw;
-        QSIM_TRY(launched("expectation", launch_expect(run.cfg, cur, w, s->f32, s->n, sw, s->d_expect, sweep_result_row(s))));
+        QSIM_TRY(launched("expectation", launch_expect(run.cfg, cur, w, s->f32, s->n, sw, sweep_partials(s), sweep_result_row(s))));
         QSIM_TRY(run.result(&a_raw));
         const double alpha = a_raw / nu[(size_t)j];
         double w2;

@@ -18,28 +18,18 @@ using cplx = std::complex<double>;
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------------
 bool qsim::matrix_plan(const int *targets, int k, const int *controls, int num_controls, int n, bool f32, MatrixPlan *out) {
-    if (n < 0 || n > 40 || k < 0 || k > kMatrixMaxQubits || k > n || num_controls < 0 || num_controls > n) return false;
-    if ((k > 0 && !targets) || (num_controls > 0 && !controls)) return false;
+    uint64_t mask, cmask;
+    if (n < 0 || n > 40 || k > kMatrixMaxQubits) return false;
+    if (!qubit_list_mask(targets, k, n, 0, &mask) || !qubit_list_mask(controls, num_controls, n, mask, &cmask)) return false;
     MatrixPlan p{};
-    uint64_t mask = 0, cmask = 0;
-    for (int j = 0; j < k; j++) {
-        if (targets[j] < 0 || targets[j] >= n || (mask >> targets[j] & 1ULL)) return false;
-        mask |= 1ULL << targets[j];
-        p.targets[j] = targets[j];
-    }
-    for (int j = 0; j < num_controls; j++) {
-        if (controls[j] < 0 || controls[j] >= n || ((mask | cmask) >> controls[j] & 1ULL)) return false;
-        cmask |= 1ULL << controls[j];
-    }
+    std::copy(targets, targets + k, p.targets);
     p.n = n, p.k = k, p.num_controls = num_controls, p.f32 = f32, p.controls = cmask;
     const bool q0_ctrl = f32 && (cmask & 1ULL);
     p.units = ((1ULL << n) >> num_controls) >> (f32 && !q0_ctrl ? 1 : 0);
     if (p.units == 0) p.units = 1; // one active fp32 amplitude
     // the matrix path: a subset of 3 to 5 qubits, padded with the lowest bits that are free, and 16 environment units per instruction
     const int kk = k < kMatrixMinKernelQubits ? kMatrixMinKernelQubits : k;
-    uint64_t padded = mask;
-    for (int q = 0; q < n && __builtin_popcountll(padded) < kk; q++)
-        if (!((padded | cmask) >> q & 1ULL)) padded |= 1ULL << q;
+    const uint64_t padded = pad_subset(mask, cmask, kk, n);
     p.path = 0;
     if (__builtin_popcountll(padded) == kk) {
         const uint64_t env_units = matrix_geom(padded, cmask, f32, n).units;
@@ -51,8 +41,7 @@ bool qsim::matrix_plan(const int *targets, int k, const int *controls, int num_c
     p.trips_at_cap = 1;
     if (p.path) {
         const uint64_t per_trip = (uint64_t)kMatrixWaves * matrix_steps_per_trip(matrix_lane_units(f32, kk, p.mode));
-        const uint64_t steps = p.env_units >> 4, per_round = per_trip * matrix_grid_cap(kk);
-        p.trips_at_cap = (long)((steps + per_round - 1) / per_round);
+        p.trips_at_cap = trips_at_cap(p.env_units >> 4, per_trip, matrix_grid_cap(kk));
     }
     *out = p;
     return true;
@@ -62,19 +51,13 @@ bool qsim::matrix_plan(const int *targets, int k, const int *controls, int num_c
 // U (x) 1 over the plan's sorted subset: 2^padded_k square; bit j of a row or column index of U is qubit targets[j]
 static std::vector<cplx> padded_matrix(const MatrixPlan &p, const double *U) {
     const int kdim = 1 << p.padded_k, dim = 1 << p.k;
-    auto position = [&](int q) { return __builtin_popcountll(p.mask & ((1ULL << q) - 1ULL)); }; // of qubit q in the sorted subset
-    uint32_t own = 0;
-    for (int j = 0; j < p.k; j++) own |= 1u << position(p.targets[j]);
-    auto callers = [&](uint32_t a) { // the caller's index behind the subset index a
-        uint32_t r = 0;
-        for (int j = 0; j < p.k; j++) r |= ((a >> position(p.targets[j])) & 1u) << j;
-        return r;
-    };
+    const SubsetOrder order{p.mask, p.targets, p.k};
+    const uint32_t own = order.own();
     std::vector<cplx> out((size_t)kdim * kdim, cplx(0.0, 0.0));
     for (uint32_t a = 0; a < (uint32_t)kdim; a++)
         for (uint32_t b = 0; b < (uint32_t)kdim; b++)
             if (((a ^ b) & ~own) == 0) { // the identity on the padding
-                const size_t at = (size_t)callers(a) * dim + callers(b);
+                const size_t at = (size_t)order.to_callers(a) * dim + order.to_callers(b);
                 out[(size_t)a * kdim + b] = cplx(U[2 * at], U[2 * at + 1]);
             }
     return out;
@@ -104,12 +87,6 @@ static int to_plan(const char *who, const int *targets, int k, const int *contro
     return QSIM_OK;
 }
 
-static int check_host_args(const char *who, int num_q, int precision_bits) {
-    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
-    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
-    return QSIM_OK;
-}
-
 static bool all_finite(const double *U, int k) {
     for (size_t i = 0; i < ((size_t)2 << (2 * k)); i++)
         if (!std::isfinite(U[i])) return false;
@@ -122,14 +99,10 @@ extern "C" int qsim_apply_matrix_plan(const int *targets, int k, const int *cont
                                       int *padded_k, uint64_t *kernel_mask, uint64_t *units, long *trips_per_workgroup) {
     const char *who = "qsim_apply_matrix_plan";
     if (!path || !padded_k || !kernel_mask || !units || !trips_per_workgroup) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    QSIM_TRY(check_host_args(who, num_q, precision_bits));
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
     MatrixPlan p;
     QSIM_TRY(to_plan(who, targets, k, controls, num_controls, num_q, precision_bits == 32, &p));
-    *path = p.path;
-    *padded_k = p.padded_k;
-    *kernel_mask = p.mask;
-    *units = p.units;
-    *trips_per_workgroup = p.trips_at_cap;
+    subset_probe_outputs(p, path, padded_k, kernel_mask, units, trips_per_workgroup);
     return QSIM_OK;
 }
 
@@ -137,7 +110,7 @@ extern "C" int qsim_apply_matrix_operand(const double *U, const int *targets, in
                                          int precision_bits, double *M, int *row_amp, int *row_part, int *rows) {
     const char *who = "qsim_apply_matrix_operand";
     if (!U || !M || !row_amp || !row_part || !rows) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    QSIM_TRY(check_host_args(who, num_q, precision_bits));
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
     MatrixPlan p;
     QSIM_TRY(to_plan(who, targets, k, controls, num_controls, num_q, precision_bits == 32, &p));
     if (!all_finite(U, k)) return fail(QSIM_ERR_ARG, "%s: a non-finite matrix entry", who);
@@ -157,7 +130,6 @@ extern "C" int qsim_apply_matrix_operand(const double *U, const int *targets, in
 // kSlots calls of one device are still queued; the copy itself is ordered on the state's stream, in front of the sweep.
 namespace {
 constexpr int kSlots = 16;
-constexpr size_t kSlotDoubles = (size_t)matrix_rows(kMatrixMaxQubits) * matrix_rows(kMatrixMaxQubits); // 4096: M for five qubits; U has 2048
 struct Ring {
     double *host = nullptr;
     hipEvent_t done[kSlots] = {};
@@ -169,19 +141,19 @@ std::map<int, Ring> g_rings;
 } // namespace
 
 static int stage_coefficients(qsim_state *s, const std::vector<double> &coef) {
-    QSIM_TRY(alloc_sweep_scratch(s)); // kExpectPartialDoubles doubles and more: stream-ordered scratch of the state's own
+    QSIM_TRY(alloc_sweep_scratch(s)); // stream-ordered scratch of the state's own
     std::lock_guard<std::mutex> lock(g_ring_mutex);
     Ring &ring = g_rings[s->device];
     if (!ring.host) {
-        HIP_TRY(hipHostMalloc((void **)&ring.host, kSlots * kSlotDoubles * sizeof(double), hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&ring.host, kSlots * kMatrixCoefDoubles * sizeof(double), hipHostMallocDefault));
         for (int i = 0; i < kSlots; i++) HIP_TRY(hipEventCreateWithFlags(&ring.done[i], hipEventDisableTiming));
     }
     const int slot = ring.next;
     ring.next = (slot + 1) % kSlots;
     if (ring.used[slot]) HIP_TRY(hipEventSynchronize(ring.done[slot]));
-    double *h = ring.host + (size_t)slot * kSlotDoubles;
+    double *h = ring.host + (size_t)slot * kMatrixCoefDoubles;
     std::memcpy(h, coef.data(), coef.size() * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(s->d_expect, h, coef.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(sweep_coef_staging(s), h, coef.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipEventRecord(ring.done[slot], s->stream));
     ring.used[slot] = true;
     return QSIM_OK;
@@ -214,8 +186,7 @@ extern "C" int qsim_apply_matrix(qsim_state *s, const double *U, const int *targ
     }
     QSIM_TRY(stage_coefficients(s, coef));
     const LaunchCfg cfg{s->stream, s->grid_cap};
-    const hipError_t e = launch_matrix(cfg, s->amps, p, s->d_expect);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
+    QSIM_TRY(launched("qsim_apply_matrix:", launch_matrix(cfg, s->amps, p, sweep_coef_staging(s))));
     g_matrix_sweeps++;
     return QSIM_OK;
 }

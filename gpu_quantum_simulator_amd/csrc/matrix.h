@@ -23,7 +23,7 @@
 #ifndef QSIM_MATRIX_H
 #define QSIM_MATRIX_H
 
-#include "pauli_sweep.h"
+#include "subset_sweep.h"
 
 namespace qsim {
 
@@ -46,18 +46,15 @@ constexpr int matrix_grid_cap(int kk) { return kk >= 5 ? 512 : 1024; }
 // The plain path: one workgroup, every thread at most this many amplitudes of the control subspace
 constexpr int kMatrixSmallPerThread = 4;
 
-struct MatrixPlan {
-    int path;            // 0: the plain one-workgroup kernel (fewer than 16 environment units), 1: the matrix path
-    int n, k, padded_k;  // padded_k: the qubits of the kernel's subset (path 0: k, nothing is padded)
+// path 0: fewer than 16 environment units, mask is the targets; units: read and written, 2^-c of the state (fp32 with a control on
+// qubit 0: 2^(1-c)); env_units: the columns of the GEMM (fp32 kMatrixEnvs: two environments each); trips_at_cap: at matrix_grid_cap
+struct MatrixPlan : SubsetPlan {
     int num_controls, mode;
-    bool f32;
-    uint64_t mask;       // the kernel's subset (path 0: the targets)
     uint64_t controls;
-    uint64_t units;      // 16-byte units the sweep reads and writes: 2^-c of the state (fp32 with a control on qubit 0: 2^(1-c))
-    uint64_t env_units;  // path 1: environment units = columns of the GEMM (fp32 kMatrixEnvs: two environments each)
-    long trips_at_cap;   // trips of a workgroup's loop when the grid is matrix_grid_cap workgroups
     int targets[kMatrixMaxQubits];
 };
+// M for five qubits, the largest operand a call hands to the device (U has half as many doubles)
+constexpr size_t kMatrixCoefDoubles = (size_t)matrix_rows(kMatrixMaxQubits) * matrix_rows(kMatrixMaxQubits);
 // The single place that decides.  false: k outside [0, 5] or above n, a negative control count, n outside [0, 40], a qubit outside
 // [0, n) or repeated, a control among the targets, a NULL list with a positive count.
 bool matrix_plan(const int *targets, int k, const int *controls, int num_controls, int n, bool f32, MatrixPlan *out);

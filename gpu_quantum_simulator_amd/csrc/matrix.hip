@@ -1,7 +1,7 @@
 // matrix.hip — a dense matrix on up to five target qubits, under any number of controls, as ONE in-place sweep of the control
 // subspace on the matrix cores (gfx950).  Its own object, like density.hip, whose walk it shares: nothing here is compiled into
-// kernels.hip.  matrix.h has the decomposition (R' = M R in 16 x 16 tiles, which rows a lane owns, the shapes) and matrix.cpp the
-// host side; this file has the two kernels.
+// kernels.hip.  matrix.h has the decomposition (R' = M R in 16 x 16 tiles, which rows a lane owns, the shapes), subset_sweep.h what
+// density.hip uses too, and matrix.cpp the host side; this file has the two kernels.
 //
 // k_matrix (the matrix path).  A wave works on its own.  Lane l = (e = l & 15, g = l >> 4) loads the units of environment unit
 // 16 step + e whose unit-row index is g (mod 4), all of a trip first; a component of such a unit IS the lane's element
@@ -21,20 +21,6 @@
 
 namespace qsim {
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// bit j of v -> the j-th lowest set bit of mask
-__device__ __forceinline__ uint64_t deposit(uint32_t v, uint64_t mask) {
-    uint64_t r = 0;
-    for (uint64_t m = mask; m != 0; m &= m - 1ULL, v >>= 1) // uniform: the mask comes off a scalar register
-        if (v & 1u) r |= m & (0ULL - m);
-    return r;
-}
-
-// component c of a unit, widened; c is a constant once the loops are unrolled
-__device__ __forceinline__ double pick(const double2 &v, int c) { return c == 0 ? v.x : v.y; }
-__device__ __forceinline__ double pick(const float4 &v, int c) { return (double)(c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w); }
 
 template <typename R, int KK, int MODE>
 __global__ __launch_bounds__(kTPB) void k_matrix(R *amp, CtrlGeom g, uint64_t row_mask, const double *__restrict__ coef) {
@@ -181,12 +167,7 @@ hipError_t launch_shape(const LaunchCfg &cfg, void *amps, const MatrixPlan &p, c
 
 template <typename R, int MODE>
 hipError_t launch_prec(const LaunchCfg &cfg, void *amps, const MatrixPlan &p, const double *d_coef) {
-    switch (p.padded_k) {
-    case 3: return launch_shape<R, 3, MODE>(cfg, amps, p, d_coef);
-    case 4: return launch_shape<R, 4, MODE>(cfg, amps, p, d_coef);
-    case 5: return launch_shape<R, 5, MODE>(cfg, amps, p, d_coef);
-    default: return hipErrorInvalidValue;
-    }
+    return for_subset_size(p.padded_k, [&](auto kk) { return launch_shape<R, decltype(kk)::value, MODE>(cfg, amps, p, d_coef); });
 }
 
 } // namespace

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "engine_state.h"
+#include "matrix.h" // kMatrixCoefDoubles: sweep_coef_staging
 #include "pauli_sweep.h"
 
 using namespace qsim;
@@ -43,34 +44,38 @@ static int check_terms(const char *who, const qsim_state *s, const uint64_t *x_m
     if (!s) return fail(QSIM_ERR_ARG, "NULL state");
     return check_pauli_terms(fail, who, s->n, x_masks, z_masks, third, numbers, num_terms, number);
 }
-// What a launcher of pauli_sweep.h returned, as the call's result: `sweep` names it in the message
-static int launched(const char *sweep, hipError_t e) {
-    if (e == hipSuccess) return QSIM_OK;
-    return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s sweep launch failed: %s", sweep, hipGetErrorString(e));
-}
 
-// ---- result rows ------------------------------------------------------------------------------------------------------------------
-// What reducing sweeps leave their sums in: s->d_expect, allocated on first use, is the partial sums of the sweep that runs
-// (kExpectPartialDoubles) and behind them kRowBatch rows of kRowSlots results, one row per sweep, so that the results of up to
-// kRowBatch sweeps travel in one copy behind one synchronisation.
-static constexpr int kRowBatch = 128;
-static constexpr int kRowSlots = kMaxPauliTermsPerSweep;
-static int alloc_result_rows(qsim_state *s) {
-    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + (size_t)kRowBatch * kRowSlots) * sizeof(double)));
+// ---- the sweep scratch and its result rows ------------------------------------------------------------------------------------------
+// s->d_expect has ONE owner, here: every file that needs a part of it calls alloc_sweep_scratch and then an accessor
+// (engine_state.h), and pauli_sweep.h has the sizes.
+int qsim::alloc_sweep_scratch(qsim_state *s) {
+    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, kSweepScratchDoubles * sizeof(double)));
     return QSIM_OK;
 }
-// launch(r, d_row) queues the sweep of row r < rows on the state's stream; scatter(r, row) gets its kRowSlots sums on the host.
-// Batch after batch in order of r; what a row means is the caller's.
+double *qsim::sweep_partials(qsim_state *s) { return s->d_expect; }
+double *qsim::sweep_result_row(qsim_state *s) { return s->d_expect + kExpectPartialDoubles; }
+// The operand of qsim_apply_matrix ALIASES the partial sums, on purpose: everything that touches either is ordered on the state's
+// stream, and no reducing sweep is in flight while a matrix sweep reads its coefficients.
+static_assert(kMatrixCoefDoubles <= kExpectPartialDoubles, "the largest matrix operand fits in the partial-sum region");
+double *qsim::sweep_coef_staging(qsim_state *s) { return sweep_partials(s); }
+
+int qsim::fetch_sweep_results(qsim_state *s, int count, double *out) {
+    HIP_TRY(hipMemcpyAsync(out, sweep_result_row(s), (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return QSIM_OK;
+}
+// launch(r, d_row) queues the sweep of row r < rows on the state's stream; scatter(r, row) gets its kResultRowSlots sums on the
+// host.  Batch after batch in order of r; what a row means is the caller's.
 template <typename Launch, typename Scatter>
 static int sweep_result_rows(qsim_state *s, size_t rows, Launch launch, Scatter scatter) {
-    double *d_rows = s->d_expect + kExpectPartialDoubles;
-    std::vector<double> host((size_t)kRowBatch * kRowSlots);
-    for (size_t first = 0; first < rows; first += kRowBatch) {
-        const size_t last = std::min(rows, first + (size_t)kRowBatch);
-        for (size_t r = first; r < last; r++) QSIM_TRY(launch(r, d_rows + (r - first) * kRowSlots));
-        HIP_TRY(hipMemcpyAsync(host.data(), d_rows, (last - first) * kRowSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    double *d_rows = sweep_result_row(s);
+    std::vector<double> host(kSweepResultDoubles);
+    for (size_t first = 0; first < rows; first += kResultRowBatch) {
+        const size_t last = std::min(rows, first + (size_t)kResultRowBatch);
+        for (size_t r = first; r < last; r++) QSIM_TRY(launch(r, d_rows + (r - first) * kResultRowSlots));
+        HIP_TRY(hipMemcpyAsync(host.data(), d_rows, (last - first) * kResultRowSlots * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t r = first; r < last; r++) scatter(r, host.data() + (r - first) * kRowSlots);
+        for (size_t r = first; r < last; r++) scatter(r, host.data() + (r - first) * kResultRowSlots);
     }
     return QSIM_OK;
 }
@@ -124,7 +129,7 @@ int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank,
         if ((X[t] >> m) != x_rank) return fail(QSIM_ERR_ARG, "expectation: terms of one shard call must pair the same shards");
     if ((x_rank != 0) != (partner != nullptr)) return fail(QSIM_ERR_ARG, "expectation: a partner buffer goes with x on rank qubits, and only with it");
     QSIM_TRY(settle(s));
-    QSIM_TRY(alloc_result_rows(s));
+    QSIM_TRY(alloc_sweep_scratch(s));
     const PauliSweeps plan = pauli_sweeps(X, mmask, num);
     const LaunchCfg cfg{s->stream, s->grid_cap};
     return sweep_result_rows(
@@ -139,7 +144,7 @@ int qsim::expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank,
                 sw.z[k] = Z[t] & mmask;
                 if (__builtin_popcountll(X[t] & Z[t]) & 1) sw.im_mask |= 1u << k;
             }
-            return launched("expectation", launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, s->d_expect, d_row));
+            return launched("expectation sweep", launch_expect(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw, sweep_partials(s), d_row));
         },
         [&](size_t w, const double *row) {
             for (int k = 0; k < plan.sweeps[w].second; k++) {
@@ -223,7 +228,7 @@ int qsim::pauli_rot_run(qsim_state *s, void *partner, uint64_t rank, uint64_t x,
     const LaunchCfg cfg{s->stream, s->grid_cap};
     for (long first = 0; first < count; first += kPauliRotationsPerSweep) {
         const RotSweep sw = rot_sweep(x, Z + first, thetas + first, (int)std::min<long>(kPauliRotationsPerSweep, count - first), 1.0, rank, mmask, m);
-        QSIM_TRY(launched("rotation", launch_pauli_rot(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw)));
+        QSIM_TRY(launched("rotation sweep", launch_pauli_rot(cfg, s->amps, partner ? partner : s->amps, s->f32, m, sw)));
         g_sweeps_launched++;
     }
     return QSIM_OK;
@@ -274,7 +279,7 @@ static int controlled_rot_run(qsim_state *s, uint64_t c, uint64_t x, const uint6
     const LaunchCfg cfg{s->stream, s->grid_cap};
     for (long first = 0; first < count; first += kPauliRotationsPerSweep) {
         const RotSweep sw = rot_sweep(x, Z + first, thetas + first, (int)std::min<long>(kPauliRotationsPerSweep, count - first), 1.0, 0, index_mask(s->n), s->n);
-        QSIM_TRY(launched("controlled rotation", launch_pauli_crot(cfg, s->amps, s->f32, s->n, c, sw)));
+        QSIM_TRY(launched("controlled rotation sweep", launch_pauli_crot(cfg, s->amps, s->f32, s->n, c, sw)));
         g_sweeps_launched++;
     }
     return QSIM_OK;
@@ -321,8 +326,7 @@ extern "C" int qsim_controlled_rotation_plan(const uint64_t *c_masks, const uint
                                              int precision_bits, long *sweeps, long *queued_as_gates, uint64_t *units_visited) {
     const char *who = "qsim_controlled_rotation_plan";
     if (!sweeps || !queued_as_gates || !units_visited) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
-    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
     QSIM_TRY(check_pauli_terms(fail, who, num_q, x_masks, z_masks, x_masks, nullptr, num_terms));
     QSIM_TRY(check_controls(who, num_q, c_masks, x_masks, z_masks, num_terms));
     *sweeps = *queued_as_gates = 0;
@@ -372,8 +376,7 @@ extern "C" int qsim_controlled_gradient_plan(const uint64_t *rot_c, const uint64
                                              int precision_bits, long *adjoint_sweeps, long *sum_sweeps, uint64_t *units_visited) {
     const char *who = "qsim_controlled_gradient_plan";
     if (!adjoint_sweeps || !sum_sweeps || !units_visited) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
-    if (num_q < 0 || num_q > 40) return fail(QSIM_ERR_ARG, "%s: a register of %d qubits", who, num_q);
-    if (precision_bits != 64 && precision_bits != 32) return fail(QSIM_ERR_ARG, "%s: precision_bits is 64 or 32, not %d", who, precision_bits);
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
     // the plan knows no z: x stands in for it, so a control that meets x is refused here and one that meets z by the call itself
     QSIM_TRY(check_pauli_terms(fail, who, num_q, rot_x, rot_x, rot_x, nullptr, num_rot));
     QSIM_TRY(check_pauli_terms(fail, who, num_q, ham_x, ham_x, ham_x, nullptr, num_ham));
@@ -410,7 +413,7 @@ int qsim::pauli_sum_sweeps(qsim_state *s, const uint64_t *X, const uint64_t *Z, 
             sw.c[k] = C[t] * pauli_phase(ny) * ((ny & 1) ? -1.0 : 1.0); // (Q psi)_i = i^ny s(i ^ x) psi_(i^x), and s(i ^ x) = (-1)^ny s(i)
             if (ny & 1) sw.odd_mask |= 1u << k;
         }
-        QSIM_TRY(launched("Pauli sum", launch_pauli_sum(cfg, s->amps, dst, s->f32, s->n, sw)));
+        QSIM_TRY(launched("Pauli sum sweep", launch_pauli_sum(cfg, s->amps, dst, s->f32, s->n, sw)));
     }
     return QSIM_OK;
 }
@@ -438,7 +441,7 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
         HIP_TRY(hipMalloc(&lam, s->amp_bytes() << s->n));
         s->d_adjoint = lam;
     }
-    QSIM_TRY(alloc_result_rows(s));
+    QSIM_TRY(alloc_sweep_scratch(s));
 
     QSIM_TRY(apply_rotations(s, C, rot_x, rot_z, thetas, num_rot));
     QSIM_TRY(settle(s));
@@ -454,13 +457,13 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
                 ExpectSweep sw{};
                 sw.full = true; // x == 0 over two buffers: every index, its partner the same index of lambda
                 sw.count = 1;
-                return launched("expectation", launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row));
+                return launched("expectation sweep", launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, sweep_partials(s), d_row));
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
             const uint64_t c = C ? C[piece.first] : 0;
             const RotSweep sw = rot_sweep(rot_x[piece.first], rot_z + piece.first, thetas + piece.first, piece.second, -1.0 /* U^+ */, 0, index_mask(s->n), s->n);
-            if (c) QSIM_TRY(launched("controlled adjoint", launch_pauli_cadjoint(cfg, s->amps, lam, s->f32, s->n, c, sw, s->d_expect, d_row)));
-            else QSIM_TRY(launched("adjoint", launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, s->d_expect, d_row)));
+            if (c) QSIM_TRY(launched("controlled adjoint sweep", launch_pauli_cadjoint(cfg, s->amps, lam, s->f32, s->n, c, sw, sweep_partials(s), d_row)));
+            else QSIM_TRY(launched("adjoint sweep", launch_pauli_adjoint(cfg, s->amps, lam, s->f32, s->n, sw, sweep_partials(s), d_row)));
             g_adjoint_sweeps++;
             return QSIM_OK;
         },

@@ -57,6 +57,12 @@ struct RotSweep : PauliSweep {
 
 constexpr int kExpectGrid = 1024;     // workgroups of an expectation sweep at most = rows of partial sums (4 per CU)
 constexpr size_t kExpectPartialDoubles = (size_t)kExpectGrid * kMaxPauliTermsPerSweep;
+// The layout of a state's sweep scratch (qsim_state::d_expect; engine_state.h declares its allocator and accessors): the partial
+// sums of the reducing sweep that runs, and behind them kResultRowBatch rows of kResultRowSlots results, one row per sweep, so that
+// the results of up to kResultRowBatch sweeps travel in one copy behind one synchronisation.
+constexpr int kResultRowBatch = 128, kResultRowSlots = kMaxPauliTermsPerSweep;
+constexpr size_t kSweepResultDoubles = (size_t)kResultRowBatch * kResultRowSlots;
+constexpr size_t kSweepScratchDoubles = kExpectPartialDoubles + kSweepResultDoubles;
 int expect_slots(int count); // term slots of the instantiation a sweep of `count` terms runs in (1, 8, 16, 32)
 // d_out[k] = sum_j s_k(j) |a_j|^2 (x == 0 and not full) or sum_j s_k(j) Re/Im(conj(b_(j^x)) a_j), for k < expect_slots(count);
 // d_partial: kExpectPartialDoubles doubles of scratch.  a and b may be the same buffer.

@@ -11,26 +11,6 @@
 
 using namespace qsim;
 
-// s->d_expect as pauli.cpp allocates it on first use (alloc_result_rows: the partial sums of a sweep, then 128 rows of results):
-// whoever comes first allocates it for both, so the size is the same here.
-static constexpr size_t kResultRowDoubles = (size_t)128 * kMaxPauliTermsPerSweep;
-int qsim::alloc_sweep_scratch(qsim_state *s) {
-    if (!s->d_expect) HIP_TRY(hipMalloc((void **)&s->d_expect, (kExpectPartialDoubles + kResultRowDoubles) * sizeof(double)));
-    return QSIM_OK;
-}
-double *qsim::sweep_result_row(qsim_state *s) { return s->d_expect + kExpectPartialDoubles; }
-
-int qsim::fetch_sweep_results(qsim_state *s, int count, double *out) {
-    HIP_TRY(hipMemcpyAsync(out, sweep_result_row(s), (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return QSIM_OK;
-}
-
-static int launched(const char *what, hipError_t e) {
-    if (e == hipSuccess) return QSIM_OK;
-    return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-}
-
 // `from`'s stream has reached this point before `to`'s stream goes on
 static int stream_waits(qsim_state *to, qsim_state *from) {
     if (to == from || to->stream == from->stream) return QSIM_OK;
@@ -85,7 +65,7 @@ extern "C" int qsim_inner(qsim_state *a, qsim_state *b, double *re, double *im) 
     sw.count = 2;
     sw.im_mask = 0b10;
     const LaunchCfg cfg{a->stream, a->grid_cap};
-    QSIM_TRY(launched("inner product", launch_expect(cfg, b->amps, a->amps, a->f32, a->n, sw, a->d_expect, sweep_result_row(a))));
+    QSIM_TRY(launched("inner product", launch_expect(cfg, b->amps, a->amps, a->f32, a->n, sw, sweep_partials(a), sweep_result_row(a))));
     if (a != b) QSIM_TRY(stream_waits(b, a));
     double out[2];
     QSIM_TRY(fetch_sweep_results(a, 2, out));
@@ -111,7 +91,7 @@ extern "C" int qsim_combine(qsim_state *dst, const double d[2], qsim_state *p, c
     if (q && q != p) QSIM_TRY(stream_waits(dst, q));
     const LaunchCfg cfg{dst->stream, dst->grid_cap};
     QSIM_TRY(launched("combine", launch_combine(cfg, dst->amps, load_dst ? d : nullptr, p->amps, a, q ? q->amps : nullptr, b, dst->f32, dst->n,
-                                                dst->d_expect, sweep_result_row(dst))));
+                                                sweep_partials(dst), sweep_result_row(dst))));
     QSIM_TRY(stream_waits(p, dst));
     if (q && q != p) QSIM_TRY(stream_waits(q, dst));
     if (norm2) QSIM_TRY(fetch_sweep_results(dst, 1, norm2));
