@@ -128,6 +128,19 @@ SIGNATURES = {
     "qsim_apply_matrix_operand": (c_int, [_DP, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, _DP, POINTER(c_int), POINTER(c_int),
                                           POINTER(c_int)]),
     "qsim_matrix_sweeps_launched": (c_uint64, []),
+    "qsim_diagonal_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
+    "qsim_diagonal_create_external": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p]),
+    "qsim_diagonal_destroy": (None, [c_void_p]),
+    "qsim_diagonal_num_qubits": (c_int, [c_void_p]),
+    "qsim_diagonal_device_ptr": (c_void_p, [c_void_p]),
+    "qsim_diagonal_add_terms": (c_int, [c_void_p, POINTER(c_uint64), _DP, c_long]),
+    "qsim_diagonal_write": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
+    "qsim_diagonal_read": (c_int, [c_void_p, c_uint64, c_uint64, _DP]),
+    "qsim_diagonal_extrema": (c_int, [c_void_p, _DP, POINTER(c_uint64), _DP, POINTER(c_uint64)]),
+    "qsim_apply_diagonal_phase": (c_int, [c_void_p, c_void_p, c_double]),
+    "qsim_expect_diagonal": (c_int, [c_void_p, c_void_p, _DP]),
+    "qsim_diagonal_sweeps_launched": (c_uint64, []),
+    "qsim_diagonal_plan": (c_int, [c_int, c_int, POINTER(c_uint64), POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_long)]),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

@@ -285,6 +285,96 @@ class _PauliStrings:
         self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
 
 
+def _diagonal_term_arrays(terms, num_q: int):
+    """(real coefficient, string of I and Z) pairs as the arrays qsim_diagonal_add_terms takes: zs, coeffs and their pointers.
+    ValueError for an X or Y factor or a complex coefficient — pure Python, before anything touches the library."""
+    from ctypes import c_uint64
+    from .pauli import pauli_masks
+    terms = list(terms)
+    masks = []
+    for coeff, text in terms:
+        if isinstance(coeff, complex) or (hasattr(coeff, "dtype") and coeff.dtype.kind == "c"):
+            raise ValueError(f"coefficient {coeff!r} of {text!r} is complex: a diagonal table is real")
+        x, z = pauli_masks(text, num_q)
+        if x:
+            raise ValueError(f"{text!r} has an X or Y factor: a diagonal operator is a sum of strings of I and Z")
+        masks.append(z)
+    zs = np.array(masks, dtype=np.uint64)
+    coeffs = np.array([float(c) for c, _ in terms], dtype=np.float64)
+    return zs, coeffs, zs.ctypes.data_as(ctypes.POINTER(c_uint64)), _dp(coeffs)
+
+
+class Diagonal:
+    """A real table d[0..2^n) of float64 on one GPU: the operator D = sum_i d_i |i><i| on a register of n qubits (qsim_diagonal).
+    Simulator.apply_diagonal_phase applies exp(-i gamma D) and Simulator.expectation_diagonal returns <D>, each in one sweep
+    whatever the number of terms D has.  `ptr` adopts 2^n float64 values already on the device (tensor.data_ptr() of a torch
+    tensor, say); the caller keeps them alive and nothing is freed.  Calls take effect in the order issued."""
+
+    def __init__(self, num_q: int, device: int = 0, ptr: Optional[int] = None):
+        self._h = c_void_p()
+        lib = _lib.load()
+        if ptr is None:
+            check(lib.qsim_diagonal_create(byref(self._h), num_q, device))
+        else:
+            check(lib.qsim_diagonal_create_external(byref(self._h), num_q, device, c_void_p(ptr)))
+        self.num_qubits = num_q
+
+    @classmethod
+    def from_terms(cls, num_q: int, terms, device: int = 0) -> "Diagonal":
+        """The diagonal of sum_k c_k P_k for (c_k, string) pairs, strings of I and Z only ("Z0 Z7"): ValueError for X or Y,
+        before any launch."""
+        arrays = _diagonal_term_arrays(terms, num_q)
+        diag = cls(num_q, device)
+        diag._add(arrays)
+        return diag
+
+    def _add(self, arrays) -> None:
+        zs, coeffs, zp, cp = arrays
+        check(_lib.load().qsim_diagonal_add_terms(self._h, zp, cp, zs.size))
+
+    def add_terms(self, terms) -> None:
+        """d_i += c_k (-1)^popcount(i & z_k), term after term in the order given: bit for bit the sequential sum."""
+        self._add(_diagonal_term_arrays(terms, self.num_qubits))
+
+    def write(self, values, first: int = 0) -> None:
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        check(_lib.load().qsim_diagonal_write(self._h, first, v.size, _dp(v)))
+
+    def read(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        if count is None:
+            count = (1 << self.num_qubits) - first
+        out = np.empty(count, dtype=np.float64)
+        check(_lib.load().qsim_diagonal_read(self._h, first, count, _dp(out)))
+        return out
+
+    def extrema(self) -> dict:
+        """{"min", "argmin", "max", "argmax"} of the table, one reduction on the device; among equal values the lowest index."""
+        from ctypes import c_uint64
+        lo, hi, ilo, ihi = c_double(), c_double(), c_uint64(), c_uint64()
+        check(_lib.load().qsim_diagonal_extrema(self._h, byref(lo), byref(ilo), byref(hi), byref(ihi)))
+        return {"min": float(lo.value), "argmin": int(ilo.value), "max": float(hi.value), "argmax": int(ihi.value)}
+
+    def device_ptr(self) -> int:
+        return int(_lib.load().qsim_diagonal_device_ptr(self._h) or 0)
+
+    def close(self) -> None:
+        if self._h:
+            _lib.load().qsim_diagonal_destroy(self._h)
+            self._h = c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Simulator(_PauliStrings):
     """One state vector resident on one GPU."""
     _expect_fn, _rotate_fn, _check = "qsim_expect_paulis", "qsim_apply_pauli_rotations", staticmethod(check)
@@ -467,6 +557,20 @@ class Simulator(_PauliStrings):
             raise ValueError(f"apply_matrix: at most 5 targets and a matrix of shape (2^k, 2^k); got {len(ts)} targets and shape {m.shape}")
         flat = np.ascontiguousarray(m.reshape(-1)).view(np.float64)
         check(_lib.load().qsim_apply_matrix(self._h, _dp(flat), (c_int * max(len(ts), 1))(*ts), len(ts), (c_int * max(len(cs), 1))(*cs), len(cs)))
+
+    # -- whole-register diagonal operators from a table (single states only: a Cluster has no counterpart)
+    def apply_diagonal_phase(self, diag: Diagonal, gamma: float) -> None:
+        """a_i <- exp(-i gamma d_i) a_i for the table of `diag`: one in-place sweep (qsim_apply_diagonal_phase), launched after
+        the queued gates and not waited for.  For diag = Diagonal.from_terms(n, [(c_k, P_k)]) it equals
+        apply_pauli_rotations([(2 gamma c_k, P_k)]) — a QAOA phase separator in one sweep whatever the number of terms."""
+        check(_lib.load().qsim_apply_diagonal_phase(self._h, diag._h, float(gamma)))
+
+    def expectation_diagonal(self, diag: Diagonal, moments: bool = False):
+        """<D> = sum_i d_i |a_i|^2 for the table of `diag`, one read-only sweep (qsim_expect_diagonal); moments=True returns
+        (<D>, <D^2>), the variance being their <D^2> - <D>^2."""
+        out = np.zeros(2, dtype=np.float64)
+        check(_lib.load().qsim_expect_diagonal(self._h, diag._h, _dp(out)))
+        return (float(out[0]), float(out[1])) if moments else float(out[0])
 
     def run(self, circuit: Circuit, first: int = 0, count: int = -1) -> None:
         check(_lib.load().qsim_run_circuit(self._h, circuit._h, first, count))

@@ -400,6 +400,60 @@ int qsim_apply_matrix_plan(const int *targets, int k, const int *controls, int n
 int qsim_apply_matrix_operand(const double *U, const int *targets, int k, const int *controls, int num_controls, int num_q,
                               int precision_bits, double *M, int *row_amp, int *row_part, int *rows);
 uint64_t qsim_matrix_sweeps_launched(void);  /* process-wide counter, as qsim_density_sweeps_launched */
+/* ---- whole-register diagonal operators from a table: exp(-i gamma D) and <D>, <D^2> in one sweep each (new) ----
+ * A qsim_diagonal is a real table d[0..2^n) of fp64 on one device, the operator D = sum_i d_i |i><i| on a register of n qubits: a
+ * cost function of QAOA, a penalty, a marked set, a potential on a grid — whatever the number of Pauli terms it would take.  The
+ * table is fp64 for fp64 and fp32 states alike.  Single states only: there is NO cluster counterpart.
+ * Ordering: calls take effect in the order issued, as if on one stream, and the caller synchronises nothing.  The calls that fill or
+ * inspect a table (add_terms, write, read, extrema) wait for every sweep that still reads it, run on a stream of the table's own and
+ * have finished when they return (they block the host); the two sweeps run on the state's stream and never wait on the host.
+ * Out of scope: controls on the phase, gradients with respect to gamma, sharded tables, complex tables. */
+typedef struct qsim_diagonal qsim_diagonal;
+/* 2^num_q doubles, all 0, for num_q in [0, 40]; QSIM_ERR_ALLOC when the allocation fails, QSIM_ERR_ARG for num_q or device out of range */
+int qsim_diagonal_create(qsim_diagonal **out, int num_q, int device);
+/* The same on the caller's buffer of 2^num_q doubles on `device` (aligned to 16 bytes), as qsim_create_external adopts a state's: how
+ * a table computed on the device gets in.  Nothing is zeroed and nothing is ever freed; the caller keeps the buffer alive while the
+ * object lives and orders its own work on the buffer against these calls (its writes finished before a call, none during a sweep). */
+int qsim_diagonal_create_external(qsim_diagonal **out, int num_q, int device, void *device_doubles);
+void qsim_diagonal_destroy(qsim_diagonal *d);              /* waits for the sweeps that read the table; NULL is allowed */
+int qsim_diagonal_num_qubits(const qsim_diagonal *d);      /* -1 for NULL */
+void *qsim_diagonal_device_ptr(qsim_diagonal *d);          /* the 2^n doubles in HBM; NULL for NULL */
+/* d_i <- (...((d_i + c_0 s_0(i)) + c_1 s_1(i)) + ...) with s_k(i) = (-1)^popcount(i & z_masks[k]): the diagonal of sum_k c_k P_k for
+ * strings P_k of I and Z, added term after term in the caller's order.  c s is an exact sign flip, so the table is bit for bit the
+ * sequential sum, whatever the grid.  z == 0 adds a constant.  The terms travel to the kernel by value in records of at most 32, one
+ * launch — one read and one write of the table — per record; nothing is allocated.  num_terms == 0 does nothing.
+ * QSIM_ERR_ARG, the table unchanged: a NULL table, NULL arrays with num_terms > 0, a negative count, a mask bit at or above n. */
+int qsim_diagonal_add_terms(qsim_diagonal *d, const uint64_t *z_masks, const double *coeffs, long num_terms);
+/* entries [first, first + count) from and to host memory; QSIM_ERR_ARG for a range outside the table or a NULL pointer with count > 0 */
+int qsim_diagonal_write(qsim_diagonal *d, uint64_t first, uint64_t count, const double *host);
+int qsim_diagonal_read(qsim_diagonal *d, uint64_t first, uint64_t count, double *host);
+/* The smallest and the largest entry and where they are, one read-only reduction: the optimum of a cost function, the scale of an
+ * approximation ratio.  Among equal values the LOWEST index is returned, and equal calls return equal results.  A table that holds a
+ * NaN gives unspecified results. */
+int qsim_diagonal_extrema(qsim_diagonal *d, double *min, uint64_t *argmin, double *max, uint64_t *argmax);
+/* a_i <- exp(-i gamma d_i) a_i for every amplitude, in place, in ONE sweep that reads the state and the table and writes the state.
+ * With D = sum_k c_k P_k built by qsim_diagonal_add_terms the call equals qsim_apply_pauli_rotations with theta_k = 2 gamma c_k.
+ * The factor is formed in fp64 for both precisions, by sincospi of (gamma / pi) d_i — exact argument reduction, whatever the
+ * magnitude — rounded once to the state's precision and multiplied in that precision.  The call settles the state first (queued gates
+ * are launched, a lazily held |0...0> or a partial support is written out: afterwards the state is dense), launches on the state's
+ * stream and returns without waiting; it allocates nothing and every amplitude is written by one thread: equal calls give equal bits.
+ * Sweeps are NOT counted in the qsim_stats record; qsim_diagonal_sweeps_launched counts them.  A shard that holds nothing
+ * (qsim_holds_nothing) stays as it is and launches no sweep.
+ * QSIM_ERR_ARG, nothing launched: a NULL argument, a table over another number of qubits or on another device, a non-finite gamma. */
+int qsim_apply_diagonal_phase(qsim_state *s, const qsim_diagonal *d, double gamma);
+/* out[0] = sum_i d_i |a_i|^2 = <D> and out[1] = sum_i d_i^2 |a_i|^2 = <D^2> (for the variance), one read-only sweep after the queued
+ * gates; the state's bits stay as they are.  The sums are fp64 in both precisions and are added in a fixed order: equal calls return
+ * equal bits.  A shard that holds nothing gives zeros and launches no sweep.  QSIM_ERR_ARG as above, and for a NULL out. */
+int qsim_expect_diagonal(qsim_state *s, const qsim_diagonal *d, double out[2]);
+uint64_t qsim_diagonal_sweeps_launched(void); /* process-wide counter of the two sweeps above (not of the calls that fill a table) */
+/* Host only, no device: how the two sweeps walk a register of num_q qubits held in precision_bits (64 or 32).  *items: the work
+ * items, one 16-byte unit of the table = two amplitudes each (1 for a register of one amplitude); *items_per_trip_*: items per thread
+ * and trip of a workgroup's loop; *trips_at_cap_*: the trips of that loop when the grid is at its cap (2048 workgroups for the phase
+ * sweep, 1024 for the expectation sweep; a device that holds fewer at once makes more).  Registers of fewer than 128 amplitudes take
+ * a plain path of one workgroup and one trip.  QSIM_ERR_ARG for num_q outside [0, 40], precision_bits other than 64 or 32, a NULL
+ * result pointer. */
+int qsim_diagonal_plan(int num_q, int precision_bits, uint64_t *items, int *items_per_trip_phase, int *items_per_trip_expect,
+                       long *trips_at_cap_phase, long *trips_at_cap_expect);
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
