@@ -1,7 +1,8 @@
 // engine.cpp — the core of the C ABI of include/qsim.h: errors, the device state and its options, the gate queue, the launch of
-// a pass, the plan cache and the flush that routes a queue's passes through the state's buffers.
+// a pass, the plan cache, the rule by which a flush schedules (flush_rule) and the flush that routes a queue's passes through the
+// state's buffers.
 // Host C++ compiled by hipcc for the HIP runtime API; every kernel lives in kernels.hip.  Owns qsim_state (engine_state.h) and
-// the thread's error message; calls the scheduler, the launchers of qsim_internal.h and, in planning.cpp, the lookups of the
+// the thread's error message; calls the scheduler, the launchers of qsim_internal.h and, in wisdom.cpp, the lookups of the
 // measured tables (order_tile_bits, apply_sched_hint, have_sched_hints, wisdom_epoch).
 //
 // There is no CPU execution path in this file or anywhere in libqsim.so: if the HIP runtime reports no
@@ -825,6 +826,29 @@ class PassRouter {
 
 } // namespace
 
+// How a flush schedules `gates` on a state that has `support` (FlushRule, engine_state.h).  The ONE statement of it: flush_impl runs
+// by it, and whatever says beforehand what a flush will do (qsim_support_after, the key choose_schedule files its choice under) asks here.
+FlushRule qsim::flush_rule(qsim_state *s, const std::vector<QueuedGate> &gates, uint64_t support, bool for_pack, bool want_key) {
+    FlushRule r;
+    r.support = support;
+    r.cacheable = s->plan_cache && s->fuse >= 3 && s->debug_tile_order == 0 && gates.size() >= 8;
+    r.hinted = s->fuse >= 3 && have_sched_hints();
+    // only a plain single-state flush defers X gates, and by default only where the planning step chose a schedule that does
+    r.defer = !for_pack && (s->defer_flips == 2 || (s->defer_flips == 1 && r.hinted)) && may_defer_flips(s) ? s->defer_flips : 0;
+    if (r.cacheable || r.hinted || want_key) {
+        r.id = plan_identity(s, gates.size(), support);
+        r.id.defer = r.defer;
+        r.key = gates_key(s, r.id, gates.data(), gates.size());
+    }
+    return r;
+}
+SchedConfig FlushRule::config(const qsim_state *s) const {
+    SchedConfig cfg = state_sched_config(s, support);
+    if (hinted) apply_sched_hint(key, cfg);
+    cfg.defer_flips = defer == 2 || (defer == 1 && cfg.defer_flips) ? 1 : 0;
+    return cfg;
+}
+
 // job != NULL: if the LAST pass of the queue is a tile pass that can do it, that pass writes the state re-laid-out (job->packed_at
 // says where) and the state's own buffers are left holding stale data; otherwise everything runs as usual and job->packed_at
 // stays NULL (the caller then runs the pack kernel).
@@ -839,18 +863,9 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
     if (s->tile_bits - s->tile_low_bits < 2 || s->tile_bits - s->tile_low_bits > kMaxTileHigh)
         return fail(QSIM_ERR_ARG, "tile_bits - tile_low_bits must be in 2..%d", kMaxTileHigh);
     HIP_TRY(hipSetDevice(s->device));
-    const bool cacheable = s->plan_cache && s->fuse >= 3 && s->debug_tile_order == 0 && s->queue.size() >= 8;
-    const bool hinted = s->fuse >= 3 && have_sched_hints();
-    PlanRecorder rec;
-    uint64_t key = 0;
-    // only a plain single-state flush defers X gates, and by default only where the planning step chose a schedule that does
-    const int defer = !job && (s->defer_flips == 2 || (s->defer_flips == 1 && hinted)) && may_defer_flips(s) ? s->defer_flips : 0;
-    if (cacheable || hinted) {
-        rec.plan.id = plan_identity(s, s->queue.size(), current_support(s));
-        rec.plan.id.defer = defer;
-        key = gates_key(s, rec.plan.id, s->queue.data(), s->queue.size());
-    }
-    const uint64_t epoch = wisdom_epoch();
+    FlushRule rule = flush_rule(s, s->queue, current_support(s), job != nullptr);
+    const bool cacheable = rule.cacheable;
+    const uint64_t key = rule.key, epoch = wisdom_epoch();
     // The flips the router could not hand to the last tile pass (PassRouter rule 6) run as X gates in passes of their own,
     // scheduled the ordinary way and pushed behind the others: right, at the price of one more pass, and counted.
     auto settle_flips = [&](PassRouter &router, uint64_t flip) {
@@ -863,7 +878,7 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
             if (flip >> q & 1ULL) xs.add_1q(kX, q);
         xs.finish([&](Pass &&p) { router.push(std::move(p)); });
     };
-    if (const CachedPlan *pl = cacheable ? find_plan(s, key, epoch, rec.plan.id) : nullptr) { // replay: no scheduling, no block preparation, no H2D copy
+    if (const CachedPlan *pl = cacheable ? find_plan(s, key, epoch, rule.id) : nullptr) { // replay: no scheduling, no block preparation, no H2D copy
         s->queue.clear();
         PassRouter router(s, job, nullptr, pl->flip);
         for (size_t i = 0; i < pl->passes.size(); i++) {
@@ -874,13 +889,14 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
         settle_flips(router, pl->flip); // (a plan is recorded with the flip its last pass took, so this finds nothing to do)
         return router.finish();
     }
-    SchedConfig scfg = state_sched_config(s, current_support(s));
-    if (hinted) apply_sched_hint(key, scfg);
-    scfg.defer_flips = defer == 2 || (defer == 1 && scfg.defer_flips) ? 1 : 0;
-    Scheduler sched(scfg);
+    Scheduler sched(rule.config(s));
     feed(sched, s->queue);
     const uint64_t flip = sched.residual_flips(); // known before the first pass is built
-    if (cacheable) rec.plan.id.gates = std::move(s->queue); // the plan remembers what it was built from
+    PlanRecorder rec;
+    if (cacheable) {
+        rec.plan.id = std::move(rule.id);
+        rec.plan.id.gates = std::move(s->queue); // the plan remembers what it was built from
+    }
     s->queue.clear();
     // passes are launched as they are scheduled, as far as the routing allows (PassRouter, rules 2 and 3)
     PassRouter router(s, job, cacheable ? &rec : nullptr, flip);
@@ -893,6 +909,7 @@ int qsim::flush_impl(qsim_state *s, PackJob *job) {
 
 bool qsim::may_defer_flips(qsim_state *s) {
     if (s->defer_flips == 0 || s->fuse < 3 || s->f32 || !s->owns) return false;
+    if (!s->alloc_done.load()) return false; // qsim_create_async is still allocating the first buffer: the second cannot be asked for beside it (every flush has joined that)
     TileGeom g{};
     g.tile_bits = std::min(s->tile_bits, s->n);
     if (!launch_tile_can_pack(false, g, s->tile_threads)) return false;

@@ -1,8 +1,12 @@
 // engine_state.h — what the host files of the engine share: the state behind the C ABI's qsim_state, the gate queue's record,
 // the error channel, and the few internal functions that cross a file boundary.  Host only: the kernels include
 // qsim_internal.h, never this.  Who defines what:
-//   engine.cpp    errors, create / destroy, options, reset / support, the gate queue, launch_pass, the plan cache, the flush
-//   planning.cpp  the measured tile-bit orders and schedule choices (process-wide tables, private to it) and the planning API
+//   engine.cpp    errors, create / destroy, options, reset / support, the gate queue, launch_pass, the plan cache, the flush and
+//                 the rule by which a flush schedules (flush_rule)
+//   wisdom.cpp    the measured tile-bit orders and schedule choices (process-wide tables, private to it) and their file format
+//   planning.cpp  the schedule choice per circuit and the timed planning (qsim_choose_schedule*, qsim_support_after, qsim_tune_circuit*)
+//   plan_probe.cpp  the device-free probes of a circuit's schedule (qsim_plan_*, qsim_schedule_circuit*, qsim_tile_records);
+//                 planning.h is what these three share
 //   readout.cpp   reads, writes, norms, sampling                             pack.cpp  re-layouts and buffer hand-overs
 //   profile.cpp   profiling events, statistics, the launch log              pauli.cpp  Pauli strings: expectation values, rotations
 //                                                                           (controlled ones too) and adjoint gradients (the host
@@ -64,6 +68,19 @@ struct PlanIdentity {
     qsim::SchedEnv env;
     int defer = 0; // QSIM_OPT_DEFER_FLIPS as it applies to this flush (0: the flush may not defer X gates at all)
     std::vector<QueuedGate> gates;
+};
+
+// How a flush schedules a queue of gates on a state that has a given support: the decisions flush_impl runs by, and what anything
+// that predicts a flush (qsim_support_after for a cluster's exchanges, the key the planning step files a choice under) must go by.
+struct FlushRule {
+    bool cacheable = false; // the plan of this queue is kept and replayed (QSIM_OPT_PLAN_CACHE)
+    bool hinted = false;    // a remembered schedule choice may apply to it
+    int defer = 0;          // QSIM_OPT_DEFER_FLIPS as it applies to this flush (0: it may not defer X gates at all)
+    uint64_t support = 0;   // where the state can be non-zero when the flush starts
+    uint64_t key = 0;       // the queue's 64-bit name and the identity behind it (without the gates): only where cacheable or
+    PlanIdentity id;        // hinted holds, or the caller asked for them
+    // The scheduler's configuration: the hint applied, defer_flips settled.  Worked out on request — a replay schedules nothing.
+    qsim::SchedConfig config(const qsim_state *s) const;
 };
 
 struct CachedPlan {
@@ -201,9 +218,12 @@ int launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, bool fr
                      uint64_t zero_mask = 0, PackJob *job = nullptr, uint64_t flip = 0);
 // qsim_flush; job != NULL: the last pass may write the state re-laid-out instead (PackJob, the comment at the definition).
 int flush_impl(qsim_state *s, PackJob *job);
+// How flush_impl will schedule these gates on a state with this support (for_pack: a flush with a PackJob).  want_key: key and
+// identity are wanted whatever the flush would need them for.
+FlushRule flush_rule(qsim_state *s, const std::vector<QueuedGate> &gates, uint64_t support, bool for_pack, bool want_key = false);
 bool trace_pack(); // QSIM_TRACE_PACK is set: stderr says why a re-layout got a sweep of its own
 
-// ---- planning.cpp ----------------------------------------------------------------------------------------------------------
+// ---- wisdom.cpp (what the engine looks up; planning.h has what the planning step enters) ---------------------------------------
 // Counts the tile pass and gives its high bits the measured order, if there is one (or the probe order of QSIM_OPT_DEBUG_TILE_ORDER).
 // zero_mask: the index bits the state is zero in when the pass starts (0: a full or a generating pass) — the high bits among
 // them end up topmost (place_new_bits), where the kernel drops their loads.

@@ -1,0 +1,167 @@
+// plan_probe.cpp — the calls that say how a circuit WOULD be scheduled without running anything: qsim_plan_circuit*, qsim_plan_passes,
+// qsim_schedule_circuit*, qsim_tile_records.  They take a circuit and the options that shape a schedule, never a qsim_state, and make
+// no HIP call: the CPU tests and tools/sched_digest.py stand on them.  Also queue_of and schedule, which planning.cpp shares (planning.h).
+#include <cstring>
+
+#include "planning.h"
+
+using namespace qsim;
+
+std::vector<QueuedGate> qsim::queue_of(const qsim_circuit *c) {
+    std::vector<QueuedGate> q;
+    q.reserve((size_t)c->count);
+    for (long i = 0; i < c->count; i++) q.emplace_back(*c, c->gates[i]);
+    return q;
+}
+
+std::vector<Pass> qsim::schedule(const SchedConfig &cfg, const std::vector<QueuedGate> &gates, uint64_t *gates_seen, uint64_t *residual_flips) {
+    Scheduler sv(cfg);
+    feed(sv, gates);
+    std::vector<Pass> passes;
+    sv.finish(passes);
+    if (gates_seen) *gates_seen = sv.gates_seen();
+    if (residual_flips) *residual_flips = sv.residual_flips();
+    return passes;
+}
+
+namespace {
+// What a probe is asked about, beside the circuit and the fuse level: the options of a state that shape its schedules.
+struct ProbeShape {
+    int tile_bits, tile_low_bits, tile_max_ops = 32;
+    uint64_t initial_support = 0;
+    bool defer = false; // the X gates left to an index flip (SchedConfig::defer_flips): residual_flips says which
+};
+
+// How every probe opens: the arguments checked (have_args: the caller's pointers are all there) and the circuit scheduled as an
+// fp64 state with these options would schedule it.
+int probe_passes(bool have_args, const qsim_circuit *c, int fuse, const ProbeShape &shape, std::vector<Pass> &passes, uint64_t *gates_seen = nullptr,
+                 uint64_t *residual_flips = nullptr) {
+    if (!have_args || !c) return fail(QSIM_ERR_ARG, "NULL argument");
+    if (fuse < 0 || fuse > 3) return fail(QSIM_ERR_ARG, "fuse level %d not in 0..3", fuse);
+    SchedConfig cfg = engine_sched_config(c->num_q, fuse, shape.tile_bits, shape.tile_low_bits, shape.tile_max_ops, 10, false, shape.initial_support);
+    cfg.defer_flips = shape.defer ? 1 : 0;
+    passes = schedule(cfg, queue_of(c), gates_seen, residual_flips);
+    return QSIM_OK;
+}
+
+// A block as the probes report it: ONE matrix, as (re, im) doubles, on (selecting qubits..., tile qubits...).
+struct BlockView {
+    std::vector<cd> full = std::vector<cd>((size_t)256 * 256);
+    std::vector<double> matrix = std::vector<double>((size_t)2 * 256 * 256);
+    int qubits[kMaxBlockQ + 2], nq = 0;
+    void set(const TileBlock &blk) {
+        nq = 0;
+        for (int a = 0; a < blk.ns; a++) qubits[nq++] = blk.s[a];
+        for (int a = 0; a < blk.nq; a++) qubits[nq++] = blk.q[a];
+        const int D = 1 << nq;
+        blk.full_matrix(full.data());
+        for (int k = 0; k < D * D; k++) { matrix[2 * k] = full[k].real(); matrix[2 * k + 1] = full[k].imag(); }
+    }
+};
+
+int report_schedule(const std::vector<Pass> &passes, qsim_sched_cb cb, void *user) {
+    int pi = 0;
+    BlockView view;
+    for (const Pass &p : passes) {
+        for (const FusedOp &op : p.ops) {
+            double U[128];
+            const int d = op.kind == OP_CX ? 0 : op.dim();
+            for (int k = 0; k < d * d; k++) { U[2 * k] = op.m[k].real(); U[2 * k + 1] = op.m[k].imag(); }
+            const int kind = op.kind == OP_G1 ? QSIM_GATE_U1 : op.kind == OP_CX ? QSIM_GATE_CX : QSIM_GATE_U2;
+            const int qs[2] = {op.q_hi, op.q_lo};
+            cb(user, pi, p.kclass, kind, qs, op.kind == OP_CX ? 2 : op.nq(), d ? U : nullptr, (int)op.gates);
+        }
+        for (const TileBlock &blk : p.blocks) {
+            TileOp t;
+            if (!to_tile_op(p.geom, blk, t)) return fail(QSIM_ERR_ARG, "internal: block does not fit its tile pass");
+            view.set(blk);
+            static const int kinds[9] = {0, QSIM_GATE_U1, QSIM_GATE_U2, QSIM_GATE_U3, QSIM_GATE_U4, QSIM_GATE_U5, QSIM_GATE_U6, QSIM_GATE_U7, QSIM_GATE_U8};
+            cb(user, pi, p.kclass, kinds[view.nq], view.qubits, view.nq, view.matrix.data(), (int)blk.gates);
+        }
+        pi++;
+    }
+    return QSIM_OK;
+}
+} // namespace
+
+extern "C" int qsim_plan_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, qsim_stats *out) {
+    return qsim_plan_circuit_from(c, fuse, tile_bits, tile_low_bits, 0, out);
+}
+
+extern "C" int qsim_plan_circuit_from(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, uint64_t initial_support, qsim_stats *out) {
+    std::vector<Pass> passes;
+    uint64_t gates = 0;
+    QSIM_TRY(probe_passes(out != nullptr, c, fuse, {tile_bits, tile_low_bits, 32, initial_support}, passes, &gates));
+    memset(out, 0, sizeof *out);
+    out->gates = gates;
+    for (const Pass &p : passes) { // a run from a reset: the first tile passes visit part of the register (Pass::visited)
+        out->launches++;
+        out->algorithmic_bytes += p.moved();
+        out->k_launches[p.kclass]++;
+        out->k_bytes[p.kclass] += p.moved();
+    }
+    return QSIM_OK;
+}
+
+// The same schedule pass by pass: which qubits each tile pass holds in its tile, how much of the register it visits and what the
+// planning steps price it at.  What a host-side model needs to decide which passes could run chunk by chunk beside an exchange
+// (bench.py exchange_model: a pass can only be pipelined over index bits that are NOT in its tile).
+extern "C" int qsim_plan_passes(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, uint64_t initial_support, qsim_pass_info *out, int cap,
+                                int *count) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(count && !(cap > 0 && !out), c, fuse, {tile_bits, tile_low_bits, 32, initial_support}, passes));
+    *count = (int)passes.size();
+    for (size_t i = 0; i < passes.size() && (int)i < cap; i++) {
+        const Pass &p = passes[i];
+        qsim_pass_info &o = out[i];
+        o.kernel_class = p.kclass;
+        o.blocks = p.kclass == QSIM_K_TILE ? (int)p.blocks.size() - p.geom.n_scale : 1;
+        o.tile_mask = p.kclass == QSIM_K_TILE ? tile_mask(p.geom) : index_mask(c->num_q); // a single-gate kernel: treat every bit as touched
+        o.visited = p.visited;
+        o.bytes = p.moved();
+        o.cost_bytes = pass_time_cost(p, false);
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
+                                     qsim_sched_cb cb, void *user) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(cb != nullptr, c, fuse, {tile_bits, tile_low_bits, tile_max_ops}, passes));
+    return report_schedule(passes, cb, user);
+}
+
+extern "C" int qsim_schedule_circuit_deferred(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
+                                              qsim_sched_cb cb, void *user, uint64_t *flip_mask) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(cb && flip_mask, c, fuse, {tile_bits, tile_low_bits, tile_max_ops, 0, true}, passes, nullptr, flip_mask));
+    return report_schedule(passes, cb, user);
+}
+
+// The same schedule as the records k_tile would read: every block of every tile pass (the TOP_SCALE factors included) encoded by
+// to_tile_op under the pass's geometry, with that geometry, the block's qubits and its matrix beside it.  order_seed != 0: the
+// high tile bits of every pass are shuffled first (seeded by it and the pass index), as the engine may reorder them
+// (order_tile_bits) — the record then speaks about other tile-local bits while the block stays the same.  What a host-side model
+// of the record contract is checked against (tests/tile_record_ref.py).
+extern "C" int qsim_tile_records(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, int f32, uint64_t order_seed,
+                                 qsim_tile_record_cb cb, void *user) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(cb != nullptr, c, fuse, {tile_bits, tile_low_bits, tile_max_ops}, passes));
+    int pi = 0;
+    BlockView view;
+    std::vector<TileOp> rec(1); // (zeroed, padding included: the callback is handed its bytes)
+    for (const Pass &p : passes) {
+        if (p.kclass == QSIM_K_TILE) {
+            TileGeom g = p.geom;
+            if (order_seed) shuffle_high(g, probe_order_seed(order_seed, (uint64_t)(pi + 1)));
+            for (const TileBlock &blk : p.blocks) {
+                if (!to_tile_op(g, blk, rec[0], f32 != 0)) return fail(QSIM_ERR_ARG, "internal: block does not fit its tile pass");
+                view.set(blk);
+                const int geom[3] = {g.tile_bits, g.low_bits, g.n_high};
+                cb(user, pi, geom, g.high, blk.s, blk.ns, blk.q, blk.nq, view.matrix.data(), &rec[0], (long)sizeof(TileOp));
+            }
+        }
+        pi++;
+    }
+    return QSIM_OK;
+}

@@ -7,6 +7,9 @@ schedule as it is.  Host only: no device is opened (torch is not loaded), nothin
                                      own; fails unless the files differ from one another (every knob was live)
   sched_digest.py --shard-plans OUT.txt   the shard planner's plans (it schedules every segment with gates tracked per pass and a partial
                                      initial support), in the configurations of profiles/dist_split: run it with QSIM_SHARD_TAIL unset, 0 and 24
+  sched_digest.py --tile-records OUT.txt [ORDER_SEED ...]   what the digests above do not cover: Circuit.tile_records() — every field of
+                                     every record, under order seeds 0, 1 and 7 unless others are named (files of different seeds must
+                                     differ) — and the schedule with deferred X gates, Circuit.schedule(flips=[]), with its flip mask
 
 A configuration is random_gates(n, 1000, seed, vocabulary) x fuse x tile geometry; its digest is the sha256 over
   * every entry of Circuit.schedule() for tile_max_ops 1, 8 and 32: pass, kernel class, kind, qubits, gates folded, matrix as raw bytes;
@@ -96,6 +99,34 @@ def shard_plans(path):
             out.write(f"n={n} configurations={len(group)} steps={steps} exchanges={exchanged} {hashlib.sha256(' '.join(group).encode()).hexdigest()}\n")
 
 
+def tile_records(path, order_seeds=(0, 1, 7)):
+    """One line per n: random_gates(n, 400, seed, vocabulary) x geometry, each with its records for fp64 and fp32 under every order
+    seed (matrices and record bytes raw) and its deferred schedule with the flip mask."""
+    from gpu_quantum_simulator_amd import Circuit, circuits
+    with open(path, "w") as out:
+        for n in (3, 6, 9, 12, 16):
+            h, records = hashlib.sha256(), 0
+            for vocabulary in VOCABULARIES:
+                for seed in (11, 12):
+                    c = Circuit.from_gates(n, circuits.random_gates(n, 400, seed, vocabulary))
+                    for tile_bits, low_bits in ((12, 3), (13, 4), (8, 2)):
+                        for f32 in (0, 1):
+                            for order_seed in order_seeds:
+                                for r in c.tile_records(3, tile_bits, low_bits, 32, bool(f32), order_seed):
+                                    h.update(repr((vocabulary, seed, tile_bits, low_bits, f32, order_seed, r["pass"], r["tile_bits"], r["low_bits"],
+                                                   r["high"], r["selectors"], r["qubits"])).encode())
+                                    h.update(r["matrix"].tobytes())
+                                    h.update(r["record"])
+                                    records += 1
+                        flips = []
+                        for pass_i, kclass, kind, qubits, matrix, folded in c.schedule(3, tile_bits, low_bits, 32, flips):
+                            h.update(repr((pass_i, kclass, kind, qubits, folded)).encode())
+                            if matrix is not None:
+                                h.update(matrix.tobytes())
+                        h.update(repr(flips).encode())
+            out.write(f"n={n} order_seeds={','.join(map(str, order_seeds))} records={records} {h.hexdigest()}\n")
+
+
 def run(path, jobs):
     from multiprocessing import Pool
     with Pool(jobs) as pool: # the workers are forked before the library is loaded
@@ -127,6 +158,8 @@ if __name__ == "__main__":
         run_all(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 4)
     elif len(sys.argv) >= 3 and sys.argv[1] == "--shard-plans":
         shard_plans(sys.argv[2])
+    elif len(sys.argv) >= 3 and sys.argv[1] == "--tile-records":
+        tile_records(sys.argv[2], tuple(int(x) for x in sys.argv[3:]) or (0, 1, 7))
     elif len(sys.argv) >= 2:
         run(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 4)
     else:
