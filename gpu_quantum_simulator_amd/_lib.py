@@ -141,6 +141,12 @@ SIGNATURES = {
     "qsim_expect_diagonal": (c_int, [c_void_p, c_void_p, _DP]),
     "qsim_diagonal_sweeps_launched": (c_uint64, []),
     "qsim_diagonal_plan": (c_int, [c_int, c_int, POINTER(c_uint64), POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_long)]),
+    "qsim_diagonal_gradient": (c_int, [c_void_p, c_long, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), _DP, POINTER(c_uint64),
+                                       POINTER(c_uint64), _DP, c_long, c_void_p, c_double, _DP, _DP]),
+    "qsim_diagonal_gradient_plan": (c_int, [POINTER(ctypes.c_ubyte), POINTER(c_uint64), POINTER(c_uint64), c_long, POINTER(c_uint64), c_long, c_int, c_int, c_int,
+                                            POINTER(c_long), POINTER(c_long), POINTER(c_long), POINTER(c_int), POINTER(c_long)]),
+    "qsim_diagonal_adjoint_sweeps_launched": (c_uint64, []),
+    "qsim_diagonal_apply_into": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_int]),
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),

@@ -1,5 +1,7 @@
 // diagonal.cpp — whole-register diagonal operators: the qsim_diagonal object (a real fp64 table d[0..2^n) on the device), the plan,
-// the set-up calls that fill and inspect a table, and the two sweeps over a state, exp(-i gamma D) and <D>, <D^2>.
+// the set-up calls that fill and inspect a table, the two sweeps over a state, exp(-i gamma D) and <D>, <D^2>, and
+// dst = w D |state> (qsim_diagonal_apply_into).  The gradient through diagonal phases is pauli.cpp's, which owns the adjoint algorithm
+// (DESIGN §7k); what it needs of a table is exported at the end.
 // The kernels are diagonal.hip's; diagonal.h has the work item they share with this file.
 //
 // Ordering.  Calls take effect in the order issued without the caller synchronising anything.  A table has a stream of its own for
@@ -193,7 +195,7 @@ extern "C" int qsim_diagonal_plan(int num_q, int precision_bits, uint64_t *items
 }
 
 // ---- the two sweeps over a state --------------------------------------------------------------------------------------------------
-static int check_pair(const char *who, const qsim_state *s, const qsim_diagonal *d) {
+int qsim::check_diag_pair(const char *who, const qsim_state *s, const qsim_diagonal *d) {
     if (!s || !d) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
     if (d->n != s->n) return fail(QSIM_ERR_ARG, "%s: a table over %d qubits on a state of %d", who, d->n, s->n);
     if (d->device != s->device) return fail(QSIM_ERR_ARG, "%s: the table lives on device %d, the state on device %d", who, d->device, s->device);
@@ -201,7 +203,7 @@ static int check_pair(const char *who, const qsim_state *s, const qsim_diagonal 
 }
 
 // the event behind the sweep just launched on the state's stream: what a later modification of the table waits for
-static int mark_read(const qsim_state *s, const qsim_diagonal *cd) {
+int qsim::mark_read(const qsim_state *s, const qsim_diagonal *cd) {
     qsim_diagonal *d = const_cast<qsim_diagonal *>(cd); // the bookkeeping is not the table
     qsim_diagonal::Reader *r = nullptr;
     for (auto &have : d->readers)
@@ -219,7 +221,7 @@ static int mark_read(const qsim_state *s, const qsim_diagonal *cd) {
 
 extern "C" int qsim_apply_diagonal_phase(qsim_state *s, const qsim_diagonal *d, double gamma) {
     const char *who = "qsim_apply_diagonal_phase";
-    QSIM_TRY(check_pair(who, s, d));
+    QSIM_TRY(check_diag_pair(who, s, d));
     if (!std::isfinite(gamma)) return fail(QSIM_ERR_ARG, "%s: a non-finite gamma", who);
     if (qsim_holds_nothing(s)) return QSIM_OK; // the zero vector stays the zero vector
     QSIM_TRY(await_buffer(s));
@@ -232,7 +234,7 @@ extern "C" int qsim_apply_diagonal_phase(qsim_state *s, const qsim_diagonal *d, 
 
 extern "C" int qsim_expect_diagonal(qsim_state *s, const qsim_diagonal *d, double out[2]) {
     const char *who = "qsim_expect_diagonal";
-    QSIM_TRY(check_pair(who, s, d));
+    QSIM_TRY(check_diag_pair(who, s, d));
     if (!out) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
     out[0] = out[1] = 0.0;
     if (qsim_holds_nothing(s)) return QSIM_OK; // zeros, no sweep
@@ -244,4 +246,24 @@ extern "C" int qsim_expect_diagonal(qsim_state *s, const qsim_diagonal *d, doubl
     g_diagonal_sweeps++;
     QSIM_TRY(mark_read(s, d));
     return fetch_sweep_results(s, 2, out);
+}
+
+// ---- what pauli.cpp's gradient needs of a table (diagonal.h) ------------------------------------------------------------------------
+const double *qsim::diag_table(const qsim_diagonal *d) { return d->table; }
+void qsim::count_diagonal_sweep() { g_diagonal_sweeps++; }
+
+// dst (= | +=) weight D |state>, out of place (k_diag_apply): the diagonal part of lambda = H psi on its own, as qsim_pauli_sum_into
+// is the Pauli part
+extern "C" int qsim_diagonal_apply_into(qsim_state *s, const qsim_diagonal *d, double weight, void *dst_device, int accumulate) {
+    const char *who = "qsim_diagonal_apply_into";
+    QSIM_TRY(check_diag_pair(who, s, d));
+    if (!std::isfinite(weight)) return fail(QSIM_ERR_ARG, "%s: a non-finite weight", who);
+    QSIM_TRY(await_buffer(s));
+    if (!dst_device || dst_device == s->amps || dst_device == s->spare)
+        return fail(QSIM_ERR_ARG, "%s: the destination is NULL or one of the state's own buffers", who);
+    QSIM_TRY(settle(s));
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    QSIM_TRY(launched("qsim_diagonal_apply_into:", launch_diag_apply(cfg, s->amps, dst_device, s->f32, s->n, d->table, weight, accumulate != 0)));
+    g_diagonal_sweeps++;
+    return mark_read(s, d);
 }

@@ -3,6 +3,9 @@
 //     k_diag_expect      sum_i d_i |a_i|^2 and sum_i d_i^2 |a_i|^2, read-only, one sweep
 //     k_diag_add_terms   d_i <- d_i + c_0 s_0(i) + c_1 s_1(i) + ..., added in the caller's order, s_k(i) = (-1)^popcount(i & z_k)
 //     k_diag_extrema     min, argmin, max, argmax of the table, ties to the lowest index
+//     k_diag_adjoint     the backward sweep of an adjoint gradient through exp(-i gamma D): sum_i d_i Im(conj(lam_i) psi_i), and psi
+//                        and lambda stepped back, one sweep: read psi, lambda and d, write psi and lambda
+//     k_diag_apply       dst_i (= | +=) w d_i src_i, out of place: the diagonal part of lambda = H psi
 // Its own object, like combine.hip: nothing here is compiled into kernels.hip.  diagonal.h has the work item and the geometry;
 // diagonal.cpp is the host side.
 //
@@ -172,6 +175,158 @@ __global__ __launch_bounds__(kTPB) void k_diag_expect(const R *__restrict__ a, c
     }
 }
 
+// ---- the backward sweep of an adjoint gradient through exp(-i gamma D) --------------------------------------------------
+// acc += dv Im(conj(lam) psi) from the values as they come in, then both amplitudes times ONE factor: phase_amp's, formed once and
+// rounded once, so psi is stepped exactly as k_diag_phase would step it.  The components of an fp32 state are widened first: each
+// product is then exact and their difference rounds once.
+template <typename R>
+__device__ __forceinline__ void adjoint_amp(double &acc, R &pr, R &pi, R &lr, R &li, double dv, double gamma_over_pi) {
+    acc = fma(dv, fma((double)lr, (double)pi, -((double)li * (double)pr)), acc);
+    double sn, cs;
+    sincospi(gamma_over_pi * dv, &sn, &cs);
+    const R c = (R)cs, sv = (R)-sn;
+    rotate_diag(pr, pi, c, sv);
+    rotate_diag(lr, li, c, sv);
+}
+
+template <typename R>
+__global__ __launch_bounds__(kTPB) void k_diag_adjoint(R *psi, R *lam, const double *__restrict__ d, DiagGeom g, double gamma_over_pi,
+                                                      double *__restrict__ partial) {
+    using V = typename Vec16<R>::type;
+    using P = typename Amp<R>::type;
+    constexpr bool F32 = sizeof(R) == 4;
+    constexpr int U = diag_adjoint_items_per_trip(F32), S = F32 ? 1 : 2;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+
+    double acc = 0.0;
+    if (g.items < (uint64_t)kDiagWave) { // the plain path: one workgroup, one thread per amplitude
+        if (blockIdx.x == 0 && tid < g.amps) {
+            P pv = *reinterpret_cast<const P *>(psi + 2 * tid), lv = *reinterpret_cast<const P *>(lam + 2 * tid);
+            adjoint_amp(acc, pv.x, pv.y, lv.x, lv.y, d[tid], gamma_over_pi);
+            *reinterpret_cast<P *>(psi + 2 * tid) = pv;
+            *reinterpret_cast<P *>(lam + 2 * tid) = lv;
+        }
+    } else {
+        for (uint64_t q0 = (uint64_t)blockIdx.x * U; (q0 << kTidBits) < g.items; q0 += (uint64_t)gridDim.x * U) {
+            V pv[U][S], lv[U][S];
+            double2 td[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t t = ((q0 + u) << kTidBits) | tid;
+                td[u] = double2{};
+#pragma unroll
+                for (int s = 0; s < S; s++) pv[u][s] = V{}, lv[u][s] = V{};
+                if (t < g.items) { // uniform over a wave: items is a multiple of 64
+                    td[u] = *reinterpret_cast<const double2 *>(d + 2 * t);
+#pragma unroll
+                    for (int s = 0; s < S; s++) {
+                        const uint64_t amp = first_amp<R>(t, lane) + (uint64_t)kDiagWave * s; // psi and lambda at the same index
+                        pv[u][s] = load_unit(const_cast<const R *>(psi), amp);
+                        lv[u][s] = load_unit(const_cast<const R *>(lam), amp);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) { // a unit that was not loaded is zeros against table entries of zero: it adds nothing
+                const uint64_t t = ((q0 + u) << kTidBits) | tid;
+                if constexpr (F32) {
+                    adjoint_amp(acc, pv[u][0].x, pv[u][0].y, lv[u][0].x, lv[u][0].y, td[u].x, gamma_over_pi);
+                    adjoint_amp(acc, pv[u][0].z, pv[u][0].w, lv[u][0].z, lv[u][0].w, td[u].y, gamma_over_pi);
+                } else {
+                    double d0, d1;
+                    table_to_lanes(td[u], lane, d0, d1);
+                    adjoint_amp(acc, pv[u][0].x, pv[u][0].y, lv[u][0].x, lv[u][0].y, d0, gamma_over_pi);
+                    adjoint_amp(acc, pv[u][1].x, pv[u][1].y, lv[u][1].x, lv[u][1].y, d1, gamma_over_pi);
+                }
+                if (t >= g.items) continue;
+#pragma unroll
+                for (int s = 0; s < S; s++) {
+                    const uint64_t amp = first_amp<R>(t, lane) + (uint64_t)kDiagWave * s;
+                    *reinterpret_cast<V *>(psi + 2 * amp) = pv[u][s];
+                    *reinterpret_cast<V *>(lam + 2 * amp) = lv[u][s];
+                }
+            }
+        }
+    }
+
+    __shared__ double part[kTPB / 64];
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if (lane == 0) part[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int w = 0; w < kTPB / 64; w++) s += part[w];
+        partial[blockIdx.x] = s;
+    }
+}
+
+// ---- dst (= | +=) w D src: the diagonal part of lambda = H psi -------------------------------------------------------------------------
+// w dv in fp64, rounded once to the state's precision, times the amplitude (accumulating: one fma per component)
+template <typename R, bool ACC>
+__device__ __forceinline__ void apply_amp(R &dr, R &di, R sr, R si, double dv, double weight) {
+    const R f = (R)(weight * dv);
+    if constexpr (ACC) dr = fma(f, sr, dr), di = fma(f, si, di);
+    else dr = f * sr, di = f * si;
+}
+
+// ACC == false: dst is not loaded.  Items per trip by diagonal.h's rule: the streams of k_diag_phase, or with dst those of k_diag_adjoint.
+template <typename R, bool ACC>
+__global__ __launch_bounds__(kTPB) void k_diag_apply(const R *__restrict__ src, R *__restrict__ dst, const double *__restrict__ d, DiagGeom g, double weight) {
+    using V = typename Vec16<R>::type;
+    using P = typename Amp<R>::type;
+    constexpr bool F32 = sizeof(R) == 4;
+    constexpr int U = ACC ? diag_adjoint_items_per_trip(F32) : diag_items_per_trip(F32), S = F32 ? 1 : 2;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+
+    if (g.items < (uint64_t)kDiagWave) { // the plain path: one thread per amplitude
+        if (blockIdx.x == 0 && tid < g.amps) {
+            const P sv = *reinterpret_cast<const P *>(src + 2 * tid);
+            P dv{};
+            if constexpr (ACC) dv = *reinterpret_cast<const P *>(dst + 2 * tid);
+            apply_amp<R, ACC>(dv.x, dv.y, sv.x, sv.y, d[tid], weight);
+            *reinterpret_cast<P *>(dst + 2 * tid) = dv;
+        }
+        return;
+    }
+
+    for (uint64_t q0 = (uint64_t)blockIdx.x * U; (q0 << kTidBits) < g.items; q0 += (uint64_t)gridDim.x * U) {
+        V sv[U][S], dv[U][S];
+        double2 td[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t t = ((q0 + u) << kTidBits) | tid;
+            td[u] = double2{};
+#pragma unroll
+            for (int s = 0; s < S; s++) sv[u][s] = V{}, dv[u][s] = V{};
+            if (t < g.items) { // uniform over a wave: items is a multiple of 64
+                td[u] = *reinterpret_cast<const double2 *>(d + 2 * t);
+#pragma unroll
+                for (int s = 0; s < S; s++) {
+                    const uint64_t amp = first_amp<R>(t, lane) + (uint64_t)kDiagWave * s;
+                    sv[u][s] = load_unit(src, amp);
+                    if constexpr (ACC) dv[u][s] = load_unit(const_cast<const R *>(dst), amp);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t t = ((q0 + u) << kTidBits) | tid;
+            if constexpr (F32) {
+                apply_amp<R, ACC>(dv[u][0].x, dv[u][0].y, sv[u][0].x, sv[u][0].y, td[u].x, weight);
+                apply_amp<R, ACC>(dv[u][0].z, dv[u][0].w, sv[u][0].z, sv[u][0].w, td[u].y, weight);
+            } else {
+                double d0, d1;
+                table_to_lanes(td[u], lane, d0, d1);
+                apply_amp<R, ACC>(dv[u][0].x, dv[u][0].y, sv[u][0].x, sv[u][0].y, d0, weight);
+                apply_amp<R, ACC>(dv[u][1].x, dv[u][1].y, sv[u][1].x, sv[u][1].y, d1, weight);
+            }
+            if (t >= g.items) continue;
+#pragma unroll
+            for (int s = 0; s < S; s++) *reinterpret_cast<V *>(dst + 2 * (first_amp<R>(t, lane) + (uint64_t)kDiagWave * s)) = dv[u][s];
+        }
+    }
+}
+
 // Table entries 2t and 2t + 1 of unit t = (q << kTidBits) | tid: popcount(i & z) = popcount((q << 9) & z), uniform over the
 // workgroup, + popcount((tid << 1) & z), the thread's own: one bit per term, formed once before the loop, + bit 0 of z for the odd
 // entry.  c s is a sign flip of c, exact, and the additions run in the terms' order, so the result is the sequential sum bit for bit.
@@ -318,7 +473,42 @@ hipError_t launch_expect_prec(hipStream_t stream, const void *amps, const DiagGe
     return launch_expect_final(stream, d_partial, (int)grid, 2, d_out);
 }
 
+// a reducing sweep that also writes: reducing_grid, so cfg.grid_cap does not apply and equal calls return equal bits
+template <typename R>
+hipError_t launch_adjoint_prec(hipStream_t stream, void *psi, void *lam, const DiagGeom &g, const double *table, double gamma_over_pi, double *d_partial,
+                               double *d_out) {
+    const unsigned grid = reducing_grid<k_diag_adjoint<R>>(g.items, (uint64_t)kTPB * diag_adjoint_items_per_trip(sizeof(R) == 4));
+    hipLaunchKernelGGL((k_diag_adjoint<R>), dim3(grid), dim3(kTPB), 0, stream, (R *)psi, (R *)lam, table, g, gamma_over_pi, d_partial);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_expect_final(stream, d_partial, (int)grid, 1, d_out);
+}
+
+template <typename R, bool ACC>
+hipError_t launch_apply_prec(const LaunchCfg &cfg, const void *src, void *dst, const DiagGeom &g, const double *table, double weight) {
+    constexpr bool F32 = sizeof(R) == 4;
+    constexpr int U = ACC ? diag_adjoint_items_per_trip(F32) : diag_items_per_trip(F32);
+    const unsigned grid = capped_grid<k_diag_apply<R, ACC>>(cfg.grid_cap, g.items, (uint64_t)kTPB * U, kDiagPhaseGrid);
+    hipLaunchKernelGGL((k_diag_apply<R, ACC>), dim3(grid), dim3(kTPB), 0, cfg.stream, (const R *)src, (R *)dst, table, g, weight);
+    return hipGetLastError();
+}
+
 } // namespace
+
+hipError_t launch_diag_adjoint(const LaunchCfg &cfg, void *psi, void *lam, bool f32, int n, const double *table, double gamma_over_pi, double *d_partial,
+                               double *d_out) {
+    if (n < 0 || n > 40 || !psi || !lam || psi == lam || !table || !d_partial || !d_out) return hipErrorInvalidValue;
+    const DiagGeom g = diag_geom(n);
+    return f32 ? launch_adjoint_prec<float>(cfg.stream, psi, lam, g, table, gamma_over_pi, d_partial, d_out)
+               : launch_adjoint_prec<double>(cfg.stream, psi, lam, g, table, gamma_over_pi, d_partial, d_out);
+}
+
+hipError_t launch_diag_apply(const LaunchCfg &cfg, const void *src, void *dst, bool f32, int n, const double *table, double weight, bool accumulate) {
+    if (n < 0 || n > 40 || !src || !dst || src == dst || !table) return hipErrorInvalidValue;
+    const DiagGeom g = diag_geom(n);
+    if (f32) return accumulate ? launch_apply_prec<float, true>(cfg, src, dst, g, table, weight) : launch_apply_prec<float, false>(cfg, src, dst, g, table, weight);
+    return accumulate ? launch_apply_prec<double, true>(cfg, src, dst, g, table, weight) : launch_apply_prec<double, false>(cfg, src, dst, g, table, weight);
+}
 
 hipError_t launch_diag_phase(const LaunchCfg &cfg, void *amps, bool f32, int n, const double *table, double gamma_over_pi) {
     if (n < 0 || n > 40 || !amps || !table) return hipErrorInvalidValue;

@@ -1,7 +1,8 @@
 // pauli.cpp — the host side of Pauli strings: expectation values <psi|P|psi> (expect.hip; DESIGN "Expectation values"),
 // rotations exp(-i theta/2 P) applied in the caller's order (evolve.hip; DESIGN "Pauli rotations"), the same under control qubits
 // (crot.hip; DESIGN "Controlled Pauli rotations") and adjoint-mode gradients of
-// <H> with respect to the angles (adjoint.hip, and cadjoint.hip through controlled rotations; DESIGN "Adjoint gradients").  pauli_sweep.h has what the sweeps share.  Every
+// <H> with respect to the angles (adjoint.hip, cadjoint.hip through controlled rotations and diagonal.hip through the phases exp(-i gamma D)
+// of a table; DESIGN "Adjoint gradients", §7k).  pauli_sweep.h has what the sweeps share.  Every
 // entry point opens with settle() and then only touches qsim_state's buffer, stream and d_expect; expectation values read the
 // buffer, rotations write it, a gradient call writes it and a second buffer of the same size (the spare one, or d_adjoint) and
 // leaves the state as it found it.
@@ -10,9 +11,11 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "diagonal.h" // a gradient's diagonal steps and the diagonal part of its observable
 #include "engine_state.h"
 #include "matrix.h" // kMatrixCoefDoubles: sweep_coef_staging
 #include "pauli_sweep.h"
+#include "subset_sweep.h" // trips_at_cap
 
 using namespace qsim;
 
@@ -29,13 +32,13 @@ static double rank_sign(uint64_t rank, uint64_t z, int m) { return (__builtin_po
 
 // qsim_internal.h says what is checked; the single-state entry points call it through check_terms, the cluster's through physical_terms
 int qsim::check_pauli_terms(int (*report)(int, const char *, ...), const char *who, int n, const uint64_t *x_masks, const uint64_t *z_masks,
-                            const void *third, const double *numbers, long num_terms, const char *number) {
+                            const void *third, const double *numbers, long num_terms, const char *number, long first) {
     if (num_terms < 0) return report(QSIM_ERR_ARG, "%s: negative term count", who);
     if (num_terms > 0 && (!x_masks || !z_masks || !third)) return report(QSIM_ERR_ARG, "%s: NULL argument", who);
     const uint64_t nmask = index_mask(n);
     for (long t = 0; t < num_terms; t++) {
-        if ((x_masks[t] | z_masks[t]) & ~nmask) return report(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, t, n);
-        if (numbers && !std::isfinite(numbers[t])) return report(QSIM_ERR_ARG, "%s: term %ld has a non-finite %s", who, t, number);
+        if ((x_masks[t] | z_masks[t]) & ~nmask) return report(QSIM_ERR_ARG, "%s: term %ld names a qubit outside the %d-qubit register", who, first + t, n);
+        if (numbers && !std::isfinite(numbers[t])) return report(QSIM_ERR_ARG, "%s: term %ld has a non-finite %s", who, first + t, number);
     }
     return QSIM_OK;
 }
@@ -249,10 +252,10 @@ extern "C" int qsim_pauli_rotation_plan(const uint64_t *x_masks, const uint64_t 
 // Term t acts as exp(-i theta/2 P_t) where every qubit of c_masks[t] is 1 and as the identity elsewhere.  route_rotations has the
 // rule: one control on a single X or Y is a 4x4 for the gate queue, every other controlled term goes to a sweep of the control
 // subspace, and a run shares sweeps only under one control mask.  A term without controls takes the uncontrolled path.
-static int check_controls(const char *who, int n, const uint64_t *C, const uint64_t *X, const uint64_t *Z, long num) {
-    for (long t = 0; C && t < num; t++) {
-        if (C[t] & ~index_mask(n)) return fail(QSIM_ERR_ARG, "%s: term %ld names a control qubit outside the %d-qubit register", who, t, n);
-        if (C[t] & (X[t] | Z[t])) return fail(QSIM_ERR_ARG, "%s: term %ld: a control qubit carries a Pauli factor", who, t);
+static int check_controls(const char *who, int n, const uint64_t *C, const uint64_t *X, const uint64_t *Z, long num, long first = 0) {
+    for (long t = 0; C && t < num; t++) { // first: as for check_pauli_terms
+        if (C[t] & ~index_mask(n)) return fail(QSIM_ERR_ARG, "%s: term %ld names a control qubit outside the %d-qubit register", who, first + t, n);
+        if (C[t] & (X[t] | Z[t])) return fail(QSIM_ERR_ARG, "%s: term %ld: a control qubit carries a Pauli factor", who, first + t);
     }
     return QSIM_OK;
 }
@@ -349,19 +352,30 @@ extern "C" int qsim_controlled_rotation_plan(const uint64_t *c_masks, const uint
 // energy, then the backward sweeps over psi and lambda, which also take the state back to where the call found it.
 static std::atomic<uint64_t> g_adjoint_sweeps{0};
 extern "C" uint64_t qsim_pauli_adjoint_sweeps_launched(void) { return g_adjoint_sweeps.load(); }
+static std::atomic<uint64_t> g_diag_adjoint_sweeps{0}; // the backward sweeps through diagonal phases, which count here only
+extern "C" uint64_t qsim_diagonal_adjoint_sweeps_launched(void) { return g_diag_adjoint_sweeps.load(); }
 
 // The backward sweeps in FORWARD order: maximal runs of consecutive equal x and equal control mask (C may be NULL: no controls
-// anywhere), cut into pieces of K.  Every term, single X and Y too.
-static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *C, const uint64_t *X, long num) {
+// anywhere), cut into pieces of K.  Every term, single X and Y too.  A step that is a diagonal phase (diag(t): DESIGN §7k) is a piece
+// of its own, and no run fuses across it; its x and control mask are not looked at.
+template <typename IsDiag>
+static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *C, const uint64_t *X, long num, IsDiag diag) {
     std::vector<std::pair<long, int>> out;
     auto c = [&](long t) { return C ? C[t] : 0; };
     for (long t = 0; t < num;) {
+        if (diag(t)) {
+            out.emplace_back(t++, 1);
+            continue;
+        }
         long e = t + 1;
-        while (e < num && X[e] == X[t] && c(e) == c(t)) e++;
+        while (e < num && !diag(e) && X[e] == X[t] && c(e) == c(t)) e++;
         for (; t < e; t += kPauliRotationsPerSweep) out.emplace_back(t, (int)std::min<long>(kPauliRotationsPerSweep, e - t));
         t = e;
     }
     return out;
+}
+static std::vector<std::pair<long, int>> adjoint_pieces(const uint64_t *C, const uint64_t *X, long num) {
+    return adjoint_pieces(C, X, num, [](long) { return false; });
 }
 
 extern "C" int qsim_pauli_gradient_plan(const uint64_t *rot_x, long num_rot, const uint64_t *ham_x, long num_ham, long *adjoint_sweeps, long *sum_sweeps) {
@@ -427,9 +441,20 @@ extern "C" int qsim_pauli_sum_into(qsim_state *s, const uint64_t *x_masks, const
     return pauli_sum_sweeps(s, x_masks, z_masks, coeffs, num_terms, dst_device);
 }
 
-// checked arguments; C may be NULL: no controls anywhere
+// The diagonal parts of a gradient call: step k of the circuit is exp(-i thetas[k] D) where step[k] is a table (NULL
+// array: no such step; the step's c, x and z are not looked at), and H has the part weight * D_obs (obs NULL: none).
+struct GradientDiagonals {
+    const qsim_diagonal *const *step = nullptr;
+    const qsim_diagonal *obs = nullptr;
+    double weight = 0.0;
+    const qsim_diagonal *at(long t) const { return step ? step[t] : nullptr; }
+};
+
+// checked arguments; C may be NULL: no controls anywhere.  The ONE owner of the adjoint algorithm: without diagonal parts its forward
+// loop is one apply_rotations call over the whole list and its pieces are the rotations' alone, which is what qsim_pauli_gradient and
+// qsim_controlled_pauli_gradient run.
 static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, const uint64_t *rot_z, const double *thetas, long num_rot, const uint64_t *ham_x,
-                    const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad) {
+                    const uint64_t *ham_z, const double *coeffs, long num_ham, double *energy, double *grad, const GradientDiagonals &dg = {}) {
     if (energy) *energy = 0.0;
     if (grad) std::fill(grad, grad + num_rot, 0.0);
     if (qsim_holds_nothing(s)) return QSIM_OK; // the zero vector: energy 0, gradient 0, no sweep
@@ -442,14 +467,33 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
         s->d_adjoint = lam;
     }
     QSIM_TRY(alloc_sweep_scratch(s));
+    const LaunchCfg cfg{s->stream, s->grid_cap};
 
-    QSIM_TRY(apply_rotations(s, C, rot_x, rot_z, thetas, num_rot));
+    // forward: the runs of rotations between the diagonal steps as apply_rotations takes them; a diagonal step is one phase sweep
+    for (long t = 0; t < num_rot;) {
+        long e = t;
+        while (e < num_rot && !dg.at(e)) e++;
+        if (e > t) QSIM_TRY(apply_rotations(s, C ? C + t : nullptr, rot_x + t, rot_z + t, thetas + t, e - t));
+        if (e < num_rot) {
+            QSIM_TRY(settle(s)); // single X and Y rotations wait in the gate queue
+            QSIM_TRY(launched("diagonal phase sweep", launch_diag_phase(cfg, s->amps, s->f32, s->n, diag_table(dg.at(e)), thetas[e] / M_PI)));
+            count_diagonal_sweep();
+            QSIM_TRY(mark_read(s, dg.at(e)));
+            e++;
+        }
+        t = e;
+    }
     QSIM_TRY(settle(s));
-    QSIM_TRY(pauli_sum_sweeps(s, ham_x, ham_z, coeffs, num_ham, lam));
+    // lambda = H psi: the Pauli part stores (zeros when there is none and no diagonal part either), the diagonal part comes on top
+    if (num_ham > 0 || !dg.obs) QSIM_TRY(pauli_sum_sweeps(s, ham_x, ham_z, coeffs, num_ham, lam));
+    if (dg.obs) {
+        QSIM_TRY(launched("diagonal sum sweep", launch_diag_apply(cfg, s->amps, lam, s->f32, s->n, diag_table(dg.obs), dg.weight, num_ham > 0)));
+        count_diagonal_sweep();
+        QSIM_TRY(mark_read(s, dg.obs));
+    }
 
     // row 0: the energy, Re <lambda|psi>, as one paired expectation sweep over the two buffers; then the pieces, last first
-    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(C, rot_x, num_rot);
-    const LaunchCfg cfg{s->stream, s->grid_cap};
+    const std::vector<std::pair<long, int>> pieces = adjoint_pieces(C, rot_x, num_rot, [&](long t) { return dg.at(t) != nullptr; });
     return sweep_result_rows(
         s, 1 + pieces.size(),
         [&](size_t r, double *d_row) -> int {
@@ -460,6 +504,12 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
                 return launched("expectation sweep", launch_expect(cfg, s->amps, lam, s->f32, s->n, sw, sweep_partials(s), d_row));
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
+            if (const qsim_diagonal *d = dg.at(piece.first)) { // the step back is the phase of -gamma
+                QSIM_TRY(launched("diagonal adjoint sweep",
+                                  launch_diag_adjoint(cfg, s->amps, lam, s->f32, s->n, diag_table(d), -thetas[piece.first] / M_PI, sweep_partials(s), d_row)));
+                g_diag_adjoint_sweeps++;
+                return mark_read(s, d);
+            }
             const uint64_t c = C ? C[piece.first] : 0;
             const RotSweep sw = rot_sweep(rot_x[piece.first], rot_z + piece.first, thetas + piece.first, piece.second, -1.0 /* U^+ */, 0, index_mask(s->n), s->n);
             if (c) QSIM_TRY(launched("controlled adjoint sweep", launch_pauli_cadjoint(cfg, s->amps, lam, s->f32, s->n, c, sw, sweep_partials(s), d_row)));
@@ -473,6 +523,10 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
                 return;
             }
             const std::pair<long, int> &piece = pieces[pieces.size() - r];
+            if (dg.at(piece.first)) { // dE/dgamma = 2 Re <lambda|(-i) D|psi> = 2 sum_i d_i Im(conj(lambda_i) psi_i)
+                if (grad) grad[piece.first] = 2.0 * row[0];
+                return;
+            }
             // Im (i^ny B): the kernel summed Im B (even ny) or Re B (odd); both members of a pair are in B, so the factor is 1, not 2
             for (int k = 0; grad && k < piece.second; k++)
                 grad[piece.first + k] = pauli_phase(__builtin_popcountll(rot_x[piece.first] & rot_z[piece.first + k])) * row[k];
@@ -496,4 +550,64 @@ extern "C" int qsim_controlled_pauli_gradient(qsim_state *s, const uint64_t *rot
     QSIM_TRY(check_terms(who, s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
     QSIM_TRY(check_controls(who, s->n, rot_c, rot_x, rot_z, num_rot));
     return gradient(s, rot_c, rot_x, rot_z, thetas, num_rot, ham_x, ham_z, coeffs, num_ham, energy, grad);
+}
+
+// ---- the same through diagonal phases, and with a diagonal part of H (diagonal.hip) --------------------------------------
+// What both the call and its plan check of a mixed step list: every rotation step by check_pauli_terms and check_controls, one step
+// at a time, so that what is refused has one definition (Z NULL: the plan, which knows no z, x stands in; angles NULL: the plan), and
+// on a diagonal step a finite gamma and no control mask.  diag(t): step t is diagonal.
+template <typename IsDiag>
+static int check_steps(const char *who, int n, IsDiag diag, const uint64_t *C, const uint64_t *X, const uint64_t *Z, const double *angles, bool plan, long num) {
+    if (num < 0) return fail(QSIM_ERR_ARG, "%s: negative step count", who);
+    for (long t = 0; t < num; t++) {
+        if (diag(t)) {
+            if (angles && !std::isfinite(angles[t])) return fail(QSIM_ERR_ARG, "%s: term %ld has a non-finite gamma", who, t);
+            if (C && C[t]) return fail(QSIM_ERR_ARG, "%s: term %ld is a diagonal phase and carries a control mask", who, t);
+            continue;
+        }
+        const uint64_t *x = X ? X + t : nullptr, *z = plan ? x : Z ? Z + t : nullptr;
+        QSIM_TRY(check_pauli_terms(fail, who, n, x, z, plan ? (const void *)x : (const void *)angles, plan ? nullptr : angles + t, 1, "angle", t));
+        QSIM_TRY(check_controls(who, n, C ? C + t : nullptr, x, z, 1, t));
+    }
+    return QSIM_OK;
+}
+
+extern "C" int qsim_diagonal_gradient(qsim_state *s, long num_steps, const qsim_diagonal *const *step_diag, const uint64_t *step_c, const uint64_t *step_x,
+                                      const uint64_t *step_z, const double *angles, const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs,
+                                      long num_ham, const qsim_diagonal *obs, double obs_weight, double *energy, double *grad) {
+    const char *who = "qsim_diagonal_gradient";
+    if (!s) return fail(QSIM_ERR_ARG, "NULL state");
+    if (num_steps > 0 && !angles) return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    GradientDiagonals dg;
+    dg.step = step_diag;
+    QSIM_TRY(check_steps(who, s->n, [&](long t) { return dg.at(t) != nullptr; }, step_c, step_x, step_z, angles, false, num_steps));
+    for (long t = 0; t < num_steps; t++)
+        if (dg.at(t)) QSIM_TRY(check_diag_pair(who, s, dg.at(t)));
+    QSIM_TRY(check_terms(who, s, ham_x, ham_z, coeffs, coeffs, num_ham, "coefficient"));
+    if (obs) {
+        QSIM_TRY(check_diag_pair(who, s, obs));
+        if (!std::isfinite(obs_weight)) return fail(QSIM_ERR_ARG, "%s: a non-finite weight of the diagonal part", who);
+        dg.obs = obs, dg.weight = obs_weight;
+    }
+    return gradient(s, step_c, step_x, step_z, angles, num_steps, ham_x, ham_z, coeffs, num_ham, energy, grad, dg);
+}
+
+extern "C" int qsim_diagonal_gradient_plan(const unsigned char *is_diag, const uint64_t *step_c, const uint64_t *step_x, long num_steps, const uint64_t *ham_x,
+                                           long num_ham, int has_obs, int num_q, int precision_bits, long *pauli_adjoint_sweeps, long *diag_adjoint_sweeps,
+                                           long *sum_sweeps, int *diag_adjoint_items_per_trip, long *diag_adjoint_trips_at_cap) {
+    const char *who = "qsim_diagonal_gradient_plan";
+    if (!pauli_adjoint_sweeps || !diag_adjoint_sweeps || !sum_sweeps || !diag_adjoint_items_per_trip || !diag_adjoint_trips_at_cap)
+        return fail(QSIM_ERR_ARG, "%s: NULL argument", who);
+    QSIM_TRY(check_register_args(who, num_q, precision_bits));
+    auto diag = [&](long t) { return is_diag && is_diag[t] != 0; };
+    QSIM_TRY(check_steps(who, num_q, diag, step_c, step_x, nullptr, nullptr, true, num_steps));
+    QSIM_TRY(check_pauli_terms(fail, who, num_q, ham_x, ham_x, ham_x, nullptr, num_ham));
+    *pauli_adjoint_sweeps = *diag_adjoint_sweeps = 0;
+    for (const std::pair<long, int> &piece : adjoint_pieces(step_c, step_x, num_steps, diag)) ++*(diag(piece.first) ? diag_adjoint_sweeps : pauli_adjoint_sweeps);
+    *sum_sweeps = (long)pauli_sweeps(ham_x, ~0ULL, num_ham).sweeps.size() + (has_obs ? 1 : 0);
+    const DiagGeom g = diag_geom(num_q);
+    *diag_adjoint_items_per_trip = qsim::diag_adjoint_items_per_trip(precision_bits == 32);
+    const uint64_t blocks = (g.items + kTPB - 1) / kTPB;
+    *diag_adjoint_trips_at_cap = g.items < (uint64_t)kDiagWave ? 1 : trips_at_cap(blocks, (uint64_t)*diag_adjoint_items_per_trip, kExpectGrid);
+    return QSIM_OK;
 }

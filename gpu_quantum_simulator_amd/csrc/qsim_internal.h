@@ -202,9 +202,10 @@ hipError_t launch_pack(const LaunchCfg &cfg, const void *in, void *out, void *co
 // The argument checks every Pauli entry point opens with, once its state or cluster is known to be there: no negative count, no
 // NULL array (`third`: the one that goes with the masks — results, angles or coefficients), no mask bit at or above n, and
 // `numbers` (angles or coefficients; `number` says which in the message) finite where there are any.  `report` is fail or cfail:
-// whose last error it becomes.  Hidden: the library's exports stay what they were.
+// whose last error it becomes.  `first`: the place of term 0 in the caller's own list, for the messages, when a part of a list is checked.
+// Hidden: the library's exports stay what they were.
 __attribute__((visibility("hidden"))) int check_pauli_terms(int (*report)(int, const char *, ...), const char *who, int n, const uint64_t *x_masks, const uint64_t *z_masks, const void *third,
-                      const double *numbers, long num_terms, const char *number = "angle");
+                      const double *numbers, long num_terms, const char *number = "angle", long first = 0);
 // <P_t> restricted to the shard; every term has the same x_rank.  Adds nothing up across shards.
 int expect_paulis_shard(qsim_state *s, const void *partner, uint64_t rank, const uint64_t *x_masks, const uint64_t *z_masks, long num_terms,
                         double *out);

@@ -375,6 +375,53 @@ class Diagonal:
             pass
 
 
+def _is_complex(number) -> bool:
+    return isinstance(number, complex) or (hasattr(number, "dtype") and number.dtype.kind == "c")
+
+
+def _split_diagonal_steps(rotations):
+    """The entries of energy_and_gradient's `rotations`, (gamma, Diagonal) steps among them, as (entries, tables): an entry that is
+    a diagonal phase has its table in `tables` (None elsewhere) and (gamma, "") — the identity string, which the library does not
+    look at — in its place.  ValueError for controls on a diagonal entry, a complex gamma, a closed table.  Pure Python."""
+    entries, tables = [], []
+    for entry in rotations:
+        entry = tuple(entry)
+        if len(entry) >= 2 and isinstance(entry[1], Diagonal):
+            if len(entry) > 3 or (len(entry) == 3 and tuple(entry[2])):
+                raise ValueError(f"a diagonal step is (gamma, diag): it takes no controls, got {entry[2:]!r}")
+            if _is_complex(entry[0]):
+                raise ValueError(f"gamma {entry[0]!r} of a diagonal step is complex")
+            if not entry[1]._h:
+                raise ValueError("a diagonal step names a closed Diagonal")
+            tables.append(entry[1])
+            entries.append((entry[0], ""))
+        else:
+            tables.append(None)
+            entries.append(entry)
+    return entries, tables
+
+
+def _split_diagonal_observable(terms):
+    """energy_and_gradient's `terms` as (Pauli terms, table or None, weight): a Diagonal alone is the whole observable with weight 1,
+    and a list may hold one (w, Diagonal) among its (coefficient, string) pairs.  ValueError for two diagonal parts, a complex
+    weight, a closed table.  Pure Python."""
+    if isinstance(terms, Diagonal):
+        terms = [(1.0, terms)]
+    paulis, table, weight = [], None, 0.0
+    for term in terms:
+        if len(term) == 2 and isinstance(term[1], Diagonal):
+            if table is not None:
+                raise ValueError("the observable has two diagonal parts: add the tables up into one Diagonal")
+            if _is_complex(term[0]):
+                raise ValueError(f"weight {term[0]!r} of the diagonal part is complex: a Hamiltonian's coefficients are real")
+            if not term[1]._h:
+                raise ValueError("the observable names a closed Diagonal")
+            table, weight = term[1], float(term[0])
+        else:
+            paulis.append(term)
+    return paulis, table, weight
+
+
 class Simulator(_PauliStrings):
     """One state vector resident on one GPU."""
     _expect_fn, _rotate_fn, _check = "qsim_expect_paulis", "qsim_apply_pauli_rotations", staticmethod(check)
@@ -421,17 +468,30 @@ class Simulator(_PauliStrings):
         state is left as the call found it, to rounding.
         Entries may be (theta, string, controls), mixed with plain ones, as apply_pauli_rotations takes them, with the same
         ValueErrors (qsim_controlled_pauli_gradient): the derivative with respect to the angle of a controlled rotation, which the
-        two-term shift rule gets wrong; its backward sweep touches 2^-c of the state and of lambda for c controls."""
+        two-term shift rule gets wrong; its backward sweep touches 2^-c of the state and of lambda for c controls.
+        An entry may also be (gamma, diag) with a Diagonal: the step exp(-i gamma D) of apply_diagonal_phase, one sweep forwards and
+        one backwards whatever the number of terms D has, and grad[k] = dE/dgamma.  `terms` may be a Diagonal (H = D) or hold one
+        (w, diag) among its pairs (H = sum_t c_t P_t + w D): a QAOA loop is energy_and_gradient(layers, cost)
+        (qsim_diagonal_gradient).  ValueError, before any launch, for controls on a diagonal entry, two diagonal parts in `terms`, a
+        complex weight or gamma."""
+        rotations, tables = _split_diagonal_steps(rotations)
+        terms, obs, weight = _split_diagonal_observable(terms)
         pairs, controls = _split_controls(rotations)
         rxs, rzs, thetas, rxp, rzp, tp = _rotation_arrays(pairs, self.num_qubits)
         hxs, hzs, coeffs, hxp, hzp, cp = _hamiltonian_arrays(terms, self.num_qubits)
         energy, grad = c_double(0.0), np.zeros(rxs.size, dtype=np.float64)
+        cs = csp = None  # the control masks, where any entry has controls
         if any(controls):
             from ctypes import c_uint64
             from .pauli import control_mask
             cs = np.array([control_mask(c, self.num_qubits, text) for (_, text), c in zip(pairs, controls)], dtype=np.uint64)
-            check(_lib.load().qsim_controlled_pauli_gradient(self._h, cs.ctypes.data_as(ctypes.POINTER(c_uint64)), rxp, rzp, tp, rxs.size, hxp, hzp, cp,
-                                                             hxs.size, byref(energy), _dp(grad)))
+            csp = cs.ctypes.data_as(ctypes.POINTER(c_uint64))
+        if obs is not None or any(t is not None for t in tables):
+            steps = (c_void_p * max(len(tables), 1))(*[t._h.value if t is not None else None for t in tables])
+            check(_lib.load().qsim_diagonal_gradient(self._h, rxs.size, steps, csp, rxp, rzp, tp, hxp, hzp, cp, hxs.size, obs._h if obs is not None else None,
+                                                     weight, byref(energy), _dp(grad)))
+        elif cs is not None:
+            check(_lib.load().qsim_controlled_pauli_gradient(self._h, csp, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
         else:
             check(_lib.load().qsim_pauli_gradient(self._h, rxp, rzp, tp, rxs.size, hxp, hzp, cp, hxs.size, byref(energy), _dp(grad)))
         return float(energy.value), grad
@@ -564,6 +624,12 @@ class Simulator(_PauliStrings):
         the queued gates and not waited for.  For diag = Diagonal.from_terms(n, [(c_k, P_k)]) it equals
         apply_pauli_rotations([(2 gamma c_k, P_k)]) — a QAOA phase separator in one sweep whatever the number of terms."""
         check(_lib.load().qsim_apply_diagonal_phase(self._h, diag._h, float(gamma)))
+
+    def diagonal_into(self, diag: Diagonal, dst_ptr: int, weight: float = 1.0, accumulate: bool = False) -> None:
+        """dst = weight D |state>, or dst += with accumulate=True, for the table of `diag`, written to the device buffer at `dst_ptr`
+        (2^n amplitudes of this state's precision, not this state's own buffer): one out-of-place sweep
+        (qsim_diagonal_apply_into), queued on the state's stream, not waited for.  When storing, dst's old contents are not read."""
+        check(_lib.load().qsim_diagonal_apply_into(self._h, diag._h, float(weight), c_void_p(dst_ptr), 1 if accumulate else 0))
 
     def expectation_diagonal(self, diag: Diagonal, moments: bool = False):
         """<D> = sum_i d_i |a_i|^2 for the table of `diag`, one read-only sweep (qsim_expect_diagonal); moments=True returns

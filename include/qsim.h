@@ -454,6 +454,44 @@ uint64_t qsim_diagonal_sweeps_launched(void); /* process-wide counter of the two
  * result pointer. */
 int qsim_diagonal_plan(int num_q, int precision_bits, uint64_t *items, int *items_per_trip_phase, int *items_per_trip_expect,
                        long *trips_at_cap_phase, long *trips_at_cap_expect);
+/* ---- adjoint-mode gradients through diagonal phases, and <D> as (part of) the observable (new) ----
+ * qsim_controlled_pauli_gradient for a circuit whose steps are Pauli rotations OR diagonal phases: step k with step_diag[k] != NULL is
+ * exp(-i angles[k] D_k) for that table (qsim_apply_diagonal_phase), and grad[k] = dE/dgamma_k = 2 sum_i d_i Im(conj(lambda_i) psi_i);
+ * every other step is the (controlled) rotation of step_c, step_x, step_z and angles[k] = theta_k.  step_c, step_x and step_z of a
+ * diagonal step are not looked at, except that a non-zero control mask there is refused.  step_diag NULL: no diagonal step.
+ * H = sum_t coeffs[t] Q_t + obs_weight D_obs; obs NULL: no diagonal part (obs_weight is not looked at); num_ham may be 0.
+ * One forward pass (a diagonal step is one sweep, rotations between two diagonal steps fuse as in qsim_apply_pauli_rotations), lambda =
+ * H psi (the Pauli sweeps, then one sweep for the diagonal part), the energy, and the backward pass: one sweep per diagonal step, which
+ * reads psi, lambda and the table, and the sweeps of qsim_pauli_gradient for each run of rotations between them.  The state is left as
+ * the call found it, to rounding; a list of diagonal steps only leaves the bits that qsim_apply_diagonal_phase with gamma_1 .. gamma_K
+ * and then -gamma_K .. -gamma_1 leaves.  Equal calls return equal bits.  A shard that holds nothing: energy 0, gradient zeros, no sweep.
+ * A call without diagonal steps and without obs launches exactly what qsim_controlled_pauli_gradient launches.
+ * QSIM_ERR_ARG, the state untouched: what qsim_controlled_pauli_gradient refuses; a table of another qubit count or on another device;
+ * a non-finite angle or obs_weight; a control mask on a diagonal step; NULL arguments or negative counts.
+ * Backward diagonal sweeps count in qsim_diagonal_adjoint_sweeps_launched only; forward phases and the D_obs sweep in
+ * qsim_diagonal_sweeps_launched; the rotations' backward sweeps in qsim_pauli_adjoint_sweeps_launched. */
+int qsim_diagonal_gradient(qsim_state *s, long num_steps,
+        const qsim_diagonal *const *step_diag, /* [num_steps], NULL entry = Pauli rotation; NULL array = none */
+        const uint64_t *step_c,                /* NULL = no controls anywhere */
+        const uint64_t *step_x, const uint64_t *step_z, const double *angles, /* theta_k or gamma_k */
+        const uint64_t *ham_x, const uint64_t *ham_z, const double *coeffs, long num_ham,
+        const qsim_diagonal *obs, double obs_weight, /* obs NULL = no diagonal part */
+        double *energy, double *grad /* [num_steps] */);
+/* Host only, no device: the sweeps qsim_diagonal_gradient makes after its forward pass.  is_diag[k] != 0: step k is a diagonal phase
+ * (NULL: none is).  *pauli_adjoint_sweeps: the rotations' backward sweeps — a run never fuses across a diagonal step;
+ * *diag_adjoint_sweeps: one per diagonal step; *sum_sweeps: the Pauli sweeps of lambda = H psi plus one for the diagonal part (has_obs);
+ * *diag_adjoint_items_per_trip and *diag_adjoint_trips_at_cap: as qsim_diagonal_plan reports them, for the backward diagonal sweep (its
+ * grid holds 1024 workgroups at most).  QSIM_ERR_ARG as for qsim_controlled_gradient_plan, and for a control mask on a diagonal step. */
+int qsim_diagonal_gradient_plan(const unsigned char *is_diag, const uint64_t *step_c, const uint64_t *step_x, long num_steps,
+        const uint64_t *ham_x, long num_ham, int has_obs, int num_q, int precision_bits,
+        long *pauli_adjoint_sweeps, long *diag_adjoint_sweeps, long *sum_sweeps,
+        int *diag_adjoint_items_per_trip, long *diag_adjoint_trips_at_cap);
+uint64_t qsim_diagonal_adjoint_sweeps_launched(void); /* process-wide counter of the backward diagonal sweeps */
+/* dst (device, 2^n amplitudes of the state's precision, not the state's own buffers) = weight D |state>, or += with accumulate != 0:
+ * one out-of-place sweep on qsim_stream(), not waited for; weight d_i is rounded once to the state's precision.  When storing, dst's
+ * old contents are not read.  Counts in qsim_diagonal_sweeps_launched.  QSIM_ERR_ARG as for qsim_apply_diagonal_phase (weight in
+ * gamma's place), and for dst_device NULL or equal to the state's buffer or its spare buffer. */
+int qsim_diagonal_apply_into(qsim_state *s, const qsim_diagonal *d, double weight, void *dst_device, int accumulate);
 void *qsim_device_ptr(qsim_state *s);        /* amplitude array in HBM: launches pending gates and writes a lazily held
                                               * |0...0> first (work is queued on qsim_stream(), not waited for); NULL on error */
 void *qsim_stream(qsim_state *s);            /* the hipStream_t every launch goes to */
