@@ -20,6 +20,7 @@ OPT_PINGPONG = 14
 OPT_SPARSE_START = 15
 OPT_DEBUG_PLAN_KEY = 16
 OPT_DEFER_FLIPS = 17
+OPT_AFFINE_SUPPORT = 18
 K_NAMES = ("init", "gate1", "gate1_lo", "phase", "cx", "gate2", "tile", "pack")
 K_COUNT = len(K_NAMES)
 
@@ -38,6 +39,13 @@ class QsimStats(ctypes.Structure):
 class QsimPassInfo(ctypes.Structure):
     _fields_ = [("kernel_class", ctypes.c_int32), ("blocks", ctypes.c_int32), ("tile_mask", c_uint64), ("visited", c_double),
                 ("bytes", c_double), ("cost_bytes", c_double)]
+
+
+class QsimPassRegion(ctypes.Structure):
+    _fields_ = [("kernel_class", ctypes.c_int32), ("on", ctypes.c_int32), ("refined", ctypes.c_int32), ("n_gen", ctypes.c_int32),
+                ("n_checks", ctypes.c_int32), ("reserved", ctypes.c_int32), ("tile_mask", c_uint64), ("support_before", c_uint64),
+                ("origin", c_uint64), ("check_parity", c_uint64), ("gen", c_uint64 * 64), ("check_mask", c_uint64 * 64),
+                ("visited", c_double), ("read_share", c_double)]
 
 
 class QsimTuneReport(ctypes.Structure):
@@ -236,7 +244,9 @@ SIGNATURES = {
     "qsim_plan_circuit": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(QsimStats)]),
     "qsim_plan_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimStats)]),
     "qsim_plan_passes": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimPassInfo), c_int, POINTER(c_int)]),
+    "qsim_plan_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_int, POINTER(QsimPassRegion), c_int, POINTER(c_int)]),
     "qsim_schedule_circuit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p]),
+    "qsim_schedule_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, SCHED_CB, c_void_p]),
     "qsim_schedule_circuit_deferred": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p, POINTER(c_uint64)]),
     "qsim_tile_records": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_uint64, TILE_RECORD_CB, c_void_p]),
 }

@@ -213,6 +213,9 @@ extern "C" int qsim_set_option(qsim_state *s, int option, long value) {
     case QSIM_OPT_SPARSE_START:
         s->sparse_start = value != 0;
         break;
+    case QSIM_OPT_AFFINE_SUPPORT:
+        s->affine_support = value != 0;
+        break;
     case QSIM_OPT_DEBUG_PLAN_KEY:
         s->debug_plan_key = value;
         break;
@@ -252,6 +255,7 @@ extern "C" long qsim_get_option(const qsim_state *s, int option) {
     case QSIM_OPT_PLAN_CACHE: return s->plan_cache;
     case QSIM_OPT_PINGPONG: return s->pingpong;
     case QSIM_OPT_SPARSE_START: return s->sparse_start;
+    case QSIM_OPT_AFFINE_SUPPORT: return s->affine_support;
     case QSIM_OPT_DEBUG_PLAN_KEY: return s->debug_plan_key;
     case QSIM_OPT_DEFER_FLIPS: return s->defer_flips;
     default: return -1;
@@ -261,6 +265,7 @@ extern "C" long qsim_get_option(const qsim_state *s, int option) {
 int qsim::materialize_zero_ket(qsim_state *s) {
     QSIM_TRY(await_buffer(s));
     if (!s->zero_ket_pending && !s->partial) return QSIM_OK;
+    if (s->region_pending) return fail(QSIM_ERR_ARG, "internal: the zeros of a state that was written inside an affine region only");
     HIP_TRY(hipSetDevice(s->device)); // a cluster drives several devices from one thread
     LaunchCfg cfg{s->stream, s->grid_cap};
     const double state_bytes = (double)s->amp_bytes() * (double)(1ULL << s->n);
@@ -288,6 +293,7 @@ extern "C" int qsim_reset_shard(qsim_state *s, int holds_index0) {
     s->zero_ket_pending = true;
     s->partial = false;
     s->support = 0;
+    s->region_pending = false;
     return QSIM_OK;
 }
 
@@ -302,6 +308,7 @@ extern "C" int qsim_set_support(qsim_state *s, uint64_t support) {
     s->zero_ket_pending = false;
     s->support = support & nmask;
     s->partial = s->support != nmask;
+    s->region_pending = false; // the caller describes the contents anew (a flush that failed behind a walking pass leaves it set)
     if (!s->sparse_start && s->partial) return materialize_zero_ket(s); // the option is off: keep the state dense
     return QSIM_OK;
 }
@@ -428,13 +435,13 @@ void *qsim::spare_buffer(qsim_state *s) {
 // re-laid-out, to job->out (or the buffer the state is not in) and records where.
 // flip (with oop, without job): deferred X gates — the amplitude of index i is stored at i ^ flip of the spare buffer.
 static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileOp *d, int need, bool from_zero_ket, bool oop = false, uint64_t zero_mask = 0,
-                                PackJob *job = nullptr, uint64_t flip = 0) {
+                                PackJob *job = nullptr, uint64_t flip = 0, int affine = 0, int walk_gens = 0) {
     LaunchCfg cfg{s->stream, s->grid_cap};
     const int threads = s->tile_threads; // 0: default for the tile size
     if (job) {
         void *dst = job->out ? job->out : (s->spare && s->spare != s->amps ? s->spare : nullptr);
         if (!dst || dst == s->amps) return fail(QSIM_ERR_ARG, "internal: no buffer for the re-layout");
-        const hipError_t e = launch_tile(cfg, s->amps, dst, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, &job->map);
+        const hipError_t e = launch_tile(cfg, s->amps, dst, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, &job->map, affine, walk_gens);
         if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
         job->packed_at = dst;
         return QSIM_OK;
@@ -442,7 +449,7 @@ static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileO
     PackMap flips = identity_pack_map();
     flips.flip = flip;
     if (flip && (!oop || !s->spare || s->spare == s->amps)) return fail(QSIM_ERR_ARG, "internal: deferred flips need an out-of-place pass");
-    const hipError_t e = launch_tile(cfg, s->amps, oop ? s->spare : s->amps, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, flip ? &flips : nullptr);
+    const hipError_t e = launch_tile(cfg, s->amps, oop ? s->spare : s->amps, s->f32, geom, d, need, threads, from_zero_ket, s->zero_ket_amp, zero_mask, flip ? &flips : nullptr, affine, walk_gens);
     if (e != hipSuccess) return fail(QSIM_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     if (oop) std::swap(s->amps, s->spare);
     return QSIM_OK;
@@ -450,22 +457,37 @@ static int launch_tile_prepared(qsim_state *s, const TileGeom &geom, const TileO
 
 // Prepares the blocks of a tile pass for the given bit order in the pinned ring, uploads and launches them; `capture`
 // (optional) receives a copy of the prepared TileOps for the plan cache.
+// The TileAffine record of a pass's region, in the place of a TileOp (zeroed beyond it).
+static void encode_region(const PassRegion &r, TileOp &slot) {
+    memset(&slot, 0, sizeof slot);
+    TileAffine a{};
+    a.origin = r.origin;
+    a.n_gen = (uint32_t)std::min(r.gen.size(), (size_t)kAffineMaxGens);
+    for (uint32_t j = 0; j < a.n_gen; j++) a.gen[j] = r.gen[j];
+    a.n_chk = (uint32_t)std::min(r.checks.size(), (size_t)kAffineMaxChecks);
+    for (uint32_t j = 0; j < a.n_chk; j++) { a.chk[j] = r.checks[j].mask; a.chk_par |= (uint32_t)(r.checks[j].parity & 1) << j; }
+    memcpy(&slot, &a, sizeof a);
+}
+// TileOps a pass takes in the op buffer: its blocks, and behind them the record of its region
+static size_t pass_op_slots(const Pass &p) { return p.blocks.size() + (p.region.on ? 1 : 0); }
+
 int qsim::launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, bool from_zero_ket, std::vector<TileOp> *capture, bool oop, uint64_t zero_mask,
-                           PackJob *job, uint64_t flip) {
-    const size_t need = p.blocks.size();
+                           PackJob *job, uint64_t flip, int affine, int walk_gens) {
+    const size_t blocks = p.blocks.size(), need = pass_op_slots(p);
     if (need > s->ops_cap) return fail(QSIM_ERR_ARG, "tile pass with %zu ops exceeds the op buffer", need);
     if (s->ops_used + need > s->ops_cap) { // ring is full: wait until earlier passes have read their ops
         HIP_TRY(hipStreamSynchronize(s->stream));
         s->ops_used = 0;
     }
     TileOp *h = s->h_ops + s->ops_used;
-    for (size_t k = 0; k < need; k++)
+    for (size_t k = 0; k < blocks; k++)
         if (!to_tile_op(geom, p.blocks[k], h[k], s->f32)) return fail(QSIM_ERR_ARG, "internal: block does not fit its tile pass");
+    if (need > blocks) encode_region(p.region, h[blocks]);
     if (capture) capture->insert(capture->end(), h, h + need);
     TileOp *d = s->d_ops + s->ops_used;
     HIP_TRY(hipMemcpyAsync(d, h, need * sizeof(TileOp), hipMemcpyHostToDevice, s->stream));
     s->ops_used += need;
-    return launch_tile_prepared(s, geom, d, (int)need, from_zero_ket, oop, zero_mask, job, flip);
+    return launch_tile_prepared(s, geom, d, (int)blocks, from_zero_ket, oop, zero_mask, job, flip, affine, walk_gens);
 }
 
 // cached_geom / cached_ops: replay of a cached plan (the tile pass's order and device-resident TileOps);
@@ -478,8 +500,9 @@ static void push_head(std::vector<uint8_t> &out, const TileOp &t) {
 // cached_heads: those bytes of the cached records, kept on the host with the plan (kHeadBytes per op).
 static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom = nullptr, const TileOp *cached_ops = nullptr,
                        std::vector<TileOp> *capture = nullptr, TileGeom *geom_out = nullptr, bool oop = false, PackJob *job = nullptr,
-                       const uint8_t *cached_heads = nullptr, uint64_t flip = 0) {
+                       const uint8_t *cached_heads = nullptr, uint64_t flip = 0, bool closing = true) {
     const bool from_zero_ket = s->zero_ket_pending && p.kclass == QSIM_K_TILE;
+    if (s->region_pending && p.kclass != QSIM_K_TILE) return fail(QSIM_ERR_ARG, "internal: a kernel other than a tile pass behind a pass that was not closing");
     if ((s->zero_ket_pending || s->partial) && p.kclass != QSIM_K_TILE) { // only tile passes work on a partially written state
         QSIM_TRY(materialize_zero_ket(s));
     }
@@ -535,6 +558,23 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
         visited = 1.0 / (double)(1ULL << __builtin_popcountll(zero_mask & ~tmask));
         // of a visited tile only the slots inside the support are read (k_tile SPARSE); a generating pass reads nothing
         read_share = from_zero_ket ? 0.0 : visited / (double)(1ULL << __builtin_popcountll(zero_mask & tmask));
+        // QSIM_OPT_AFFINE_SUPPORT: the pass goes by its region where that says what this launch finds — a partially written state of
+        // exactly the support the scheduler assumed.  It tests its input by the previous pass's region if that pass wrote nothing
+        // else, and walks its own tiles unless it is closing (the next thing to run is no tile pass of this flush that tests them).
+        const PassRegion &reg = p.region;
+        const bool by_region = s->affine_support && reg.on && zero_mask != 0 && !from_zero_ket && (reg.support_before & nmask) == (s->support & nmask);
+        if (s->region_pending && !(by_region && !reg.checks.empty()))
+            return fail(QSIM_ERR_ARG, "internal: a tile pass without the checks of the region the pass before it wrote");
+        int affine = 0, walk_gens = 0;
+        if (by_region) {
+            if (s->region_pending) affine |= kAffineChecks;
+            if (!closing && reg.refined && reg.gen.size() <= (size_t)kAffineMaxGens) {
+                affine |= kAffineWalk;
+                walk_gens = (int)reg.gen.size();
+                visited = reg.visited;
+                read_share = reg.read_share;
+            }
+        }
         LaunchScope scope(s, p.kclass, (int)p.blocks.size(), hm, oc, visited, read_share);
         if (scope.on && s->profile >= 2) // what the blocks look like, for the pass-time model's data (tools/pass_model_data.py); host work per launch: only on request
             for (size_t k = (size_t)geom.n_scale; k < p.blocks.size(); k++) {
@@ -550,12 +590,13 @@ static int launch_pass(qsim_state *s, const Pass &p, const TileGeom *cached_geom
                 }
                 scope.pe.forms.push_back((uint8_t)((T == 4 ? 2 : T == 2 ? 1 : 0) | (b.nq << 2) | (2 * ident >= b.dim() ? 32 : 0) | (b.ns << 6)));
             }
-        const int rc = cached_ops ? launch_tile_prepared(s, geom, cached_ops, (int)p.blocks.size(), from_zero_ket, oop, zero_mask, job, flip)
-                                  : launch_tile_pass(s, p, geom, from_zero_ket, capture, oop, zero_mask, job, flip);
+        const int rc = cached_ops ? launch_tile_prepared(s, geom, cached_ops, (int)p.blocks.size(), from_zero_ket, oop, zero_mask, job, flip, affine, walk_gens)
+                                  : launch_tile_pass(s, p, geom, from_zero_ket, capture, oop, zero_mask, job, flip, affine, walk_gens);
         if (rc) return rc;
+        s->region_pending = (affine & kAffineWalk) != 0;
         if (scope.on && s->profile >= 2) { // which kernel form each block ran through: out of the records the kernel was given
             const size_t need = p.blocks.size();
-            const TileOp *h = s->h_ops + (s->ops_used - need); // a fresh pass: launch_tile_pass has just encoded them there
+            const TileOp *h = s->h_ops + (s->ops_used - pass_op_slots(p)); // a fresh pass: launch_tile_pass has just encoded them there
             for (size_t k = (size_t)geom.n_scale; k < need; k++) {
                 if (!cached_ops) push_head(scope.pe.heads, h[k]);
                 else if (cached_heads) scope.pe.heads.insert(scope.pe.heads.end(), cached_heads + kHeadBytes * k, cached_heads + kHeadBytes * (k + 1));
@@ -620,7 +661,7 @@ static bool same_gates(const QueuedGate *a, const QueuedGate *b, size_t count) {
     return true;
 }
 static bool plan_matches(const PlanIdentity &have, const PlanIdentity &want, const QueuedGate *gates, size_t count) {
-    return memcmp(have.opts, want.opts, sizeof have.opts) == 0 && have.support == want.support && have.env == want.env && have.defer == want.defer &&
+    return memcmp(have.opts, want.opts, sizeof have.opts) == 0 && have.support == want.support && have.env == want.env && have.defer == want.defer && have.affine == want.affine &&
            have.gates.size() == count && same_gates(have.gates.data(), gates, count);
 }
 
@@ -668,7 +709,7 @@ namespace {
 struct PlanRecorder {
     CachedPlan plan;
     std::vector<TileOp> host_ops;
-    int launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip);
+    int launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip, bool closing);
 };
 
 // Keeps the recorded plan: its TileOps move to a device buffer of their own (one copy, ordered behind the launches).  A stale plan
@@ -708,10 +749,10 @@ static int keep_plan(qsim_state *s, PlanRecorder &rec, uint64_t key, uint64_t ep
     return QSIM_OK;
 }
 
-int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip) {
+int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64_t flip, bool closing) {
     TileGeom g = p.geom;
     plan.op_first.push_back(host_ops.size());
-    const int rc = launch_pass(s, p, nullptr, nullptr, &host_ops, &g, oop, job, nullptr, flip);
+    const int rc = launch_pass(s, p, nullptr, nullptr, &host_ops, &g, oop, job, nullptr, flip, closing);
     plan.geoms.push_back(g);
     plan.passes.push_back(std::move(p));
     return rc;
@@ -738,6 +779,11 @@ int PlanRecorder::launch(qsim_state *s, Pass &&p, bool oop, PackJob *job, uint64
 //      once every pass has been pushed, whether that works out: the queue ends in a tile pass that has the PACK variant, with a
 //      tile pass before it, a second buffer, and every flipped bit inside the support the state then has (a flipped bit outside it
 //      would be a qubit in |1> that no zero_mask can express).  If not, the caller drops the flip and pushes the X gates as passes.
+//   7. Affine support (QSIM_OPT_AFFINE_SUPPORT; scheduler.h PassRegion): a tile pass may write only the tiles of its region if the
+//      next thing to run is a tile pass that tests its input by that region: one of the same schedule, launched plainly.  Every
+//      other tile pass is CLOSING and writes the coordinate cube, so that whatever follows (the end of the queue, any other kernel,
+//      the re-layout or the flipping pass, the X passes of a dropped flip) finds a state that `support` describes.  Which it is
+//      shows only when the next pass is seen: a tile pass that carries a region waits for that even where rule 2 would launch it.
 class PassRouter {
   public:
     // rec: the fresh path's recorder for the plan cache, through which the passes moved in are launched (NULL: nothing is recorded)
@@ -777,13 +823,16 @@ class PassRouter {
     uint64_t sup_before_last_ = 0; // ... and once every pass but the most recent one has
     std::vector<Item> held_, prev_; // the most recent group; with a PackJob also the one before it
 
-    void launch(Item &it, bool oop, PackJob *pj, uint64_t flip = 0) {
+    void launch(Item &it, bool oop, PackJob *pj, uint64_t flip = 0, bool closing = true) {
         if (rc_ != QSIM_OK) return;
-        if (it.own && rec_) rc_ = rec_->launch(s_, std::move(*it.own), oop, pj, flip);
-        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj, it.heads, flip);
+        if (it.own && rec_) rc_ = rec_->launch(s_, std::move(*it.own), oop, pj, flip, closing);
+        else rc_ = launch_pass(s_, *it.p, it.geom, it.d_ops, nullptr, nullptr, oop, pj, it.heads, flip, closing);
     }
-    void run_group(std::vector<Item> &grp, bool oop, PackJob *pj = nullptr, uint64_t flip = 0) { // oop / pj / flip: of the tile pass at its head
-        for (size_t i = 0; i < grp.size(); i++) launch(grp[i], i == 0 && oop, i == 0 ? pj : nullptr, i == 0 ? flip : 0);
+    // oop / pj / flip: of the tile pass at the group's head; next: the tile pass that runs right behind the group, launched plainly
+    // (NULL: none, or the re-layout / flipping pass) — rule 7
+    void run_group(std::vector<Item> &grp, bool oop, PackJob *pj = nullptr, uint64_t flip = 0, const Item *next = nullptr) {
+        const bool closing = grp.size() != 1 || !next || next->p->kclass != QSIM_K_TILE || !next->p->region.on;
+        for (size_t i = 0; i < grp.size(); i++) launch(grp[i], i == 0 && oop, i == 0 ? pj : nullptr, i == 0 ? flip : 0, i == 0 ? closing : true);
         grp.clear();
     }
     void route(Item &&it) {
@@ -792,16 +841,23 @@ class PassRouter {
         sup_before_last_ = sup_;
         sup_ = tile ? sup_ | tile_mask(it.tile_geom()) : ~0ULL; // anything but a tile pass has the zeros written out first
         if (tile && pp_ < 0) pp_ = spare_buffer(s_) != nullptr ? 1 : 0;
-        if (pp_ <= 0 && !two_) { launch(it, false, nullptr); return; } // rule 2
-        if (tile) release(false);
+        const bool waits = pp_ > 0 || two_ || (tile && it.p->region.on); // rules 3, 4 and 6; rule 7
+        if (!waits && held_.empty()) { launch(it, false, nullptr); return; } // rule 2
+        if (tile) release(false, &it);
+        if (!waits && held_.empty()) { launch(it, false, nullptr); return; } // rule 2 again: the pass that waited under rule 7 has gone
         if (tile || !held_.empty()) held_.push_back(std::move(it));
         else launch(it, false, nullptr); // no tile pass seen yet
     }
     // last = false: a newer tile pass has arrived, so the oldest group held is not the last (rule 3); true: the end of the queue
-    void release(bool last) {
+    // arriving: that newer tile pass
+    void release(bool last, const Item *arriving = nullptr) {
         if (!last) {
-            run_group(two_ ? prev_ : held_, pp_ > 0);
-            if (two_) prev_.swap(held_);
+            if (two_) { // (the group in between is not the last either: it will be launched plainly)
+                run_group(prev_, pp_ > 0, nullptr, 0, held_.empty() ? nullptr : &held_[0]);
+                prev_.swap(held_);
+            } else {
+                run_group(held_, pp_ > 0, nullptr, 0, arriving);
+            }
             return;
         }
         if (flip_ok()) { // rule 6
@@ -818,7 +874,7 @@ class PassRouter {
                 rc_ = fail(QSIM_ERR_ARG, "internal: state not in its own buffer before the re-layout");
             run_group(held_, false, job_);
         } else {
-            run_group(prev_, pp_ > 0);
+            run_group(prev_, pp_ > 0, nullptr, 0, held_.empty() ? nullptr : &held_[0]);
             run_group(held_, pp_ > 0 && s_->amps != home_);
         }
     }
@@ -838,6 +894,7 @@ FlushRule qsim::flush_rule(qsim_state *s, const std::vector<QueuedGate> &gates, 
     if (r.cacheable || r.hinted || want_key) {
         r.id = plan_identity(s, gates.size(), support);
         r.id.defer = r.defer;
+        r.id.affine = s->affine_support && s->sparse_start ? 1 : 0;
         r.key = gates_key(s, r.id, gates.data(), gates.size());
     }
     return r;
@@ -846,6 +903,7 @@ SchedConfig FlushRule::config(const qsim_state *s) const {
     SchedConfig cfg = state_sched_config(s, support);
     if (hinted) apply_sched_hint(key, cfg);
     cfg.defer_flips = defer == 2 || (defer == 1 && cfg.defer_flips) ? 1 : 0;
+    cfg.affine_support = s->affine_support && s->sparse_start ? 1 : 0; // on wherever a run may start sparse; the schedule is the same either way
     return cfg;
 }
 

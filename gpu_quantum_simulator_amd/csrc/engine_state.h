@@ -67,6 +67,7 @@ struct PlanIdentity {
     uint64_t support = 0;
     qsim::SchedEnv env;
     int defer = 0; // QSIM_OPT_DEFER_FLIPS as it applies to this flush (0: the flush may not defer X gates at all)
+    int affine = 0; // QSIM_OPT_AFFINE_SUPPORT: the passes carry their PassRegion (compared, not hashed: the key names the same schedule either way)
     std::vector<QueuedGate> gates;
 };
 
@@ -126,6 +127,11 @@ struct qsim_state {
     bool partial = false;
     uint64_t support = 0; // qubits some tile pass has had inside its tile since the reset
     int sparse_start = 1; // QSIM_OPT_SPARSE_START
+    // QSIM_OPT_AFFINE_SUPPORT: inside ONE flush the tile passes over a partial support go by the affine subspace the support lies in
+    // (scheduler.h PassRegion): fewer tiles than the coordinate cube.  Between flushes the state is described by support / partial
+    // alone: the last tile pass in front of anything that is not a tile pass of the same flush (a closing pass) writes the whole cube.
+    int affine_support = 1;
+    bool region_pending = false; // the last pass launched wrote only its region: the next launch must be a tile pass that tests it
     int defer_flips = 1;  // QSIM_OPT_DEFER_FLIPS
     uint64_t flips_applied = 0, flip_fallbacks = 0; // flushes whose last tile pass stored the state flipped; flushes that had to run the X gates as a pass of their own
     // op ring for tile passes
@@ -214,8 +220,10 @@ void *spare_buffer(qsim_state *s);
 // fp64 in the tile shape that has the PACK variant, passes out of place between two buffers of the state's own.
 bool may_defer_flips(qsim_state *s);
 // Prepares the blocks of a tile pass for the given bit order in the pinned ring, uploads and launches them.
+// affine / walk_gens: launch_tile's; a pass with a PassRegion always uploads its TileAffine record behind the blocks (a replay of
+// the plan may need it where this launch does not).
 int launch_tile_pass(qsim_state *s, const Pass &p, const TileGeom &geom, bool from_zero_ket, std::vector<TileOp> *capture = nullptr, bool oop = false,
-                     uint64_t zero_mask = 0, PackJob *job = nullptr, uint64_t flip = 0);
+                     uint64_t zero_mask = 0, PackJob *job = nullptr, uint64_t flip = 0, int affine = 0, int walk_gens = 0);
 // qsim_flush; job != NULL: the last pass may write the state re-laid-out instead (PackJob, the comment at the definition).
 int flush_impl(qsim_state *s, PackJob *job);
 // How flush_impl will schedule these gates on a state with this support (for_pack: a flush with a PackJob).  want_key: key and

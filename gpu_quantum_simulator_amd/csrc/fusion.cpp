@@ -143,7 +143,9 @@ bool SchedEnv::operator==(const SchedEnv &o) const {
 
 static SchedConfig with_env(SchedConfig cfg) { apply_sched_env(read_sched_env(), cfg); return cfg; }
 
-Scheduler::Scheduler(const SchedConfig &cfg) : cfg_(with_env(cfg)), tile_(cfg_), open_(cfg.n > 0 ? cfg.n : 0, -1) {}
+Scheduler::Scheduler(const SchedConfig &cfg) : cfg_(with_env(cfg)), tile_(cfg_), open_(cfg.n > 0 ? cfg.n : 0, -1) {
+    if (cfg_.affine_support && cfg_.fuse >= 3) tracker_.start(cfg_.n, cfg_.initial_support);
+}
 
 SchedConfig engine_sched_config(int n, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, int pad_from, bool f32, uint64_t initial_support) {
     SchedConfig c;
@@ -318,7 +320,8 @@ void Scheduler::fold_2q(const cd U[16], int q_hi, int q_lo, uint32_t gates, uint
     open_cluster(op, std::move(src));
 }
 
-void Scheduler::finish(const PassSink &sink) {
+void Scheduler::finish(const PassSink &out) {
+    const PassSink sink = [&](Pass &&p) { tracker_.visit(p); out(std::move(p)); }; // every pass, in the order it will run
     for (int q = 0; q < cfg_.n; q++) close(open_[q]);
     pool_.clear();
     pool_src_.clear();

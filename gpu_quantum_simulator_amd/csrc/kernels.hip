@@ -87,8 +87,8 @@ hipError_t launch_diag1_full(const LaunchCfg &cfg, void *v, bool f32, int n, int
 hipError_t launch_cx(const LaunchCfg &cfg, void *v, bool f32, int n, int control, int target) { return QSIM_DISPATCH(launch_cx(cfg, v, n, control, target)); }
 hipError_t launch_gate2(const LaunchCfg &cfg, void *v, bool f32, int n, int q_hi, int q_lo, const M4 &U) { return QSIM_DISPATCH(launch_gate2(cfg, v, n, q_hi, q_lo, U)); }
 hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, bool f32, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads, bool from_zero_ket,
-                       double amp0, uint64_t zero_mask, const PackMap *pack) {
-    return QSIM_DISPATCH(launch_tile(cfg, v, vout, g, d_ops, n_ops, threads, from_zero_ket, amp0, zero_mask, pack));
+                       double amp0, uint64_t zero_mask, const PackMap *pack, int affine, int walk_gens) {
+    return QSIM_DISPATCH(launch_tile(cfg, v, vout, g, d_ops, n_ops, threads, from_zero_ket, amp0, zero_mask, pack, affine, walk_gens));
 }
 bool launch_tile_can_pack(bool f32, const TileGeom &g, int threads) { return QSIM_DISPATCH(launch_tile_can_pack(g, threads)); }
 hipError_t launch_norm2(const LaunchCfg &cfg, const void *v, bool f32, int n, double *d_out) { return QSIM_DISPATCH(launch_norm2(cfg, v, n, d_out)); }

@@ -113,16 +113,18 @@ static void split_flip(PackMap &pm, const TileGeom &g, int threads) {
 
 template <int B, int THREADS>
 static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops,
-                                bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
+                                bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack, int affine, int walk_gens) {
     zero_mask &= index_mask(g.n); // (a generating pass gets all bits from the engine: only the tile at base 0 exists)
-    const uint64_t ntiles = 1ULL << __builtin_popcountll(index_mask(g.n) & ~tile_mask(g) & ~zero_mask); // tiles whose base index may be non-zero
+    const bool sparse = zero_mask != 0 && !from_zero_ket; // a pass over a partially written state: k_tile<SPARSE>
+    if (affine && (!sparse || walk_gens < 0 || walk_gens > kAffineMaxGens)) return hipErrorInvalidValue; // only SPARSE reads the record
+    // tiles whose base index may be non-zero: the coordinate cube outside zero_mask, or the span of the record's generators
+    const uint64_t ntiles = (affine & kAffineWalk) ? 1ULL << walk_gens : 1ULL << __builtin_popcountll(index_mask(g.n) & ~tile_mask(g) & ~zero_mask);
     const int lds = ((int)sizeof(amp_t) << g.tile_bits) + (8 << g.n_high); // the tile, then k_tile's hoff table
     constexpr bool kHasPack = tile_has_pack(B, THREADS);
     const bool packed = pack != nullptr && (pack->k > 0 || pack->flip != 0); // flips alone: the identity permutation (identity_pack_map)
     if (packed && !kHasPack) return hipErrorNotSupported;
-    const bool sparse = zero_mask != 0 && !from_zero_ket; // a pass over a partially written state: k_tile<SPARSE>
     // four instantiations at most (PACK x SPARSE), all of one signature: the variant is chosen here, once, as an index and a pointer
-    using TileKernel = void (*)(amp_t *, amp_t *, TileDev, const TileOp *, int, uint64_t, int, int, PackMap);
+    using TileKernel = void (*)(amp_t *, amp_t *, TileDev, const TileOp *, int, uint64_t, int, int, PackMap, int);
     const TileKernel plain[2] = {k_tile<B, THREADS, false, false>, k_tile<B, THREADS, false, true>};
     int which = sparse ? 1 : 0;
     TileKernel fn = plain[which];
@@ -170,15 +172,15 @@ static hipError_t launch_tile_t(const LaunchCfg &cfg, void *v, void *vout, const
         split_flip(pm, g, THREADS);
     }
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(THREADS), lds, cfg.stream, (amp_t *)v, (amp_t *)vout, td, d_ops, n_ops - n_scale, ntiles, tpw,
-                       n_scale, pm);
+                       n_scale, pm, affine);
     return hipGetLastError();
 }
 
 // threads: 0 = the default for the tile size (tile_threads).  One case per shape that exists.
 hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads,
-                       bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack) {
+                       bool from_zero_ket, double amp0, uint64_t zero_mask, const PackMap *pack, int affine, int walk_gens) {
 #define QSIM_TILE(B_, T_) \
-    case (B_) * 2048 + (T_): return launch_tile_t<B_, T_>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, zero_mask, pack)
+    case (B_) * 2048 + (T_): return launch_tile_t<B_, T_>(cfg, v, vout, g, d_ops, n_ops, from_zero_ket, amp0, zero_mask, pack, affine, walk_gens)
     switch (g.tile_bits * 2048 + tile_threads(g.tile_bits, threads)) {
     QSIM_TILE(0, 64);
     QSIM_TILE(1, 64);

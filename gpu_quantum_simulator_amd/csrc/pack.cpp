@@ -121,6 +121,7 @@ extern "C" int qsim_swap_buffer(qsim_state *s, void **buffer) {
     *buffer = old;
     s->zero_ket_pending = false; // the new buffer's contents ARE the state: taken as written everywhere unless the caller says
     s->partial = false;          // otherwise (qsim_set_support, qsim_reset_shard)
+    s->region_pending = false;
     if (s->spare == s->amps && !s->owns_spare) s->spare = old; // a lent spare that just became the state: the old state takes its place
     return QSIM_OK;
 }

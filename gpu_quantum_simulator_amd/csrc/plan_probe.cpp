@@ -30,6 +30,7 @@ struct ProbeShape {
     int tile_bits, tile_low_bits, tile_max_ops = 32;
     uint64_t initial_support = 0;
     bool defer = false; // the X gates left to an index flip (SchedConfig::defer_flips): residual_flips says which
+    bool affine = false; // the passes carry their PassRegion (SchedConfig::affine_support)
 };
 
 // How every probe opens: the arguments checked (have_args: the caller's pointers are all there) and the circuit scheduled as an
@@ -40,6 +41,7 @@ int probe_passes(bool have_args, const qsim_circuit *c, int fuse, const ProbeSha
     if (fuse < 0 || fuse > 3) return fail(QSIM_ERR_ARG, "fuse level %d not in 0..3", fuse);
     SchedConfig cfg = engine_sched_config(c->num_q, fuse, shape.tile_bits, shape.tile_low_bits, shape.tile_max_ops, 10, false, shape.initial_support);
     cfg.defer_flips = shape.defer ? 1 : 0;
+    cfg.affine_support = shape.affine ? 1 : 0;
     passes = schedule(cfg, queue_of(c), gates_seen, residual_flips);
     return QSIM_OK;
 }
@@ -124,10 +126,43 @@ extern "C" int qsim_plan_passes(const qsim_circuit *c, int fuse, int tile_bits, 
     return QSIM_OK;
 }
 
+extern "C" int qsim_plan_regions(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support, int defer,
+                                 qsim_pass_region *out, int cap, int *count) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(count && !(cap > 0 && !out), c, fuse, {tile_bits, tile_low_bits, tile_max_ops, initial_support, defer != 0, true}, passes));
+    *count = (int)passes.size();
+    for (size_t i = 0; i < passes.size() && (int)i < cap; i++) {
+        const Pass &p = passes[i];
+        const PassRegion &r = p.region;
+        qsim_pass_region &o = out[i];
+        memset(&o, 0, sizeof o);
+        o.kernel_class = p.kclass;
+        o.tile_mask = p.kclass == QSIM_K_TILE ? tile_mask(p.geom) : index_mask(c->num_q);
+        o.on = r.on ? 1 : 0;
+        o.refined = r.refined ? 1 : 0;
+        o.support_before = r.support_before;
+        o.origin = r.origin;
+        o.n_gen = (int)r.gen.size();
+        for (size_t j = 0; j < r.gen.size() && j < 64; j++) o.gen[j] = r.gen[j];
+        o.n_checks = (int)r.checks.size();
+        for (size_t j = 0; j < r.checks.size() && j < 64; j++) { o.check_mask[j] = r.checks[j].mask; o.check_parity |= (uint64_t)(r.checks[j].parity & 1) << j; }
+        o.visited = r.on ? r.visited : p.visited;
+        o.read_share = r.on ? r.read_share : p.read_share;
+    }
+    return QSIM_OK;
+}
+
 extern "C" int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                                      qsim_sched_cb cb, void *user) {
     std::vector<Pass> passes;
     QSIM_TRY(probe_passes(cb != nullptr, c, fuse, {tile_bits, tile_low_bits, tile_max_ops}, passes));
+    return report_schedule(passes, cb, user);
+}
+
+extern "C" int qsim_schedule_circuit_from(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                                          qsim_sched_cb cb, void *user) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(cb != nullptr, c, fuse, {tile_bits, tile_low_bits, tile_max_ops, initial_support}, passes));
     return report_schedule(passes, cb, user);
 }
 

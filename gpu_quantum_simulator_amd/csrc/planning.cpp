@@ -267,7 +267,7 @@ static int keep_fastest_schedule(qsim_state *s, const qsim_circuit *c, const Sch
         for (int rep2 = 0; rep2 < 2 && rc == QSIM_OK; rep2++) { // the second run replays the cached plan: no host work in the way
             if (support == 0) rc = qsim_reset(s);
             else if (support != ~0ULL) rc = qsim_set_support(s, support & nmask);
-            else { s->zero_ket_pending = false; s->partial = false; } // a dense state: whatever the buffer holds
+            else { s->zero_ket_pending = false; s->partial = false; s->region_pending = false; } // a dense state: whatever the buffer holds
             if (rc) break;
             timer.start();
             rc = qsim_run_circuit(s, c, 0, -1);

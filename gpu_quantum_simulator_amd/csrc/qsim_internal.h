@@ -81,6 +81,20 @@ constexpr uint32_t kInfoSkips = 8u, kInfoBarrier = 16u;
 static_assert(sizeof(PartRec) == 64 + 512 && offsetof(TileOp, scale) == 32 && offsetof(TileOp, rec) == 128 &&
               sizeof(TileOp) == 128 + kMaxBanks * kMaxParts * sizeof(PartRec), "TileOp layout is shared with the device");
 
+// Affine support (scheduler.h PassRegion).  A pass over a partially written state that knows the affine subspace the support lies
+// in finds this record BEHIND its last block in the op buffer (it takes a TileOp's place there, read through scalar loads like
+// the blocks): the tiles to visit are origin ^ span(gen[0 .. n_gen)), and an amplitude of the input is stale memory, staged in as
+// zero, unless popcount(index & chk[j]) has parity bit j of chk_par for every j < n_chk.
+constexpr int kAffineMaxGens = 18, kAffineMaxChecks = 18;
+constexpr int kAffineWalk = 1, kAffineChecks = 2; // k_tile's `affine` argument: which halves of the record the pass goes by
+struct TileAffine {
+    uint32_t n_gen, n_chk, chk_par, pad0;
+    uint64_t origin, pad1;
+    uint64_t gen[kAffineMaxGens];
+    uint64_t chk[kAffineMaxChecks];
+};
+static_assert(sizeof(TileAffine) <= sizeof(TileOp) && offsetof(TileAffine, gen) == 32, "TileAffine takes the place of a TileOp in the op buffer");
+
 // LDS layout swizzle of a tile slot index: the 16-byte unit inside a 256-byte bank row (slot bits 0..3) is XORed with a
 // linear image of the HIGHER slot bits.  A block on tile-local bits H ("holes") makes the lanes of a wave walk the
 // lowest non-hole bits; a ds_read_b128 is conflict-free when, inside each of its four 16-lane groups (a 4-dimensional
@@ -176,8 +190,10 @@ hipError_t launch_gate2(const LaunchCfg &cfg, void *v, bool f32, int n, int q_hi
 // with one inside a tile are staged in as zero (their memory may never have been written)
 // vout: where the pass writes the state — v itself (in place) or a second buffer of the same size
 // pack (fp64, the default tile shape only — launch_tile_can_pack): vout is the output buffer of the re-layout, written at perm(index)
+// affine (kAffineWalk | kAffineChecks; only with a zero_mask, never from_zero_ket): d_ops[n_ops] is a TileAffine the pass goes by;
+// walk_gens: its n_gen, which the grid is sized by when the pass walks
 hipError_t launch_tile(const LaunchCfg &cfg, void *v, void *vout, bool f32, const TileGeom &g, const TileOp *d_ops, int n_ops, int threads,
-                       bool from_zero_ket, double amp0, uint64_t zero_mask = 0, const PackMap *pack = nullptr);
+                       bool from_zero_ket, double amp0, uint64_t zero_mask = 0, const PackMap *pack = nullptr, int affine = 0, int walk_gens = 0);
 bool launch_tile_can_pack(bool f32, const TileGeom &g, int threads);
 // zeroes the amplitudes whose index has a bit of zero_mask set (the part of a state the tile passes have not written yet)
 hipError_t launch_zero_outside(const LaunchCfg &cfg, void *v, bool f32, int n, uint64_t zero_mask);

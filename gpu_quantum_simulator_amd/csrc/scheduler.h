@@ -8,12 +8,14 @@
 // (the reference's 1e-3 tolerance reorders gates), and level 3 groups clusters into
 // cache-blocked passes by a greedy scan over the dependency order.
 //
-// Three files implement it, by concern (scheduler_impl.h holds the few helpers they share; libqsim.so exports none of them):
+// Four files implement it, by concern (scheduler_impl.h holds the few helpers they share; libqsim.so exports none of them):
 //   fusion.cpp        FusedOp predicates, the fusion algebra, the cluster state machine (add_1q / add_cx / add_2q / fold_2q /
 //                     close / finish), the QSIM_SCHED_* knob table and engine_sched_config
 //   tile_block.cpp    TileBlock methods, the row-class components, to_block, merge_blocks
 //   pass_builder.cpp  single_op_pass, tile_pass, and the level-3 pass construction: PendingWalk (the ONE walk over the pending
 //                     clusters) and PassBuilder, whose named steps build_passes calls in a loop
+//   support_tracker.cpp  SupportTracker: the state's support as an affine subspace (affine.h), carried through the passes as they
+//                     are handed out; what a tile pass over a partial support has to visit and may believe of its input (PassRegion)
 #ifndef QSIM_SCHEDULER_H
 #define QSIM_SCHEDULER_H
 
@@ -23,6 +25,7 @@
 #include <functional>
 #include <vector>
 
+#include "affine.h"
 #include "qsim_internal.h"
 
 namespace qsim {
@@ -107,6 +110,25 @@ struct TileBlock {
 // LDS slots, coefficients rounded once, here, and stored as the float pairs the fp32 kernels consume (tile_kernel.inc coef_t).
 bool to_tile_op(const TileGeom &g, const TileBlock &blk, TileOp &t, bool f32 = false);
 
+// What SchedConfig::affine_support adds to a tile pass: where the pass has to go and what it may believe of its input, both
+// from the affine subspace V of GF(2)^n that the state's support lies in when the pass starts (SupportTracker).
+//   tiles    origin ^ span(gen): V projected onto the index bits outside the tile.  `refined`: that is fewer tiles than the
+//            coordinate cube over (support | tile) which the pass visits otherwise; when it is not, gen are that cube's unit vectors.
+//   checks   the region the PREVIOUS tile pass of the flush wrote when it was refined: an index outside it holds stale memory and
+//            is staged in as zero.  Checks that the coordinate zero_mask of this pass implies are left out.
+// visited / read_share are the shares of the register the pass then writes and reads; Pass::visited and Pass::read_share keep
+// the coordinate count, which the plan probes and the pass-time model were fitted and pinned on.
+constexpr int kMaxRegionGens = kAffineMaxGens, kMaxRegionChecks = kAffineMaxChecks; // what the kernel's record holds (qsim_internal.h TileAffine)
+struct PassRegion {
+    bool on = false;
+    bool refined = false;
+    uint64_t support_before = 0; // the coordinate support the engine must find when the pass starts: what all of this assumes
+    uint64_t origin = 0;
+    std::vector<uint64_t> gen;
+    std::vector<ParityCheck> checks;
+    double visited = 1.0, read_share = 1.0;
+};
+
 struct Pass {
     int kclass = 0;           // QSIM_K_*
     std::vector<FusedOp> ops;      // the one op of a single-op pass; empty for QSIM_K_TILE
@@ -125,6 +147,7 @@ struct Pass {
                               // support before the pass are loaded (visited / 2^(tile qubits new to the support); 0 for the pass that generates the basis state)
     double moved() const { return bytes / 2 * (visited + read_share); } // algorithmic bytes of the pass as it runs: half of `bytes` are reads, half writes
     bool diag_full = false;   // QSIM_K_PHASE executed over every amplitude (d0 != 1 or q < 2)
+    PassRegion region;        // SchedConfig::affine_support
 };
 
 // What a pass costs, in bytes moved at the rate of a pass that is bound by its memory traffic.  A tile pass is: up to four
@@ -183,6 +206,9 @@ struct SchedConfig {
     // gates then force no qubit into any tile.  Off by default: the constraints only ever shrink, but the greedy packing does
     // not turn that into fewer sweeps on every circuit, so it is one more variant for the planning step to price.
     int defer_flips = 0;
+    // 1: every tile pass of a run that starts on a partial support carries its PassRegion.  The schedule itself is the same either
+    // way: the packer keeps to the coordinate support.
+    int affine_support = 0;
     int track = 0; // 1: every pass lists the gates it absorbed (Pass::src) — the shard planner asks which gates a segment's last pass holds
 };
 
@@ -219,6 +245,24 @@ struct SchedEnv {
 SchedEnv read_sched_env();                      // the environment as it is now
 void apply_sched_env(const SchedEnv &e, SchedConfig &cfg);
 
+// The state's support as an affine subspace, carried through the passes of a schedule in the order they will run.  X translates
+// it, CX maps it linearly, diagonal gates leave it alone; only a gate that mixes a qubit adds a direction, so its dimension grows
+// by at most one per h / sx and not by one per qubit a tile touches.  Each merged block is applied by its exact non-zero pattern
+// (the entries TileBlock keeps): the new V is the affine hull of every index some non-zero entry can carry an amplitude of V to.
+// A hull may be larger than the true support (sound); it is never smaller.
+class SupportTracker {
+  public:
+    void start(int n, uint64_t initial_support);
+    void visit(Pass &p); // fills p.region (tile passes while the support is partial), then moves V through the pass
+  private:
+    void apply(const TileBlock &b);
+    int n_ = 0;
+    bool live_ = false;
+    AffineSpace V_;
+    uint64_t sup_ = 0;                // the coordinate support as the engine tracks it (qsim_state::support)
+    std::vector<ParityCheck> wrote_;  // the region the last tile pass wrote, if it was refined
+};
+
 class Scheduler {
   public:
     explicit Scheduler(const SchedConfig &cfg);
@@ -251,6 +295,7 @@ class Scheduler {
     std::vector<FusedOp> closed_; // fused ops in a valid execution order
     std::vector<std::vector<uint32_t>> pool_src_, closed_src_; // SchedConfig::track: the gates behind pool_[i] / closed_[i]
     mutable std::vector<uint32_t> cur_src_;                     // ... and behind the pass being emitted
+    SupportTracker tracker_;         // SchedConfig::affine_support
     uint64_t flips_ = 0;             // SchedConfig::defer_flips: qubits whose X is still owed
     std::vector<uint32_t> deferred_; // ... and the X statements that produced no cluster, by their order of arrival
     bool deferring() const { return cfg_.defer_flips != 0 && cfg_.fuse >= 3; }

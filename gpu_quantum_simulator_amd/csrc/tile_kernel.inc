@@ -460,7 +460,7 @@ __host__ __device__ __forceinline__ uint64_t pack_perm(const PackMap &pm, uint64
 // the sub-millisecond passes come that way.  Full sweeps run the SPARSE = false instantiation, which carries none of this.
 template <int B, int THREADS, bool PACK = false, bool SPARSE = false>
 __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(amp_t *v, amp_t *vout, TileDev g, const TileOp *__restrict__ ops_g,
-                                                  int n_ops, uint64_t ntiles, int tiles_per_wg, int n_scale, PackMap pm) {
+                                                  int n_ops, uint64_t ntiles, int tiles_per_wg, int n_scale, PackMap pm, int affine) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     amp_t *lds = reinterpret_cast<amp_t *>(smem);
     constexpr uint32_t E = 1u << B;
@@ -519,7 +519,47 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     auto elem_ptr = [&](uint64_t tile_base, int k) -> amp_t * {
         return reinterpret_cast<amp_t *>(reinterpret_cast<unsigned char *>(v) + ((tile_base << kAmpShift) + k_off[k]) + lane_off);
     };
-    auto next_base = [&](uint64_t b) { return ((b | ~outer_mask) + 1ULL) & outer_mask; }; // +1 scattered over the outer bits
+    // SPARSE with an affine record (qsim_internal.h TileAffine, behind the last block): the tiles are origin ^ span(gen), walked in
+    // Gray-code order of the tile counter — the next base is ONE scalar XOR with gen[ctz(counter + 1)] — and a slot of the input
+    // is stale unless every parity check holds.  Parity is linear and the index is lane part | register part | tile base over
+    // disjoint bits, so bit j of (lane_par ^ k_par(k) ^ tile parities) is check j of the slot: one compare per register per tile.
+    // The register part is linear in the bits of k as well: kb[i] is the vector of register 2^i, k_par(k) a few scalar XORs of them.
+    typedef const __attribute__((address_space(4))) TileAffine *ConstAffine;
+    ConstAffine aff = (ConstAffine)(ops + n_ops);
+    const bool walk = SPARSE && (affine & kAffineWalk) != 0; // wave-uniform
+    const int n_chk = SPARSE && (affine & kAffineChecks) ? (int)aff->n_chk : 0;
+    uint64_t tcount = 0; // the tile counter of `base` (walk)
+    constexpr int KB = APT > 1 ? __builtin_ctz((unsigned)APT) : 1; // (APT is a power of two)
+    uint32_t lane_par = 0, kb[KB], chk_want = 0;
+    if constexpr (SPARSE) {
+#pragma unroll
+        for (int i = 0; i < KB; i++) kb[i] = 0;
+        if (n_chk > 0) chk_want = aff->chk_par;
+        for (int j = 0; j < n_chk; j++) {
+            const uint64_t m = aff->chk[j]; // wave-uniform
+            lane_par |= (uint32_t)(__builtin_popcountll((lane_off >> kAmpShift) & m) & 1) << j;
+#pragma unroll
+            for (int i = 0; i < KB; i++)
+                if ((1 << i) < APT) kb[i] |= (uint32_t)(__builtin_popcountll((k_off[(1 << i) < APT ? (1 << i) : 0] >> kAmpShift) & m) & 1) << j;
+        }
+    }
+    auto k_par = [&](int k) { // wave-uniform
+        uint32_t par = 0;
+#pragma unroll
+        for (int i = 0; i < KB; i++)
+            if (k >> i & 1) par ^= kb[i];
+        return par;
+    };
+    auto tile_par = [&](uint64_t b) { // the checks' parities of a tile base, against the wanted ones: 0 where the tile's share agrees
+        uint32_t par = chk_want;
+        for (int j = 0; j < n_chk; j++) par ^= (uint32_t)(__builtin_popcountll(b & aff->chk[j]) & 1) << j;
+        return par;
+    };
+    auto next_base = [&](uint64_t b) -> uint64_t {
+        if constexpr (SPARSE)
+            if (walk) return b ^ aff->gen[__builtin_ctzll(tcount + 1ULL)];
+        return ((b | ~outer_mask) + 1ULL) & outer_mask; // +1 scattered over the outer bits
+    };
 
     // vout != v: the pass reads the state from one buffer and writes it to the other (the engine then swaps them).  Same
     // bytes, but the chip sustains more of them when a read stream and a write stream do not share addresses: the
@@ -576,11 +616,14 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
 #pragma unroll
             for (int k = 0; k < APT; k++) pf[k] = cmul(pf[k], make_coef(fr, fi));
         }
-        if (SPARSE && !generate) { // slots outside the state's support are zero (not loaded, or unwritten memory the fallback loaded);
-                                   // after the tile-uniform factors, so that they are +0 whatever the factors are
+        if constexpr (SPARSE) {
+            if (!generate) { // slots outside the state's support are zero (not loaded, unwritten memory the fallback loaded, or memory outside
+                             // the region the previous pass wrote); after the tile-uniform factors, so that they are +0 whatever the factors are
+                const uint32_t tp = tile_par(base); // wave-uniform, and so is k_par(k) ^ tp: the lane's own vector is compared with a scalar
 #pragma unroll
-            for (int k = 0; k < APT; k++)
-                if (!(sparse_lane_ok && ((k_off[k] >> kAmpShift) & g.zero_mask) == 0)) pf[k] = amp_t{(real_t)0, (real_t)0};
+                for (int k = 0; k < APT; k++)
+                    if (!(sparse_lane_ok && ((k_off[k] >> kAmpShift) & g.zero_mask) == 0 && lane_par == (k_par(k) ^ tp))) pf[k] = amp_t{(real_t)0, (real_t)0};
+            }
         }
 #pragma unroll
         for (int k = 0; k < APT; k++)
@@ -611,10 +654,21 @@ __global__ __launch_bounds__(THREADS, QSIM_TILE_MIN_WAVES(THREADS)) void k_tile(
     };
 
     uint64_t base = deposit(first_tile, outer_mask); // wave-uniform
+    if constexpr (SPARSE) {
+        if (walk) { // the chunk's first base: the generators the Gray code of its first counter picks
+            tcount = first_tile;
+            base = aff->origin;
+            const uint64_t gray = first_tile ^ (first_tile >> 1);
+            const int n_gen = (int)aff->n_gen;
+            for (int i = 0; i < n_gen; i++)
+                if (gray >> i & 1ULL) base ^= aff->gen[i];
+        }
+    }
     fetch(base);
     process(base, cnt > 1);                                                   // peeled first iteration
     for (int j = 1; j < cnt; j++) {                                           // steady state; the last one fetches nothing
         base = next_base(base);
+        if constexpr (SPARSE) tcount++;
         process(base, j + 1 < cnt);
     }
 }

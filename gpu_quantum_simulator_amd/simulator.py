@@ -120,10 +120,28 @@ class Circuit:
                  "visited": float(buf[i].visited), "bytes": float(buf[i].bytes), "cost_bytes": float(buf[i].cost_bytes)}
                 for i in range(min(n.value, cap))]
 
-    def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, flips: list = None) -> list:
+    def regions(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, initial_support: int = 0,
+                defer: bool = False) -> list:
+        """qsim_plan_regions: per pass of schedule() with the same arguments (defer: of schedule(flips=[])) what
+        QSIM_OPT_AFFINE_SUPPORT adds — the tiles to visit (origin, gen), the parity checks of the region the previous pass wrote
+        as (mask, parity) pairs, and the shares of the register written and read."""
+        from ctypes import c_int
+        cap = 4096
+        buf = (_lib.QsimPassRegion * cap)()
+        n = c_int()
+        check(_lib.load().qsim_plan_regions(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(defer)), buf, cap, byref(n)))
+        return [{"kernel": _lib.K_NAMES[r.kernel_class], "on": bool(r.on), "refined": bool(r.refined), "tile_mask": int(r.tile_mask),
+                 "support_before": int(r.support_before), "origin": int(r.origin), "gen": [int(r.gen[j]) for j in range(r.n_gen)],
+                 "checks": [(int(r.check_mask[j]), int(r.check_parity >> j & 1)) for j in range(r.n_checks)],
+                 "visited": float(r.visited), "read_share": float(r.read_share)}
+                for r in (buf[i] for i in range(min(n.value, cap)))]
+
+    def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, flips: list = None,
+                 initial_support: int = 0) -> list:
         """Fused blocks in launch order: (pass, kernel_class, kind, qubits, matrix|None, gates_folded); kind is
         "u1" / "cx" / "u2" ... "u8", qubits most significant first (cx: control, target).  flips: a list — the schedule with
-        the X gates deferred (qsim_schedule_circuit_deferred); the residual index mask is appended to it."""
+        the X gates deferred (qsim_schedule_circuit_deferred); the residual index mask is appended to it.  initial_support
+        (without flips): the index bits that may be 1 in the state the circuit finds (qsim_schedule_circuit_from)."""
         out = []
 
         def cb(_user, pass_i, kclass, kind, qubits, nq, U, folded):
@@ -135,8 +153,10 @@ class Circuit:
             out.append((pass_i, _lib.K_NAMES[kclass], {1: "u1", 2: "cx", 3: "u2", 4: "u3", 5: "u4", 6: "u5", 7: "u6", 8: "u7", 9: "u8"}[kind], qs, m, folded))
 
         if flips is None:
-            check(_lib.load().qsim_schedule_circuit(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, _lib.SCHED_CB(cb), None))
+            check(_lib.load().qsim_schedule_circuit_from(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, _lib.SCHED_CB(cb), None))
             return out
+        if initial_support:
+            raise ValueError("schedule: initial_support goes with flips=None")
         mask = ctypes.c_uint64()
         check(_lib.load().qsim_schedule_circuit_deferred(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, _lib.SCHED_CB(cb), None,
                                                          byref(mask)))
@@ -451,7 +471,7 @@ class Simulator(_PauliStrings):
                  "grid_cap": _lib.OPT_GRID_CAP, "tile_threads": _lib.OPT_TILE_THREADS,
                  "tile_pad_from": _lib.OPT_TILE_PAD_FROM, "debug_tile_order": _lib.OPT_DEBUG_TILE_ORDER, "plan_cache": _lib.OPT_PLAN_CACHE,
                  "pingpong": _lib.OPT_PINGPONG, "sparse_start": _lib.OPT_SPARSE_START, "debug_plan_key": _lib.OPT_DEBUG_PLAN_KEY,
-                 "defer_flips": _lib.OPT_DEFER_FLIPS}
+                 "defer_flips": _lib.OPT_DEFER_FLIPS, "affine_support": _lib.OPT_AFFINE_SUPPORT}
         # tile_low_bits first when shrinking, tile_bits first when growing: keep every intermediate valid
         for key in sorted(options, key=lambda k: k != "tile_low_bits"):
             self.set_option(names[key], options[key])
@@ -883,7 +903,8 @@ class Cluster(_PauliStrings):
             raise _lib.QsimError(rc, (lib.qsim_cluster_error() or b"").decode())
         self.num_qubits, self.num_shards = num_q, num_shards
         names = {"fuse": _lib.OPT_FUSE, "tile_bits": _lib.OPT_TILE_BITS, "tile_low_bits": _lib.OPT_TILE_LOW_BITS,
-                 "tile_max_ops": _lib.OPT_TILE_MAX_OPS, "profile": _lib.OPT_PROFILE, "pingpong": _lib.OPT_PINGPONG}
+                 "tile_max_ops": _lib.OPT_TILE_MAX_OPS, "profile": _lib.OPT_PROFILE, "pingpong": _lib.OPT_PINGPONG,
+                 "affine_support": _lib.OPT_AFFINE_SUPPORT}
         for key in sorted(options, key=lambda k: k != "tile_low_bits"):
             self._check(lib.qsim_cluster_set_option(self._h, names[key], int(options[key])))
 

@@ -66,6 +66,10 @@ enum {
                                 * two swap (an even number of times per flush: the state is back in its own buffer afterwards).  The
                                 * same bytes move ~5 % faster than in place at n = 30.  0 never, 1 (default) for states of >= 8 GiB
                                 * when the second buffer fits (allocated on first use, or lent with qsim_set_spare_buffer), 2 always */
+    QSIM_OPT_AFFINE_SUPPORT = 18,/* default 1: inside one flush, tile passes over a partially written state (QSIM_OPT_SPARSE_START) visit only
+                                 * the tiles of the affine subspace of index space the support lies in — X translates it, CX maps it
+                                 * linearly, only a mixing gate adds a direction — instead of the whole cube over the qubits touched.
+                                 * Schedules are the same either way; 0: every launch is what it was without the option. */
     QSIM_OPT_SPARSE_START = 15,/* default 1: after a reset the state is zero wherever a qubit no pass has mixed yet is 1, and the tile
                                 * passes only visit the rest: the first pass of a circuit writes one tile, the second a few hundred,
                                 * the full sweeps start when every qubit has been inside a tile (memory outside that support is
@@ -810,6 +814,20 @@ typedef struct {
     double visited, bytes, cost_bytes;
 } qsim_pass_info;
 int qsim_plan_passes(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, uint64_t initial_support, qsim_pass_info *out, int cap, int *count);
+/* The schedule qsim_schedule_circuit (defer == 0) or qsim_schedule_circuit_deferred (defer != 0) reports, for a run that finds a
+ * state of the given support, with what QSIM_OPT_AFFINE_SUPPORT adds to each pass.  on: the pass is a tile pass over a partial
+ * support.  The tiles it visits unless it is a closing pass (then the coordinate cube over support_before | tile_mask) are the
+ * index bases origin ^ span(gen[0 .. n_gen)); refined: those are fewer than that cube.  check_mask / check_parity (bit j): the
+ * region the previous pass wrote — an input index x is stale memory unless popcount(x & check_mask[j]) has parity bit j for every
+ * j < n_checks.  visited / read_share: the shares of the register the pass writes and reads when it goes by its region. */
+typedef struct {
+    int32_t kernel_class, on, refined, n_gen, n_checks, reserved;
+    uint64_t tile_mask, support_before, origin, check_parity;
+    uint64_t gen[64], check_mask[64];
+    double visited, read_share;
+} qsim_pass_region;
+int qsim_plan_regions(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support, int defer,
+                      qsim_pass_region *out, int cap, int *count);
 /* Same scheduler, op by op: calls `cb` for every fused block in launch order with the pass it belongs to, the
  * kernel class of that pass, the block kind (QSIM_GATE_U1 / _CX / _U2 .. _U8 by qubit count), its qubits (most
  * significant first; CX: control, target) and its matrix (2^nq x 2^nq complex, row-major; NULL for CX).  A block of a
@@ -820,6 +838,10 @@ typedef void (*qsim_sched_cb)(void *user, int pass, int kernel_class, int kind, 
                               const double *U, int gates_folded);
 int qsim_schedule_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                           qsim_sched_cb cb, void *user);
+/* The same for a run that finds a state of the given support (index bits that may be 1; 0: fresh from a reset), as
+ * qsim_plan_regions with defer == 0 describes it. */
+int qsim_schedule_circuit_from(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                               qsim_sched_cb cb, void *user);
 /* The same with the X gates deferred (QSIM_OPT_DEFER_FLIPS; level 3 only): the blocks of a schedule without them, and in *flip_mask
  * the index bits still flipped at the end — the circuit's state is the replayed one with amplitude i moved to i ^ *flip_mask.  The
  * deferred statements are counted in gates_folded of the last block reported. */
