@@ -158,6 +158,9 @@ SIGNATURES = {
     "qsim_device_ptr": (c_void_p, [c_void_p]),
     "qsim_stream": (c_void_p, [c_void_p]),
     "qsim_sample": (c_int, [c_void_p, _DP, c_long, POINTER(c_uint64)]),
+    "qsim_sample_geometry": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64)]),
+    "qsim_sample_shots": (c_int, [c_void_p, _DP, c_long, POINTER(c_int), c_int, POINTER(c_uint64)]),
+    "qsim_sample_stage_times": (c_int, [c_void_p, _DP, _DP]),
     "qsim_draw_randn": (c_double, []),
     "qsim_putb": (None, [ctypes.c_longlong, c_int, c_char_p]),
     "qsim_pack_bits": (c_int, [c_void_p, POINTER(c_int), c_int, c_void_p]),

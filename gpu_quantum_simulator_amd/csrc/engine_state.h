@@ -18,6 +18,7 @@
 //   density.cpp        reduced density matrices of qubit subsets: the plan, the call, from tiles to rho (the host side of density.hip; density.h)
 //   matrix.cpp         dense matrices on up to five targets under controls: the plan, the operand, the call (the host side of matrix.hip; matrix.h)
 //   diagonal.cpp       whole-register diagonal operators from a table: the qsim_diagonal object, the plan, the set-up calls and the two sweeps (the host side of diagonal.hip; diagonal.h)
+//   sample.cpp         shots drawn on the device: the pyramid's geometry and the call (the host side of sample.hip; sample.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 

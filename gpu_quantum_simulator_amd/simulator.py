@@ -817,6 +817,33 @@ class Simulator(_PauliStrings):
         check(_lib.load().qsim_sample(self._h, _dp(r), r.size, out.ctypes.data_as(ctypes.POINTER(c_uint64))))
         return out
 
+    def sample_shots(self, shots: Optional[int] = None, qubits=None, *, seed=None, draws=None) -> np.ndarray:
+        """Basis states drawn on the device (qsim_sample_shots): one uint64 per shot — the basis index, or with `qubits`
+        the outcome on them (bit j of a result is qubit qubits[j]).  Pass either `draws`, the caller's own numbers in [0, 1] (a
+        reproducible pipeline), or `shots`, for which np.random.default_rng(seed).random(shots) is drawn here.  The draws are scaled by
+        the state's own total, so an unnormalised state samples |a|^2 / norm2; an index of probability zero is never returned.  Pending
+        gates are launched first; the state is not changed."""
+        from ctypes import c_uint64
+        if (draws is None) == (shots is None):
+            raise ValueError("sample_shots takes either shots or draws")
+        if draws is None:
+            if int(shots) < 0:
+                raise ValueError("shots must not be negative")
+            draws = np.random.default_rng(seed).random(int(shots))
+        elif seed is not None:
+            raise ValueError("a seed goes with shots, not with draws")
+        u = np.ascontiguousarray(draws, dtype=np.float64).reshape(-1)
+        qs = [] if qubits is None else [int(q) for q in qubits]
+        arr = (c_int * len(qs))(*qs) if qs else None
+        out = np.zeros(u.size, dtype=np.uint64)
+        check(_lib.load().qsim_sample_shots(self._h, _dp(u), u.size, arr, len(qs), out.ctypes.data_as(ctypes.POINTER(c_uint64))))
+        return out
+
+    def sample_counts(self, shots: int, qubits=None, seed=None) -> dict:
+        """{outcome: how often it was drawn} over sample_shots(shots, qubits, seed=seed), keys ascending."""
+        values, counts = np.unique(self.sample_shots(shots, qubits, seed=seed), return_counts=True)
+        return {int(v): int(c) for v, c in zip(values, counts)}
+
     def norm2(self) -> float:
         v = c_double()
         check(_lib.load().qsim_norm2(self._h, byref(v)))

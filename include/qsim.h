@@ -513,6 +513,39 @@ double qsim_draw_randn(void);
 /* putb (:285-293): `len` binary digits of n, most significant first, NUL-terminated into buf (len + 1 bytes). */
 void qsim_putb(long long n, int len, char *buf);
 
+/* ---- shots drawn on the device (one state only — a cluster keeps qsim_cluster_sample) ----
+ * qsim_sample above restates the reference for a handful of draws: a blocking copy and a host scan per draw.  qsim_sample_shots draws
+ * any number of shots in one read-only sweep of the state plus one wave per draw, and never writes the cumulative distribution at
+ * amplitude resolution.  It keeps a pyramid of fp64 sums instead (both precisions; p_i = fma(re, re, im im) on widened components):
+ * chunks of 2^cb amplitudes, cb = min(8, n), which one wave scans in a fixed order; groups of 2^gb amplitudes, gb = min(18, n), with
+ * the running sums of their chunks' totals; and the running sums of the groups' totals.  Both running sums are sequential, so they
+ * never decrease.  A draw u in [0, 1] becomes r = u T, T the state's own total; the first group and then the first chunk whose running
+ * sum is non-zero and >= r are found by bisection, the chunk is scanned again by the same code that formed its total, and the result is
+ * the chunk's first index i with p_i > 0 whose cumulative value is non-zero and >= r.  The chunk's end and the bisected sums round
+ * differently, so rounding can leave no such index: then the result is the chunk's LAST index with p_i > 0 (there is one: the chunk
+ * moved the running sum).  What follows, and where it departs from qsim_sample:
+ *   - draws are scaled by the state's total, so an unnormalised state samples |a_i|^2 / sum |a|^2 (qsim_sample compares the random
+ *     number with the unscaled cumulative sum and piles what lies beyond it on 2^n - 1);
+ *   - an index of probability zero is never returned, and there is no fallback index: u = 0 returns the first index with p > 0, u = 1
+ *     an index of the last chunk that moved the total, never a blind 2^n - 1;
+ *   - a draw within rounding of a boundary of the cumulative distribution (about 2^(n-52) T) may land on either side of it, as for
+ *     qsim_sample, whose order of summation is another one;
+ *   - every result depends only on the state's bits and the draw: equal calls return equal bits whatever QSIM_OPT_GRID_CAP is (it caps
+ *     all three kernels), and the state's bits are untouched.  No atomics.
+ * The scratch — 8 bytes per chunk and per group, 0.2 % of an fp64 state — and 16 bytes per draw are allocated and freed by the call. */
+/* Host only, no device: the pyramid of a register of n qubits (0 to 40): *chunk_bits = min(8, n), *group_bits = min(18, n),
+ * *scratch_bytes = 8 (2^(n - cb) + 2^(n - gb)).  QSIM_ERR_ARG for n outside 0..40 or a NULL pointer. */
+int qsim_sample_geometry(int n, int *chunk_bits, int *group_bits, uint64_t *scratch_bytes);
+/* out[k] for draws[k] in [0, 1], k < shots: the basis index, or with num_qubits > 0 the outcome on `qubits` — bit j of out[k] is bit
+ * qubits[j] of the index.  Launches pending gates first (deferred X flips included), uploads the draws, runs the three kernels on
+ * qsim_stream(), copies the results back and waits.  shots == 0 is QSIM_OK and launches nothing.  QSIM_ERR_ARG, before any launch: a
+ * NULL pointer (qubits may be NULL with num_qubits == 0), shots < 0, a draw outside [0, 1] or NaN, more than 64 qubits, a qubit outside
+ * the register or listed twice.  QSIM_ERR_ARG also for a state whose total is 0 (or not finite): nothing is written to out then. */
+int qsim_sample_shots(qsim_state *s, const double *draws, long shots, const int *qubits, int num_qubits, uint64_t *out);
+/* For measurements (tools/sample_bench.py): runs the two preparing stages of qsim_sample_shots once on a pyramid of its own and reports
+ * what device events around them say, in milliseconds: the chunk-sum sweep, and the two launches of the prefix kernel.  Waits. */
+int qsim_sample_stage_times(qsim_state *s, double *chunk_sums_ms, double *prefix_ms);
+
 /* ---- measured pass geometry (planning, in the sense of FFTW's wisdom) -------------------------------------------------
  * A cache-blocked pass walks nine "high" index bits besides the contiguous low ones; which of them the lanes of a wave,
  * the waves of a workgroup and the registers of a lane walk changes nothing in the result and up to 2x in the pass's
