@@ -129,6 +129,11 @@ SIGNATURES = {
     "qsim_reduced_density_plan": (c_int, [POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64),
                                           POINTER(c_long)]),
     "qsim_density_sweeps_launched": (c_uint64, []),
+    "qsim_subsystem_density": (c_int, [c_void_p, POINTER(c_int), c_int, _DP]),
+    "qsim_subsystem_density_max_qubits": (c_int, []),
+    "qsim_subsystem_density_plan": (c_int, [POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_long),
+                                            POINTER(c_uint64), POINTER(c_uint64), POINTER(c_long)]),
+    "qsim_subsystem_sweeps_launched": (c_uint64, []),
     "qsim_apply_matrix": (c_int, [c_void_p, _DP, POINTER(c_int), c_int, POINTER(c_int), c_int]),
     "qsim_apply_matrix_max_qubits": (c_int, []),
     "qsim_apply_matrix_plan": (c_int, [POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64),

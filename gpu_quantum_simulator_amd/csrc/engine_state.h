@@ -16,6 +16,7 @@
 //   state_algebra.cpp  calls on several states: copy, inner product, linear combination (the host side of combine.hip)
 //   lanczos.cpp        the Lanczos ground-state solver on top of pauli.cpp's H application and the two above
 //   density.cpp        reduced density matrices of qubit subsets: the plan, the call, from tiles to rho (the host side of density.hip; density.h)
+//   subsystem.cpp      reduced density matrices of 6 to 10 qubits: the plan, the call, from blocks to rho (the host side of subsystem.hip; subsystem.h)
 //   matrix.cpp         dense matrices on up to five targets under controls: the plan, the operand, the call (the host side of matrix.hip; matrix.h)
 //   diagonal.cpp       whole-register diagonal operators from a table: the qsim_diagonal object, the plan, the set-up calls and the two sweeps (the host side of diagonal.hip; diagonal.h)
 //   sample.cpp         shots drawn on the device: the pyramid's geometry and the call (the host side of sample.hip; sample.h)

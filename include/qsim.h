@@ -354,7 +354,7 @@ int qsim_lanczos_plan(const uint64_t *ham_x, long num_ham, int max_steps, int wa
  * QSIM_ERR_ARG, nothing launched: a NULL state or output, qubits NULL with k > 0, k < 0, k above the maximum or above the register's
  * qubit count, a qubit outside the register, a repeated qubit.
  * Single states only, fp64 and fp32: there is NO cluster counterpart.  Out of scope: more than five qubits (the accumulators no
- * longer fit one wave) and any call that writes the state (collapse). */
+ * longer fit one wave; qsim_subsystem_density below takes six to ten) and any call that writes the state (collapse). */
 int qsim_reduced_density(qsim_state *s, const int *qubits, int k, double *out_re_im);
 int qsim_reduced_density_max_qubits(void);   /* 5 */
 /* Host only, no device: what the call above does on a register of num_q qubits held in precision_bits (64 or 32) — *path 1: the
@@ -366,6 +366,36 @@ int qsim_reduced_density_max_qubits(void);   /* 5 */
 int qsim_reduced_density_plan(const int *qubits, int k, int num_q, int precision_bits, int *path, int *padded_k, uint64_t *kernel_mask,
                               uint64_t *units_visited, long *trips_per_workgroup_at_grid_cap);
 uint64_t qsim_density_sweeps_launched(void); /* process-wide counter, as qsim_pauli_rotation_sweeps_launched */
+/* ---- reduced density matrices of up to ten qubits: R R^T in blocks and slices on the matrix cores (new) ----
+ * The same rho as qsim_reduced_density with the same conventions — bit j of a row/column index is qubit qubits[j], any order,
+ * distinct; not normalised, the trace is norm^2; the call settles the state first, leaves its bits alone and waits for its result; a
+ * shard that holds nothing gives zeros and launches nothing; QSIM_ERR_ARG for the same misuses — for k in [0, 10].  out: 4^k complex,
+ * row-major, (re, im): 16 MiB at k = 10.  k <= 5 is forwarded to qsim_reduced_density and returns its bits (and counts there).
+ * k >= 6: the real matrix R (row 2a = Re Psi[a], row 2a + 1 = Im Psi[a], a over the SORTED subset) has 2^(k+1) rows; G = R R^T is cut
+ * into square blocks of 128 rows, of which only the blocks (bi <= bj) are computed, and the 2^(n-k) environments into S slices of
+ * chunks of 32.  One workgroup takes one (block, slice): per chunk it stages the two row panels in LDS, widened to fp64, and its four
+ * waves accumulate a 64 x 64 quarter each with the fp64 matrix instruction (of a diagonal block, symmetric itself, only the 16 x 16
+ * tiles on and above its diagonal); it writes one partial block, and a final kernel adds the S partials of every element in ascending
+ * slice order.  No atomics.  Block size, S and the order depend on (n, k, precision, subset)
+ * alone — not on the device, QSIM_OPT_GRID_CAP or an occupancy query — so equal calls return equal bits on any device.  Products of
+ * fp32 amplitudes are exact and every sum is fp64.  The state is read `blocks` = 2^(k+1) / 128 times over all workgroups (once for
+ * k = 6, 16 times for k = 10); the caches take a part of that.  A register with fewer than four environments (n - k < 2) takes a plain
+ * kernel, one thread per element of rho.  The host builds rho from the blocks, fills the lower triangle from the upper one, makes the
+ * diagonal's imaginary parts exactly +0 and permutes rows and columns into the caller's order: Hermitian bit for bit.  Scratch (S
+ * partials of every upper block and the result, at most 1 GiB) is allocated per call before anything is launched.
+ * qsim_subsystem_sweeps_launched() counts the sweeps of k >= 6.  Single states only, fp64 and fp32: there is NO cluster counterpart.
+ * Out of scope: more than ten qubits — beyond that the 4^k result and its diagonalisation on the host dominate the call. */
+int qsim_subsystem_density(qsim_state *s, const int *qubits, int k, double *out_re_im);
+int qsim_subsystem_density_max_qubits(void); /* 10 */
+/* Host only, no device: what the call above does on a register of num_q qubits held in precision_bits (64 or 32) — *path 1: blocks
+ * and slices, 0: the plain kernel, 2: forwarded to qsim_reduced_density (k <= 5; qsim_reduced_density_plan says what that does, the
+ * fields below are 0 but for *units_read, one state volume); *block_rows: rows of R in a block (128); *upper_blocks: blocks computed;
+ * *slices: S; *units_read: 16-byte units (one fp64 amplitude, two fp32 amplitudes) loaded by all workgroups together — the traffic
+ * model, state volumes times the units of the state; *scratch_bytes: device scratch of the call; *trips_per_workgroup: chunks of 32
+ * environments a workgroup walks (path 0: 1).  QSIM_ERR_ARG as for qsim_reduced_density_plan, with k up to 10. */
+int qsim_subsystem_density_plan(const int *qubits, int k, int num_q, int precision_bits, int *path, int *block_rows, long *upper_blocks,
+                                long *slices, uint64_t *units_read, uint64_t *scratch_bytes, long *trips_per_workgroup);
+uint64_t qsim_subsystem_sweeps_launched(void); /* process-wide counter, as qsim_density_sweeps_launched */
 /* ---- dense matrices on up to five target qubits, under controls, one in-place sweep (new) ----
  * psi <- (1 - Pi) psi + Pi (U on targets) psi, Pi = the projector on "every control qubit is 1".
  * U: 2^k x 2^k, row-major, (re, im) doubles; bit j of a row/column index is targets[j] (targets[0] = LSB, any order, as
