@@ -141,6 +141,13 @@ SIGNATURES = {
     "qsim_apply_matrix_operand": (c_int, [_DP, POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, _DP, POINTER(c_int), POINTER(c_int),
                                           POINTER(c_int)]),
     "qsim_matrix_sweeps_launched": (c_uint64, []),
+    "qsim_apply_permutation": (c_int, [c_void_p, POINTER(ctypes.c_uint32), POINTER(c_int), c_int, POINTER(c_int), c_int]),
+    "qsim_apply_permutation_max_qubits": (c_int, []),
+    "qsim_apply_permutation_plan": (c_int, [POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_uint64),
+                                            POINTER(c_uint64), POINTER(c_uint64), POINTER(c_long)]),
+    "qsim_apply_permutation_operand": (c_int, [POINTER(ctypes.c_uint32), POINTER(c_int), c_int, POINTER(c_int), c_int, c_int, c_int,
+                                               POINTER(ctypes.c_uint16), POINTER(c_int)]),
+    "qsim_permutation_sweeps_launched": (c_uint64, []),
     "qsim_diagonal_create": (c_int, [POINTER(c_void_p), c_int, c_int]),
     "qsim_diagonal_create_external": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p]),
     "qsim_diagonal_destroy": (None, [c_void_p]),

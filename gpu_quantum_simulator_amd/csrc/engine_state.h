@@ -252,6 +252,9 @@ int alloc_sweep_scratch(qsim_state *s);
 double *sweep_partials(qsim_state *s);      // kExpectPartialDoubles: what a reducing sweep takes as d_partial
 double *sweep_result_row(qsim_state *s);    // the first of kResultRowBatch rows of kResultRowSlots sums: where a call of one sweep has it leave them
 double *sweep_coef_staging(qsim_state *s);  // kMatrixCoefDoubles: the operand of qsim_apply_matrix (the definition says where it lies)
+// matrix.cpp: `bytes` (at most kMatrixCoefDoubles doubles) through a pinned ring to sweep_coef_staging(s), ordered on the state's
+// stream in front of the sweep that reads them; the operand of qsim_apply_matrix and of qsim_apply_permutation
+int stage_sweep_operand(qsim_state *s, const void *data, size_t bytes);
 // out[0..count) = the first `count` sums of the first result row; waits for the state's stream
 int fetch_sweep_results(qsim_state *s, int count, double *out);
 

@@ -128,6 +128,7 @@ extern "C" int qsim_apply_matrix_operand(const double *U, const int *targets, in
 // ---- the way of the coefficients to the device --------------------------------------------------------------------------------------
 // A ring of pinned slots per device.  A slot is free again when the copy out of it has run (its event), so a call waits only when
 // kSlots calls of one device are still queued; the copy itself is ordered on the state's stream, in front of the sweep.
+// qsim_apply_permutation (permutation.cpp) sends its destination map the same way.
 namespace {
 constexpr int kSlots = 16;
 struct Ring {
@@ -140,7 +141,8 @@ std::mutex g_ring_mutex;
 std::map<int, Ring> g_rings;
 } // namespace
 
-static int stage_coefficients(qsim_state *s, const std::vector<double> &coef) {
+int qsim::stage_sweep_operand(qsim_state *s, const void *data, size_t bytes) {
+    if (bytes > kMatrixCoefDoubles * sizeof(double)) return fail(QSIM_ERR_ARG, "stage_sweep_operand: %zu bytes do not fit a slot", bytes);
     QSIM_TRY(alloc_sweep_scratch(s)); // stream-ordered scratch of the state's own
     std::lock_guard<std::mutex> lock(g_ring_mutex);
     Ring &ring = g_rings[s->device];
@@ -152,8 +154,8 @@ static int stage_coefficients(qsim_state *s, const std::vector<double> &coef) {
     ring.next = (slot + 1) % kSlots;
     if (ring.used[slot]) HIP_TRY(hipEventSynchronize(ring.done[slot]));
     double *h = ring.host + (size_t)slot * kMatrixCoefDoubles;
-    std::memcpy(h, coef.data(), coef.size() * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(sweep_coef_staging(s), h, coef.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    std::memcpy(h, data, bytes);
+    HIP_TRY(hipMemcpyAsync(sweep_coef_staging(s), h, bytes, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipEventRecord(ring.done[slot], s->stream));
     ring.used[slot] = true;
     return QSIM_OK;
@@ -184,7 +186,7 @@ extern "C" int qsim_apply_matrix(qsim_state *s, const double *U, const int *targ
     } else {
         coef.assign(U, U + ((size_t)2 << (2 * k)));
     }
-    QSIM_TRY(stage_coefficients(s, coef));
+    QSIM_TRY(stage_sweep_operand(s, coef.data(), coef.size() * sizeof(double)));
     const LaunchCfg cfg{s->stream, s->grid_cap};
     QSIM_TRY(launched("qsim_apply_matrix:", launch_matrix(cfg, s->amps, p, sweep_coef_staging(s))));
     g_matrix_sweeps++;

@@ -5,7 +5,8 @@
 // plan fields and probe outputs both plans have, the relation between the caller's qubit order and the sorted subset, the
 // dispatch on the subset's size, and the three device helpers both kernels use.
 // subsystem.{h,hip,cpp} (rho of 6 to 10 qubits in blocks and slices) borrows the list check, SubsetOrder and f64x4 and
-// pads nothing.
+// pads nothing; permutation.{h,hip,cpp} (a table on up to 10 qubits under controls) borrows the list check, pad_subset,
+// SubsetOrder and deposit.
 // NOT shared, on purpose: the kernel bodies and their shape constants (density.h, matrix.h).  The walks differ — 4 against 16
 // environment units per step, g.ones, the row formula — and a shared trip loop or address table would change their instructions.
 #ifndef QSIM_SUBSET_SWEEP_H

@@ -12,7 +12,7 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, permutations
 from ._lib import QsimStats, check
 
 
@@ -637,6 +637,42 @@ class Simulator(_PauliStrings):
             raise ValueError(f"apply_matrix: at most 5 targets and a matrix of shape (2^k, 2^k); got {len(ts)} targets and shape {m.shape}")
         flat = np.ascontiguousarray(m.reshape(-1)).view(np.float64)
         check(_lib.load().qsim_apply_matrix(self._h, _dp(flat), (c_int * max(len(ts), 1))(*ts), len(ts), (c_int * max(len(cs), 1))(*cs), len(cs)))
+
+    # -- permutations of the basis states of up to ten qubits (single states only: a Cluster has no counterpart)
+    def apply_permutation(self, perm, targets, controls=(), inverse: bool = False) -> None:
+        """Basis state j of `targets` (at most 10, distinct, any order; bit i of j is targets[i]) goes to basis state perm[j] where
+        every qubit of `controls` (any number, disjoint from the targets) is 1; nothing is read or written elsewhere.  `perm` is a
+        bijection of range(2**k); inverse=True applies permutations.inverse_table(perm).  Amplitudes are moved bit for bit, fp64 and
+        fp32: apply_matrix with U[perm[j], j] = 1 without the arithmetic.  One in-place sweep of 2^-len(controls) of the state
+        (qsim_apply_permutation), launched after the queued gates and not waited for; it does not pass through the gate queue.
+        ValueError, before the library is called: a table of the wrong length, a non-integer entry, not a bijection."""
+        ts, cs = [int(q) for q in targets], [int(q) for q in controls]
+        if len(ts) > permutations.MAX_QUBITS:
+            raise ValueError(f"apply_permutation: at most {permutations.MAX_QUBITS} targets, got {len(ts)}")
+        table = permutations.as_table(perm, len(ts))
+        if inverse:
+            table = permutations.inverse_table(table)
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        check(_lib.load().qsim_apply_permutation(self._h, table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), (c_int * max(len(ts), 1))(*ts), len(ts),
+                                                 (c_int * max(len(cs), 1))(*cs), len(cs)))
+
+    def apply_function_xor(self, values, inputs, outputs, controls=()) -> None:
+        """|x>|y> -> |x>|y ^ values[x]>: bit i of x is inputs[i], bit i of y is outputs[i]; a bit oracle for any function of up to
+        10 - len(outputs) bits (permutations.xor_function_table)."""
+        ins, outs = [int(q) for q in inputs], [int(q) for q in outputs]
+        self.apply_permutation(permutations.xor_function_table(values, len(ins), len(outs)), ins + outs, controls)
+
+    def apply_modular_add(self, a: int, modulus: int, targets, controls=()) -> None:
+        """x -> (x + a) mod `modulus` on the register `targets` (bit i of x is targets[i]), the identity on x >= modulus
+        (permutations.modular_add_table)."""
+        ts = [int(q) for q in targets]
+        self.apply_permutation(permutations.modular_add_table(a, modulus, len(ts)), ts, controls)
+
+    def apply_modular_multiply(self, a: int, modulus: int, targets, controls=()) -> None:
+        """x -> a x mod `modulus` on the register `targets`, the identity on x >= modulus; gcd(a, modulus) = 1
+        (permutations.modular_multiply_table).  Under one control per counting qubit: the modular exponentiation of order finding."""
+        ts = [int(q) for q in targets]
+        self.apply_permutation(permutations.modular_multiply_table(a, modulus, len(ts)), ts, controls)
 
     # -- whole-register diagonal operators from a table (single states only: a Cluster has no counterpart)
     def apply_diagonal_phase(self, diag: Diagonal, gamma: float) -> None:

@@ -434,6 +434,43 @@ int qsim_apply_matrix_plan(const int *targets, int k, const int *controls, int n
 int qsim_apply_matrix_operand(const double *U, const int *targets, int k, const int *controls, int num_controls, int num_q,
                               int precision_bits, double *M, int *row_amp, int *row_part, int *rows);
 uint64_t qsim_matrix_sweeps_launched(void);  /* process-wide counter, as qsim_density_sweeps_launched */
+/* ---- permutations of the basis states of up to ten target qubits, under controls, one in-place sweep (new) ----
+ * A classical reversible function on a register: for every environment e (the index bits outside the targets) in which every control
+ * qubit is 1,  new[e | dep(perm[j])] = old[e | dep(j)],  dep putting bit i of its argument on qubit targets[i].  It is qsim_apply_matrix
+ * with U[perm[j]][j] = 1 without the arithmetic: amplitudes are moved bit for bit, in fp64 and in fp32, and nothing is rounded.
+ * perm: 2^k entries, a bijection of [0, 2^k); bit i of an entry and of its position is targets[i] (targets[0] = LSB, any order).  k in
+ * [0, 10] (qsim_apply_permutation_max_qubits); k == 0 takes the table {0}.  controls: any number of qubits, disjoint from the targets.
+ * The call settles the state first (queued gates are launched, a lazily held |0...0> is written out), sends the operand through a
+ * pinned ring to the state's sweep scratch, launches ONE sweep on the state's stream that reads and writes 2^-c of the state once, and
+ * returns without waiting.  It does not go through the gate queue or the fusion scheduler.  The identity table is swept like any other.
+ * The sweep works tile by tile: a tile is B index bits — the targets and the lowest index bits that are neither targets nor controls,
+ * B = min(12, n - c) for fp64 and min(13, n - c) for fp32, 64 KiB of amplitudes at most.  A workgroup loads a tile with coalesced loads,
+ * writes each amplitude into shared memory at its destination, and stores the tile back linearly to the addresses it loaded; a tile
+ * holds every target, so it is closed under the map and the sweep needs no second buffer.  Each amplitude is written by one thread:
+ * equal calls give equal bits whatever QSIM_OPT_GRID_CAP is.  Amplitudes outside the control subspace are neither read nor written.
+ * Sweeps are NOT counted in the qsim_stats record; qsim_permutation_sweeps_launched counts them, one per accepted call.  A shard that
+ * holds nothing (qsim_holds_nothing) stays as it is and launches no sweep.
+ * QSIM_ERR_ARG, nothing launched and the state untouched: a NULL state or table, targets NULL with k > 0, controls NULL with
+ * num_controls > 0, a negative count, k above the maximum or above the register's qubit count, a qubit outside the register, a repeated
+ * qubit, a control among the targets, an entry of the table >= 2^k, two equal entries.
+ * Single states only, fp64 and fp32: there is NO cluster counterpart.  Out of scope: phases on the moved amplitudes (a monomial
+ * matrix; its table would follow the map in the scratch), gradients through these calls. */
+int qsim_apply_permutation(qsim_state *s, const uint32_t *perm, const int *targets, int k, const int *controls, int num_controls);
+int qsim_apply_permutation_max_qubits(void); /* 10 */
+/* Host only, no device: what the call above does on a register of num_q qubits held in precision_bits (64 or 32) — *path 1: whole
+ * tiles of 12 (fp64) or 13 (fp32) bits; 0: n - c is smaller, the one tile is the whole control subspace and one workgroup runs the
+ * same kernel with runtime bounds; *tile_bits: B; *tile_mask: the tile's index bits; *tiles: 2^(n - c - B); *units: the 16-byte units
+ * read and written once (fp64: 2^(n - c); fp32: half as many, an amplitude being 8 bytes; never below 1); *trips_per_workgroup: the
+ * tiles a workgroup walks at the default grid's cap of 512 workgroups (a device that holds fewer at once makes more).  QSIM_ERR_ARG as
+ * above, and for num_q outside [0, 40], precision_bits other than 64 or 32, a NULL result pointer. */
+int qsim_apply_permutation_plan(const int *targets, int k, const int *controls, int num_controls, int num_q, int precision_bits, int *path,
+                                int *tile_bits, uint64_t *tile_mask, uint64_t *tiles, uint64_t *units, long *trips_per_workgroup);
+/* Host only: exactly the array the device is handed for this call — local_map[u] for every tile-local index u in [0, *entries),
+ * *entries = 2^B (room for 8192 is enough): bit i of u is the i-th lowest bit of tile_mask; the target bits of u go through perm (the
+ * caller's order against the sorted one), the padding bits are kept.  QSIM_ERR_ARG as above. */
+int qsim_apply_permutation_operand(const uint32_t *perm, const int *targets, int k, const int *controls, int num_controls, int num_q,
+                                   int precision_bits, uint16_t *local_map, int *entries);
+uint64_t qsim_permutation_sweeps_launched(void); /* process-wide counter, as qsim_density_sweeps_launched */
 /* ---- whole-register diagonal operators from a table: exp(-i gamma D) and <D>, <D^2> in one sweep each (new) ----
  * A qsim_diagonal is a real table d[0..2^n) of fp64 on one device, the operator D = sum_i d_i |i><i| on a register of n qubits: a
  * cost function of QAOA, a penalty, a marked set, a potential on a grid — whatever the number of Pauli terms it would take.  The
