@@ -14,6 +14,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 #include "diagonal.h"
 #include "engine_state.h"
@@ -30,6 +32,10 @@ struct qsim_diagonal {
     struct Reader { hipStream_t stream; hipEvent_t done; bool pending; };
     std::vector<Reader> readers;  // the streams whose sweeps have read the table, and the event behind the last one of each
 };
+
+// The tables alive, so that a state that goes can tell them (forget_diagonal_reads): a table may outlive the states that swept it.
+static std::mutex g_live_mutex;
+static std::vector<qsim_diagonal *> g_live;
 
 static int use_device(const char *who, int device) {
     int ndev = 0;
@@ -66,6 +72,10 @@ static int make_diagonal(const char *who, qsim_diagonal **out, int num_q, int de
         qsim_diagonal_destroy(d);
         return code;
     }
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        g_live.push_back(d);
+    }
     *out = d;
     return QSIM_OK;
 }
@@ -89,6 +99,10 @@ static hipError_t wait_for_readers(qsim_diagonal *d) {
 
 extern "C" void qsim_diagonal_destroy(qsim_diagonal *d) {
     if (!d) return;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        g_live.erase(std::remove(g_live.begin(), g_live.end(), d), g_live.end());
+    }
     (void)hipSetDevice(d->device);
     (void)wait_for_readers(d);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
@@ -217,6 +231,15 @@ int qsim::mark_read(const qsim_state *s, const qsim_diagonal *cd) {
     HIP_TRY(hipEventRecord(r->done, s->stream));
     r->pending = true;
     return QSIM_OK;
+}
+
+// The state's stream has been waited for and is about to be destroyed: its sweeps have read what they read, and their events, last
+// recorded on that stream, are not to be waited for any more (engine_state.h).
+void qsim::forget_diagonal_reads(const qsim_state *s) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    for (qsim_diagonal *d : g_live)
+        for (auto &r : d->readers)
+            if (r.stream == s->stream) r.pending = false;
 }
 
 extern "C" int qsim_apply_diagonal_phase(qsim_state *s, const qsim_diagonal *d, double gamma) {

@@ -113,7 +113,6 @@ static int make_state(qsim_state **out, int num_q, int device, void *ext, bool f
     }
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_ops, kOpsCap * sizeof(TileOp));
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_ops, kOpsCap * sizeof(TileOp), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_scalar, 64);
     if (e != hipSuccess) {
         const int code = fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE,
                               "Malloc error: %s (state needs %zu bytes)", hipGetErrorString(e), bytes);
@@ -145,6 +144,8 @@ extern "C" void qsim_destroy(qsim_state *s) {
     if (s->alloc_thread.joinable()) s->alloc_thread.join();
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
+    forget_staged_operands(s); // what outlives the state lets go of the events it recorded on this stream
+    forget_diagonal_reads(s);
     for (auto &pe : s->events) { (void)hipEventDestroy(pe.start); (void)hipEventDestroy(pe.stop); }
     for (auto ev : s->event_pool) (void)hipEventDestroy(ev);
     for (CachedPlan &pl : s->plans)
@@ -153,7 +154,6 @@ extern "C" void qsim_destroy(qsim_state *s) {
     if (s->owns_spare && s->spare) (void)hipFree(s->spare);
     if (s->d_ops) (void)hipFree(s->d_ops);
     if (s->h_ops) (void)hipHostFree(s->h_ops);
-    if (s->d_scalar) (void)hipFree(s->d_scalar);
     if (s->d_expect) (void)hipFree(s->d_expect);
     if (s->d_adjoint) (void)hipFree(s->d_adjoint);
     if (s->stream) (void)hipStreamDestroy(s->stream);

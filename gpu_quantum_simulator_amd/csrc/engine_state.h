@@ -139,7 +139,6 @@ struct qsim_state {
     // op ring for tile passes
     qsim::TileOp *d_ops = nullptr, *h_ops = nullptr;
     size_t ops_cap = 0, ops_used = 0;
-    double *d_scalar = nullptr;
     double *d_expect = nullptr; // the sweep scratch: partial sums of a sweep, then the results of a batch of sweeps (alloc_sweep_scratch and the accessors below)
     void *d_adjoint = nullptr;  // qsim_pauli_gradient: lambda's 2^n amplitudes for a state without a spare buffer; allocated on first use, the state's own
     // stats
@@ -255,6 +254,11 @@ double *sweep_coef_staging(qsim_state *s);  // kMatrixCoefDoubles: the operand o
 // matrix.cpp: `bytes` (at most kMatrixCoefDoubles doubles) through a pinned ring to sweep_coef_staging(s), ordered on the state's
 // stream in front of the sweep that reads them; the operand of qsim_apply_matrix and of qsim_apply_permutation
 int stage_sweep_operand(qsim_state *s, const void *data, size_t bytes);
+// What qsim_destroy calls once it has waited for s->stream, before the stream goes.  The ring (matrix.cpp) and a table (diagonal.cpp)
+// outlive a state and keep events last recorded on its stream; hipEventSynchronize looks at that stream, so an event must not be
+// waited for after the stream died.  Everything on the stream has run by now: the slots are free and the reads are over.
+void forget_staged_operands(const qsim_state *s);
+void forget_diagonal_reads(const qsim_state *s);
 // out[0..count) = the first `count` sums of the first result row; waits for the state's stream
 int fetch_sweep_results(qsim_state *s, int count, double *out);
 

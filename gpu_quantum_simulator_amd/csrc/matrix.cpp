@@ -134,6 +134,7 @@ constexpr int kSlots = 16;
 struct Ring {
     double *host = nullptr;
     hipEvent_t done[kSlots] = {};
+    hipStream_t on[kSlots] = {}; // the stream `done` was last recorded on
     bool used[kSlots] = {};
     int next = 0;
 };
@@ -157,8 +158,17 @@ int qsim::stage_sweep_operand(qsim_state *s, const void *data, size_t bytes) {
     std::memcpy(h, data, bytes);
     HIP_TRY(hipMemcpyAsync(sweep_coef_staging(s), h, bytes, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipEventRecord(ring.done[slot], s->stream));
+    ring.on[slot] = s->stream;
     ring.used[slot] = true;
     return QSIM_OK;
+}
+
+void qsim::forget_staged_operands(const qsim_state *s) {
+    std::lock_guard<std::mutex> lock(g_ring_mutex);
+    const auto it = g_rings.find(s->device);
+    if (it == g_rings.end()) return;
+    for (int i = 0; i < kSlots; i++)
+        if (it->second.on[i] == s->stream) it->second.used[i] = false;
 }
 
 // ---- the call ---------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "engine_state.h"
+#include "pauli_sweep.h"
 
 using namespace qsim;
 
@@ -64,12 +65,15 @@ extern "C" int qsim_write(qsim_state *s, uint64_t first, uint64_t count, const d
 extern "C" int qsim_norm2(qsim_state *s, double *out) {
     if (!s || !out) return fail(QSIM_ERR_ARG, "NULL argument");
     QSIM_TRY(settle(s));
-    HIP_TRY(hipMemsetAsync(s->d_scalar, 0, 8, s->stream));
-    LaunchCfg cfg{s->stream, s->grid_cap};
-    HIP_TRY(launch_norm2(cfg, s->amps, s->f32, s->n, s->d_scalar));
-    HIP_TRY(hipMemcpyAsync(out, s->d_scalar, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return QSIM_OK;
+    QSIM_TRY(alloc_sweep_scratch(s));
+    // The expectation value of the identity string (x = z = 0), as qsim_lanczos_ground takes its start vector's norm: one read-only
+    // sweep whose partial sums are added in a fixed order, so equal calls on equal bits return equal bits.  (The sums of k_norm2 met
+    // in one atomicAdd, in whatever order the workgroups finished: a lazily held state and its dense copy differed in the last bit.)
+    ExpectSweep sw{};
+    sw.count = 1;
+    const LaunchCfg cfg{s->stream, s->grid_cap};
+    QSIM_TRY(launched("norm sweep", launch_expect(cfg, s->amps, s->amps, s->f32, s->n, sw, sweep_partials(s), sweep_result_row(s))));
+    return fetch_sweep_results(s, 1, out);
 }
 
 // ---- measurement post-path ----------------------------------------------------------------------------------

@@ -1,5 +1,9 @@
 // readout_kernels.inc — reductions and gathers that read a state for the host: norm, block probabilities, one masked block.
 
+// k_norm2 has no caller any more: its workgroups' sums meet in one atomicAdd, in whatever order they finish, so equal calls could
+// differ in the last bit, and qsim_norm2 (readout.cpp) is now the identity string's expectation sweep, which adds in a fixed order.
+// The kernel stays because the code layout of this translation unit is part of what the benchmark measures (DESIGN §3): it leaves
+// with the next change that re-measures k_tile.
 __global__ __launch_bounds__(TPB) void k_norm2(const amp_t *__restrict__ v, uint64_t N, double *out) {
     double acc = 0.0;
     const uint64_t stride = (uint64_t)gridDim.x * TPB;

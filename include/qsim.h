@@ -166,7 +166,8 @@ int qsim_deferred_flip_stats(const qsim_state *s, uint64_t *applied, uint64_t *f
 /* ---- amplitudes in / out (the reference's final cudaMemcpy D2H, quantum_simulator_naive.cu:193-194) -- */
 int qsim_read(qsim_state *s, uint64_t first, uint64_t count, double *out_re_im);
 int qsim_write(qsim_state *s, uint64_t first, uint64_t count, const double *in_re_im);
-int qsim_norm2(qsim_state *s, double *out); /* sum |a|^2 computed on the device */
+int qsim_norm2(qsim_state *s, double *out); /* sum |a|^2 computed on the device: the identity string of qsim_expect_paulis below, one
+                                             * read-only sweep, fp64 sums in a fixed order (equal calls return equal bits) */
 /* ---- expectation values of Pauli strings, computed on the device (new: the reference has no observables) ----
  * A string on the register is two masks: bit q of x_mask set where it has X or Y on qubit q, bit q of z_mask where it has Z or Y
  * (both: Y).  out[t] = <psi|P_t|psi>, a real number, for num_terms strings; coefficients of a Hamiltonian are the caller's.

@@ -398,3 +398,22 @@ def test_refusals_leave_the_state_alone(precision):
         with pytest.raises(ValueError):
             diag.add_terms([(1.0, f"Z{n}")])
     assert not hasattr(Cluster, "apply_diagonal_phase") and not hasattr(Cluster, "expectation_diagonal")
+
+
+def test_a_table_outlives_the_states_that_swept_it():
+    """The event behind a sweep that read a table is recorded on the STATE's stream, and the table's set-up calls wait for it.  A state
+    that goes takes its stream along, so it tells the tables first (qsim_destroy): add_terms after the state is gone waits for nothing
+    that is gone, and the table is the exact sequential sum — every coefficient is a dyadic fraction."""
+    n = 10
+    j = np.arange(1 << n)
+    sign = lambda *qs: 1.0 - 2.0 * (sum((j >> q) & 1 for q in qs) & 1)
+    with Diagonal.from_terms(n, [(0.5, "Z0 Z3"), (-0.25, "Z9")]) as diag:
+        rounds = 0
+        for precision in PRECISIONS:
+            for _ in range(20):
+                with Simulator(n, precision=precision) as sim:
+                    sim.apply_diagonal_phase(diag, GAMMA)
+                    sim.expectation_diagonal(diag)
+                diag.add_terms([(0.125, "Z1")])  # waits for every sweep that still reads the table
+                rounds += 1
+        assert np.array_equal(diag.read(), 0.5 * sign(0, 3) - 0.25 * sign(9) + 0.125 * rounds * sign(1))

@@ -449,3 +449,23 @@ def test_refusals(precision):
         assert _sweeps() == before + 4
     with Simulator(2, precision=precision) as sim:
         assert lib.qsim_apply_matrix(sim._h, up, _ints([0, 1, 1]), 3, None, 0) == _lib.ERR_ARG  # k > n
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_the_operand_ring_outlives_the_states_it_served(precision):
+    """The operand travels through a ring of pinned slots that belongs to the device, not to a state; a slot's event is recorded on the
+    state's stream.  Forty states come and go, more than twice around the ring: a slot that a state used is free when the state has
+    gone, and is not waited for on the stream that went with it (qsim_destroy tells the ring)."""
+    n, targets, controls = 9, (7, 0, 4), (2,)
+    rng = np.random.default_rng(90)
+    first = None
+    for i in range(40):
+        U = _contraction(8, rng)
+        sim, before = _sim_with(n, precision, 90)
+        with sim:
+            got = _apply_and_check(sim, before, U, targets, controls, f"ring, state {i}")
+            first = first or (U, got)
+    sim, before = _sim_with(n, precision, 90)  # the first state's call again, on the forty-first: the same bits
+    with sim:
+        sim.apply_matrix(first[0], targets, controls)
+        assert np.array_equal(sim.read().view(np.uint64), first[1].view(np.uint64))
