@@ -267,6 +267,14 @@ SIGNATURES = {
 }
 # include/qsim_legacy.h
 LEGACY_SYMBOLS = ("compute_state_vector", "execute_single_qubit_gate", "execute_cnot")
+# every symbol include/qsim_qft.h declares (the header says why it is a file of its own)
+QFT_SIGNATURES = {
+    "qsim_apply_qft": (c_int, [c_void_p, POINTER(c_int), c_int, c_int, c_int]),
+    "qsim_apply_qft_max_digit_bits": (c_int, []),
+    "qsim_apply_qft_plan": (c_int, [POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_uint64),
+                                    POINTER(c_uint64), POINTER(c_uint64), POINTER(c_long)]),
+    "qsim_qft_sweeps_launched": (c_uint64, []),
+}
 
 _lib = None
 
@@ -297,7 +305,7 @@ def load() -> ctypes.CDLL:
                 pass
         # QSIM_LIB: another build of the same library (A/B runs of kernel variants from tools/); never a different backend
         lib = ctypes.CDLL(os.environ.get("QSIM_LIB") or LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **QFT_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError here = header and library disagree
             fn.restype = res
             fn.argtypes = args

@@ -20,6 +20,7 @@
 //   matrix.cpp         dense matrices on up to five targets under controls: the plan, the operand, the call (the host side of matrix.hip; matrix.h)
 //   diagonal.cpp       whole-register diagonal operators from a table: the qsim_diagonal object, the plan, the set-up calls and the two sweeps (the host side of diagonal.hip; diagonal.h)
 //   sample.cpp         shots drawn on the device: the pyramid's geometry and the call (the host side of sample.hip; sample.h)
+//   qft.cpp            the quantum Fourier transform on any qubits: the plan, the per-pass record, the call (the host side of qft.hip; qft.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 
@@ -259,6 +260,9 @@ int stage_sweep_operand(qsim_state *s, const void *data, size_t bytes);
 // waited for after the stream died.  Everything on the stream has run by now: the slots are free and the reads are over.
 void forget_staged_operands(const qsim_state *s);
 void forget_diagonal_reads(const qsim_state *s);
+// pauli.cpp: a second buffer of 2^n amplitudes for a call outside a flush (a gradient's lambda, a Fourier transform's moving passes):
+// the idle spare buffer, else d_adjoint, allocated on first use.  QSIM_ERR_ALLOC when it cannot be had; nothing is touched then.
+int second_buffer(qsim_state *s, void **out);
 // out[0..count) = the first `count` sums of the first result row; waits for the state's stream
 int fetch_sweep_results(qsim_state *s, int count, double *out);
 

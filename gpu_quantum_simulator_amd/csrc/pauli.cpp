@@ -62,6 +62,19 @@ double *qsim::sweep_result_row(qsim_state *s) { return s->d_expect + kExpectPart
 static_assert(kMatrixCoefDoubles <= kExpectPartialDoubles, "the largest matrix operand fits in the partial-sum region");
 double *qsim::sweep_coef_staging(qsim_state *s) { return sweep_partials(s); }
 
+// ---- a second buffer of the state's size, outside a flush --------------------------------------------------------------------------
+// lambda of a gradient call, the other side of a Fourier transform's moving passes: the spare buffer, which is idle outside a flush,
+// else d_adjoint, allocated on first use and the state's own from then on.  Call it before the state is touched.
+int qsim::second_buffer(qsim_state *s, void **out) {
+    void *buf = s->spare && s->spare != s->amps ? s->spare : s->d_adjoint;
+    if (!buf) {
+        HIP_TRY(hipMalloc(&buf, s->amp_bytes() << s->n));
+        s->d_adjoint = buf;
+    }
+    *out = buf;
+    return QSIM_OK;
+}
+
 int qsim::fetch_sweep_results(qsim_state *s, int count, double *out) {
     HIP_TRY(hipMemcpyAsync(out, sweep_result_row(s), (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -461,11 +474,8 @@ static int gradient(qsim_state *s, const uint64_t *C, const uint64_t *rot_x, con
     QSIM_TRY(await_buffer(s));
     HIP_TRY(hipSetDevice(s->device));
     // everything that can fail for want of memory comes before the state is touched
-    void *lam = s->spare && s->spare != s->amps ? s->spare : s->d_adjoint; // the spare buffer is idle outside a flush
-    if (!lam) {
-        HIP_TRY(hipMalloc(&lam, s->amp_bytes() << s->n));
-        s->d_adjoint = lam;
-    }
+    void *lam = nullptr;
+    QSIM_TRY(second_buffer(s, &lam));
     QSIM_TRY(alloc_sweep_scratch(s));
     const LaunchCfg cfg{s->stream, s->grid_cap};
 

@@ -674,6 +674,17 @@ class Simulator(_PauliStrings):
         ts = [int(q) for q in targets]
         self.apply_permutation(permutations.modular_multiply_table(a, modulus, len(ts)), ts, controls)
 
+    # -- the quantum Fourier transform on any qubits (single states only: a Cluster has no counterpart)
+    def apply_qft(self, qubits, inverse: bool = False, *, max_digit_bits: int = 0) -> None:
+        """The quantum Fourier transform on the register `qubits` (any number up to the whole state, distinct, any order and places;
+        bit j of the register value is qubits[j]): new[y] = 2^(-k/2) sum_x exp(+2 pi i x y / 2^k) old[x] for every setting of the other
+        qubits, exp(-...) with inverse=True; in numpy terms forwards is ifft * sqrt(2^k) along the register axis.  The output is in
+        natural order (the textbook circuit with its final swaps).  One sweep per digit of at most ten qubits (qsim_apply_qft),
+        launched after the queued gates and not waited for; it does not pass through the gate queue.  max_digit_bits (1 ... 10) caps
+        the digits, for tests and tuning; 0 leaves the choice to the plan.  An empty register is accepted and does nothing."""
+        qs = [int(q) for q in qubits]
+        check(_lib.load().qsim_apply_qft(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), 1 if inverse else 0, int(max_digit_bits)))
+
     # -- whole-register diagonal operators from a table (single states only: a Cluster has no counterpart)
     def apply_diagonal_phase(self, diag: Diagonal, gamma: float) -> None:
         """a_i <- exp(-i gamma d_i) a_i for the table of `diag`: one in-place sweep (qsim_apply_diagonal_phase), launched after

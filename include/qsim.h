@@ -963,4 +963,5 @@ int qsim_tile_records(const qsim_circuit *c, int fuse, int tile_bits, int tile_l
 #ifdef __cplusplus
 }
 #endif
+#include "qsim_qft.h"
 #endif /* QSIM_H */
