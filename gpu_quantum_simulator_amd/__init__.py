@@ -8,8 +8,9 @@ importing it never loads anything from oracle/.
 from . import circuits  # noqa: F401  (pure Python, no native code)
 from .pauli import pauli_masks, trotter_rotations  # noqa: F401  (pure Python too)
 from . import permutations  # noqa: F401  (pure numpy: tables for Simulator.apply_permutation)
+from . import channels  # noqa: F401  (pure numpy: Kraus lists for Simulator.apply_channel)
 
-__all__ = ["circuits", "pauli_masks", "trotter_rotations", "permutations", "Simulator", "Circuit", "Cluster", "Diagonal", "run_qasm", "gate_matrix", "ShardPlanHandle", "RankComm"]
+__all__ = ["circuits", "pauli_masks", "trotter_rotations", "permutations", "channels", "Simulator", "Circuit", "Cluster", "Diagonal", "run_qasm", "gate_matrix", "ShardPlanHandle", "RankComm"]
 
 
 def __getattr__(name):  # lazy: `import gpu_quantum_simulator_amd.circuits` must work before the library is built

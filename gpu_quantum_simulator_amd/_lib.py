@@ -275,6 +275,13 @@ QFT_SIGNATURES = {
                                     POINTER(c_uint64), POINTER(c_uint64), POINTER(c_long)]),
     "qsim_qft_sweeps_launched": (c_uint64, []),
 }
+# every symbol include/qsim_measure.h declares (the header says why it is a file of its own)
+MEASURE_SIGNATURES = {
+    "qsim_postselect": (c_int, [c_void_p, POINTER(c_int), c_int, c_uint64, _DP]),
+    "qsim_measure": (c_int, [c_void_p, POINTER(c_int), c_int, c_double, POINTER(c_uint64), _DP]),
+    "qsim_collapse_plan": (c_int, [POINTER(c_int), c_int, c_uint64, c_int, c_int, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_long), POINTER(c_long)]),
+    "qsim_collapse_sweeps_launched": (c_uint64, []),
+}
 
 _lib = None
 
@@ -305,7 +312,7 @@ def load() -> ctypes.CDLL:
                 pass
         # QSIM_LIB: another build of the same library (A/B runs of kernel variants from tools/); never a different backend
         lib = ctypes.CDLL(os.environ.get("QSIM_LIB") or LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **QFT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **QFT_SIGNATURES, **MEASURE_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError here = header and library disagree
             fn.restype = res
             fn.argtypes = args

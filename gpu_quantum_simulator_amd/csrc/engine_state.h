@@ -21,6 +21,7 @@
 //   diagonal.cpp       whole-register diagonal operators from a table: the qsim_diagonal object, the plan, the set-up calls and the two sweeps (the host side of diagonal.hip; diagonal.h)
 //   sample.cpp         shots drawn on the device: the pyramid's geometry and the call (the host side of sample.hip; sample.h)
 //   qft.cpp            the quantum Fourier transform on any qubits: the plan, the per-pass record, the call (the host side of qft.hip; qft.h)
+//   measure.cpp        projective measurement: post-selection, measurement by one draw of sample.cpp's sampler, the plan (the host side of measure.hip; measure.h)
 #ifndef QSIM_ENGINE_STATE_H
 #define QSIM_ENGINE_STATE_H
 
@@ -265,6 +266,11 @@ void forget_diagonal_reads(const qsim_state *s);
 int second_buffer(qsim_state *s, void **out);
 // out[0..count) = the first `count` sums of the first result row; waits for the state's stream
 int fetch_sweep_results(qsim_state *s, int count, double *out);
+
+// ---- sample.cpp ----------------------------------------------------------------------------------------------------------------
+// qsim_sample_shots under the caller's name `who`: the same checks, the same pyramid, the same draws.  total (may be NULL): the sum
+// the draws were scaled by, set whenever the pyramid was built.
+int sample_outcomes(qsim_state *s, const char *who, const double *draws, long shots, const int *qubits, int num_qubits, uint64_t *out, double *total);
 
 } // namespace qsim
 

@@ -4,7 +4,9 @@
 // opens with the same account.  combine.hip (linear combinations of whole states) is no Pauli sweep; it borrows the
 // x == 0 geometry, the unit loads and the reducing grid; diagonal.hip (a real table over the whole register) borrows the
 // unit type, the parity signs, rotate_diag, the resident and the reducing grid and has a geometry of its own (diagonal.h); sample.hip
-// (shots drawn on the device) borrows the workgroup size and the resident grid and nothing else (sample.h).
+// (shots drawn on the device) borrows the workgroup size and the resident grid and nothing else (sample.h); measure.hip
+// (the weight of a measurement's outcome and the collapse onto it) borrows CtrlGeom and spread, with the outcome's bits as
+// `ones`, the unit loads and the two grids (measure.h).
 //
 // A string is two masks: x (bit q: X or Y on qubit q) and z (bit q: Z or Y); s(j) = (-1)^popcount(j & z).  P maps every index
 // pair {j, j ^ x} to itself, so a sweep visits one member j of each pair — the one with the highest bit h of x clear — and meets

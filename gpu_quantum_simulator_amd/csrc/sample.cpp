@@ -51,8 +51,9 @@ extern "C" int qsim_sample_stage_times(qsim_state *s, double *chunk_sums_ms, dou
     return QSIM_OK;
 }
 
-extern "C" int qsim_sample_shots(qsim_state *s, const double *draws, long shots, const int *qubits, int num_qubits, uint64_t *out) {
-    const char *who = "qsim_sample_shots";
+// The body of qsim_sample_shots, for measure.cpp's qsim_measure too (one sampler): `who` names the caller in messages,
+// *total (when asked for, and whenever the pyramid was built) is T[last], the sum the draws are scaled by.
+int qsim::sample_outcomes(qsim_state *s, const char *who, const double *draws, long shots, const int *qubits, int num_qubits, uint64_t *out, double *total_out) {
     if (!s || shots < 0 || (shots > 0 && (!draws || !out)) || (num_qubits > 0 && !qubits)) return fail(QSIM_ERR_ARG, "%s: NULL argument or a negative count", who);
     if (num_qubits < 0 || num_qubits > kSampleMaxQubits) return fail(QSIM_ERR_ARG, "%s: 0 to %d qubits, not %d", who, kSampleMaxQubits, num_qubits);
     SampleQubits qs{};
@@ -92,6 +93,11 @@ extern "C" int qsim_sample_shots(qsim_state *s, const double *draws, long shots,
     }
     (void)hipFree(d_buf);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QSIM_ERR_ALLOC : QSIM_ERR_DEVICE, "%s: %s: %s", who, step, hipGetErrorString(e));
+    if (total_out) *total_out = total;
     if (!drawable) return fail(QSIM_ERR_ARG, "%s: the state's total probability is %g, nothing to draw from", who, total);
     return QSIM_OK;
+}
+
+extern "C" int qsim_sample_shots(qsim_state *s, const double *draws, long shots, const int *qubits, int num_qubits, uint64_t *out) {
+    return sample_outcomes(s, "qsim_sample_shots", draws, shots, qubits, num_qubits, out, nullptr);
 }

@@ -12,7 +12,7 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, permutations
+from . import _lib, channels, permutations
 from ._lib import QsimStats, check
 
 
@@ -918,6 +918,75 @@ class Simulator(_PauliStrings):
         """{outcome: how often it was drawn} over sample_shots(shots, qubits, seed=seed), keys ascending."""
         values, counts = np.unique(self.sample_shots(shots, qubits, seed=seed), return_counts=True)
         return {int(v): int(c) for v, c in zip(values, counts)}
+
+    # -- measurement: collapse, post-selection, reset, Kraus channels (single states only: a Cluster has no counterpart)
+    @staticmethod
+    def _one_draw(who: str, seed, draw) -> float:
+        """The number in [0, 1] a measuring call goes by: the caller's `draw`, or the first of np.random.default_rng(seed).random(1) —
+        what sample_shots(1, seed=seed) would draw."""
+        if draw is None:
+            return float(np.random.default_rng(seed).random(1)[0])
+        if seed is not None:
+            raise ValueError(f"{who}: a seed or a draw, not both")
+        return float(draw)
+
+    def postselect(self, qubits, outcome: int) -> float:
+        """Projects the state onto `outcome` of `qubits` (any number up to the whole state, distinct, any order and places; bit j of the
+        outcome is qubits[j]) and normalises it: the other amplitudes become +0.0, the kept ones are divided by sqrt(W).  Returns W, the
+        squared norm of the kept part before the call — the outcome's probability on a normalised state.  Two sweeps on the device
+        (qsim_postselect), after the queued gates; the discarded amplitudes are overwritten without being read.  QsimError
+        for an outcome of probability zero, the state's bits then unchanged."""
+        qs = [int(q) for q in qubits]
+        if int(outcome) < 0 or int(outcome) >> 64:
+            raise ValueError(f"postselect: the outcome is a non-negative integer below 2^k, got {outcome!r}")
+        w = c_double()
+        check(_lib.load().qsim_postselect(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), int(outcome), byref(w)))
+        return w.value
+
+    def measure(self, qubits, *, seed=None, draw=None, return_probability: bool = False):
+        """Measures `qubits` in the computational basis and collapses the state onto what was read: returns the outcome (bit j is
+        qubits[j]), with return_probability=True (outcome, its probability).  The outcome is exactly sample_shots(draws=[u],
+        qubits=qubits)[0] for the same state and number u in [0, 1]: `draw` is that number (a reproducible pipeline), otherwise it comes
+        from `seed` the way sample_shots(1, seed=seed) makes its draw.  An unnormalised state measures |a|^2 / norm2; afterwards the
+        state has norm 1 (qsim_measure)."""
+        from ctypes import c_uint64
+        qs = [int(q) for q in qubits]
+        out, p = c_uint64(), c_double()
+        check(_lib.load().qsim_measure(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), self._one_draw("measure", seed, draw), byref(out), byref(p)))
+        return (int(out.value), p.value) if return_probability else int(out.value)
+
+    def reset_qubits(self, qubits, *, seed=None, draw=None) -> int:
+        """Measures `qubits` and returns every one of them to |0>: measure(), then an x gate through the ordinary gate queue on each
+        qubit that read 1 — an index flip deferred to, or folded into, the next pass; nothing is launched for it here.  Returns the
+        outcome that was measured."""
+        qs = [int(q) for q in qubits]
+        outcome = self.measure(qs, seed=seed, draw=draw)
+        for j, q in enumerate(qs):
+            if (outcome >> j) & 1:
+                self.apply_1q(gate_matrix("x"), q)
+        return outcome
+
+    def apply_channel(self, kraus, targets, *, seed=None, draw=None, return_probability: bool = False):
+        """One quantum-trajectory step of the channel rho -> sum_i K_i rho K_i^dagger on `targets` (at most 5; bit j of a matrix index
+        is targets[j]; channels.py has the usual lists): operator i is picked with probability p_i = Tr(K_i rho_A K_i^dagger) / Tr rho_A
+        from reduced_density_matrix(targets) — by the draw against the running sum, lowest index first, never one of probability zero —
+        and the state becomes K_i |psi> / sqrt(p_i Tr rho_A), norm 1, through apply_matrix.  Returns i, with
+        return_probability=True (i, p_i).  Averaged over the draws the states reproduce the channel.  ValueError for a list that is not trace-preserving (channels.TRACE_TOLERANCE)."""
+        ts = [int(q) for q in targets]
+        if len(ts) > 5:
+            raise ValueError(f"apply_channel: at most 5 targets, got {len(ts)}")
+        ks = channels.as_kraus_list(kraus, len(ts))
+        u = self._one_draw("apply_channel", seed, draw)
+        if not 0.0 <= u <= 1.0:
+            raise ValueError(f"apply_channel: the draw is {u!r}, not a number in [0, 1]")
+        rho = self.reduced_density_matrix(ts)
+        total = float(np.real(np.trace(rho)))
+        if not (total > 0.0 and np.isfinite(total)):
+            raise ValueError(f"apply_channel: the state's total probability is {total!r}, nothing to draw from")
+        p = channels.probabilities(ks, rho)
+        i = channels.pick(p, u)
+        self.apply_matrix(ks[i] / np.sqrt(p[i] * total), ts)
+        return (i, float(p[i])) if return_probability else i
 
     def norm2(self) -> float:
         v = c_double()

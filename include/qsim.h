@@ -964,4 +964,5 @@ int qsim_tile_records(const qsim_circuit *c, int fuse, int tile_bits, int tile_l
 }
 #endif
 #include "qsim_qft.h"
+#include "qsim_measure.h"
 #endif /* QSIM_H */
