@@ -48,6 +48,20 @@ class QsimPassRegion(ctypes.Structure):
                 ("visited", c_double), ("read_share", c_double)]
 
 
+class QsimSchedSetting(ctypes.Structure):
+    _fields_ = [("commute", ctypes.c_int32), ("lookahead", ctypes.c_int32), ("cap", ctypes.c_int32), ("defer", ctypes.c_int32),
+                ("support_weight", ctypes.c_int32), ("is_default", ctypes.c_int32), ("seed", c_uint64), ("cheap_margin", c_double),
+                ("cost_bytes", c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    @classmethod
+    def of(cls, setting: dict) -> "QsimSchedSetting":
+        """A setting with the fields not named left to the state's options (commute, lookahead, cheap_margin) or off."""
+        return cls(**{"commute": -1, "lookahead": -1, "cheap_margin": 0.0, **{k: v for k, v in setting.items() if k != "cost_bytes"}})
+
+
 class QsimTuneReport(ctypes.Structure):
     _fields_ = [("tile_passes", c_int), ("already_known", c_int), ("passes_tuned", c_int), ("passes_reordered", c_int),
                 ("candidates_timed", c_int), ("ms_ascending", c_double), ("ms_best", c_double), ("seconds", c_double)]
@@ -260,6 +274,12 @@ SIGNATURES = {
     "qsim_plan_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimStats)]),
     "qsim_plan_passes": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimPassInfo), c_int, POINTER(c_int)]),
     "qsim_plan_regions": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_int, POINTER(QsimPassRegion), c_int, POINTER(c_int)]),
+    "qsim_plan_regions_with": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimSchedSetting), POINTER(QsimPassRegion), c_int, POINTER(c_int)]),
+    "qsim_plan_choice": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, c_int, c_int, POINTER(QsimSchedSetting), c_int, POINTER(c_int), POINTER(c_int),
+                                 POINTER(c_double)]),
+    "qsim_sched_choice_lookup": (c_int, [c_uint64, POINTER(QsimSchedSetting)]),
+    "qsim_sched_choice_enter": (c_int, [c_uint64, POINTER(QsimSchedSetting)]),
+    "qsim_schedule_circuit_with": (c_int, [c_void_p, c_int, c_int, c_int, c_uint64, POINTER(QsimSchedSetting), SCHED_CB, c_void_p, POINTER(c_uint64)]),
     "qsim_schedule_circuit": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p]),
     "qsim_schedule_circuit_from": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_uint64, SCHED_CB, c_void_p]),
     "qsim_schedule_circuit_deferred": (c_int, [c_void_p, c_int, c_int, c_int, c_int, SCHED_CB, c_void_p, POINTER(c_uint64)]),

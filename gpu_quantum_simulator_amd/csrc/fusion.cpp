@@ -110,6 +110,7 @@ const Knob kKnobs[] = {
     {"QSIM_SCHED_CHEAP", nullptr, &SchedEnv::cheap_margin, [](const SchedEnv &e, SchedConfig &c) { c.cheap_margin = e.cheap_margin; }},
     {"QSIM_SCHED_NOCOMMUTE", nullptr, nullptr, [](const SchedEnv &, SchedConfig &c) { c.commute = 0; }},
     {"QSIM_SCHED_SEED", &SchedEnv::seed, nullptr, [](const SchedEnv &e, SchedConfig &c) { c.seed = (uint64_t)e.seed; }},
+    {"QSIM_SCHED_SUPW", &SchedEnv::support_weight, nullptr, [](const SchedEnv &e, SchedConfig &c) { c.support_weight = e.support_weight; }},
 };
 constexpr int kNumKnobs = (int)(sizeof kKnobs / sizeof kKnobs[0]);
 } // namespace

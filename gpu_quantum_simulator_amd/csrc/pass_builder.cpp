@@ -191,7 +191,7 @@ class PendingWalk { // plain pointers and values: the trial fills spend their ti
     uint64_t bm_ = 0, bs_ = 0;
 };
 
-struct Cand { long idx; int need; };
+struct Cand { long idx; int need; int rank; }; // rank: need, plus SchedConfig::support_weight per slot that would grow the support
 
 } // namespace
 
@@ -220,6 +220,8 @@ class __attribute__((visibility("hidden"))) Scheduler::PassBuilder {
     std::vector<FusedOp> group_;
 
     uint64_t high_of(long i) const { return cl_.must[(size_t)i] & ~tile_.lowmask; } // the slots cluster i needs
+    // SchedConfig::support_weight, while it counts: the support is neither empty (the generating pass reads nothing) nor complete
+    int grow_weight() const { return cfg_.support_weight > 0 && support_ != 0 && support_ != cl_.all ? cfg_.support_weight : 0; }
     bool coin();
     size_t pending_from_first(size_t limit) const;
     void note(const std::vector<long> &idx);
@@ -271,18 +273,21 @@ void Scheduler::PassBuilder::note(const std::vector<long> &idx) { // the gates b
     for (long i : idx) s_.cur_src_.insert(s_.cur_src_.end(), s_.closed_src_[(size_t)i].begin(), s_.closed_src_[(size_t)i].end());
 }
 
-// Runnable blocks under the qubits chosen so far, cheapest (fewest new high-qubit slots) first.
+// Runnable blocks under the qubits chosen so far, cheapest (fewest new high-qubit slots) first.  While the support is partial a
+// slot outside it costs support_weight more than its place in the tile: it doubles what this pass and every later one visits.
 Cand Scheduler::PassBuilder::scan(const std::vector<char> &dn, uint64_t hset, std::vector<Cand> *cands) const {
-    Cand best{-1, 1 << 30};
+    Cand best{-1, 1 << 30, 1 << 30};
     const int used = __builtin_popcountll(hset);
+    const int gw = grow_weight();
     PendingWalk w(cl_, dn, first_, end_);
     for (long i; (i = w.next()) >= 0; w.pass_over(i)) {
         if (!w.runnable(i)) continue;
         const int need = __builtin_popcountll(high_of(i) & ~hset);
         if (used + need > tile_.kmax) continue;
-        if (cands) cands->push_back({i, need});
-        if (need < best.need) {
-            best = {i, need};
+        const int rank = gw ? need + gw * __builtin_popcountll(high_of(i) & ~hset & ~support_) : need;
+        if (cands) cands->push_back({i, need, rank});
+        if (rank < best.rank) {
+            best = {i, need, rank};
             if (need == 0) return best; // free: take it right away
         }
     }
@@ -295,10 +300,11 @@ Cand Scheduler::PassBuilder::scan(const std::vector<char> &dn, uint64_t hset, st
 // it with the blocked qubits and the cheapest candidate seen so far; only a pick that admits a qubit (it comes after a
 // whole scan) changes what the others need, and the next scan starts over.  (The local search fills ~4000 trial passes
 // per schedule this way; with the pruned local search below 34 -> 15.6 ms of host time for the 1000 gates of the bench circuit.)
+// (scan() without a support weight, that is: the trial fills and rollouts count what a pass can absorb, by slots alone.)
 // `admit`: only clusters whose slots all lie in it are taken (the pass inside the support); the others are passed over.
 int Scheduler::PassBuilder::fill(std::vector<char> &dn, uint64_t &hset, int limit, uint64_t admit) const {
     int cnt = 0;
-    Cand best{-1, 1 << 30};
+    Cand best{-1, 1 << 30, 0};
     const uint64_t himask = ~tile_.lowmask;
     const int kmax = tile_.kmax;
     uint64_t h = hset;
@@ -312,7 +318,7 @@ int Scheduler::PassBuilder::fill(std::vector<char> &dn, uint64_t &hset, int limi
             if (high & ~admit) continue;
             const int need = __builtin_popcountll(high & ~h);
             if (need == 0) { free_pick = i; break; } // used + 0 <= kmax always holds
-            if (used + need <= kmax && need < best.need) best = {i, need};
+            if (used + need <= kmax && need < best.need) best = {i, need, 0};
         }
         if (free_pick >= 0) {
             dn[(size_t)free_pick] = 1;
@@ -325,7 +331,7 @@ int Scheduler::PassBuilder::fill(std::vector<char> &dn, uint64_t &hset, int limi
         h |= high_of(best.idx);
         cnt++;
         w.restart();
-        best = {-1, 1 << 30};
+        best = {-1, 1 << 30, 0};
         used = __builtin_popcountll(h);
     }
     hset = h;
@@ -438,7 +444,7 @@ uint64_t Scheduler::PassBuilder::grow_greedy() {
         if (pick.need > 0 && cfg_.rollout > 1 && cands_.size() > 1) {
             // a new qubit has to be admitted: try the cheapest few candidates and keep the one after which a
             // greedy completion of this pass absorbs the most blocks
-            std::stable_sort(cands_.begin(), cands_.end(), [](const Cand &a, const Cand &b) { return a.need < b.need; });
+            std::stable_sort(cands_.begin(), cands_.end(), [](const Cand &a, const Cand &b) { return a.rank < b.rank; });
             int best_score = -1;
             const size_t tries = std::min(cands_.size(), (size_t)cfg_.rollout);
             for (size_t t = 0; t < tries; t++) {
@@ -460,7 +466,11 @@ uint64_t Scheduler::PassBuilder::grow_greedy() {
 uint64_t Scheduler::PassBuilder::swap_search(uint64_t hset) {
     const int iters = endgame_ ? std::max(cfg_.local_iters, 3) : cfg_.local_iters;
     if (iters <= 0 || __builtin_popcountll(hset) < 2) return hset;
-    int best = eval_ahead(hset, &best_picks_);
+    // ... less support_weight per chosen qubit outside the partial support (grow_weight): a set that absorbs a few clusters more
+    // by doubling the visited share does not win
+    const int gw = grow_weight();
+    auto growth = [&](uint64_t S) { return gw ? gw * __builtin_popcountll(S & ~support_) : 0; };
+    int best = eval_ahead(hset, &best_picks_) - growth(hset);
     for (int it = 0; it < iters; it++) {
         uint64_t bestS = hset;
         for (uint64_t in = hset; in; in &= in - 1) {
@@ -472,7 +482,7 @@ uint64_t Scheduler::PassBuilder::swap_search(uint64_t hset) {
             for (int b = tile_.L; b < cfg_.n; b++) {
                 if (hset >> b & 1ULL) continue;
                 const uint64_t S2 = (hset & ~qi) | (1ULL << b);
-                const int v = (one_short >> b & 1ULL) ? eval_ahead(S2, nullptr) : v_without;
+                const int v = ((one_short >> b & 1ULL) ? eval_ahead(S2, nullptr) : v_without) - growth(S2);
                 if (v > best || (v == best && bestS != hset && coin())) { best = v; bestS = S2; }
             }
         }

@@ -1,6 +1,7 @@
 // plan_probe.cpp — the calls that say how a circuit WOULD be scheduled without running anything: qsim_plan_circuit*, qsim_plan_passes,
 // qsim_schedule_circuit*, qsim_tile_records.  They take a circuit and the options that shape a schedule, never a qsim_state, and make
 // no HIP call: the CPU tests and tools/sched_digest.py stand on them.  Also queue_of and schedule, which planning.cpp shares (planning.h).
+#include <chrono>
 #include <cstring>
 
 #include "planning.h"
@@ -31,7 +32,19 @@ struct ProbeShape {
     uint64_t initial_support = 0;
     bool defer = false; // the X gates left to an index flip (SchedConfig::defer_flips): residual_flips says which
     bool affine = false; // the passes carry their PassRegion (SchedConfig::affine_support)
+    const qsim_sched_setting *setting = nullptr; // the scheduler setting of a planning candidate on top (its defer counts, not `defer`)
 };
+
+SchedHint hint_of(const qsim_sched_setting &h, const SchedConfig &own) { // fields left open take the configuration's own value
+    return {h.commute < 0 ? own.commute : h.commute, h.cheap_margin > 0 ? h.cheap_margin : own.cheap_margin, h.lookahead < 0 ? own.lookahead : h.lookahead,
+            h.cap, h.seed, h.defer != 0 ? 1 : 0, h.support_weight};
+}
+qsim_sched_setting setting_of(const SchedHint &h, double cost, bool is_default) {
+    qsim_sched_setting o{};
+    o.commute = h.commute; o.lookahead = h.lookahead; o.cap = h.cap; o.defer = h.defer; o.support_weight = h.support_weight;
+    o.is_default = is_default ? 1 : 0; o.seed = h.seed; o.cheap_margin = h.cheap_margin; o.cost_bytes = cost;
+    return o;
+}
 
 // How every probe opens: the arguments checked (have_args: the caller's pointers are all there) and the circuit scheduled as an
 // fp64 state with these options would schedule it.
@@ -42,6 +55,10 @@ int probe_passes(bool have_args, const qsim_circuit *c, int fuse, const ProbeSha
     SchedConfig cfg = engine_sched_config(c->num_q, fuse, shape.tile_bits, shape.tile_low_bits, shape.tile_max_ops, 10, false, shape.initial_support);
     cfg.defer_flips = shape.defer ? 1 : 0;
     cfg.affine_support = shape.affine ? 1 : 0;
+    if (shape.setting) {
+        if (shape.setting->cap < 0 || shape.setting->cap > 512 || shape.setting->support_weight < 0) return fail(QSIM_ERR_ARG, "scheduler setting out of range");
+        cfg = with_hint(cfg, hint_of(*shape.setting, cfg));
+    }
     passes = schedule(cfg, queue_of(c), gates_seen, residual_flips);
     return QSIM_OK;
 }
@@ -85,6 +102,8 @@ int report_schedule(const std::vector<Pass> &passes, qsim_sched_cb cb, void *use
     return QSIM_OK;
 }
 } // namespace
+
+static void fill_regions(const qsim_circuit *c, const std::vector<Pass> &passes, qsim_pass_region *out, int cap);
 
 extern "C" int qsim_plan_circuit(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, qsim_stats *out) {
     return qsim_plan_circuit_from(c, fuse, tile_bits, tile_low_bits, 0, out);
@@ -131,6 +150,11 @@ extern "C" int qsim_plan_regions(const qsim_circuit *c, int fuse, int tile_bits,
     std::vector<Pass> passes;
     QSIM_TRY(probe_passes(count && !(cap > 0 && !out), c, fuse, {tile_bits, tile_low_bits, tile_max_ops, initial_support, defer != 0, true}, passes));
     *count = (int)passes.size();
+    fill_regions(c, passes, out, cap);
+    return QSIM_OK;
+}
+
+static void fill_regions(const qsim_circuit *c, const std::vector<Pass> &passes, qsim_pass_region *out, int cap) {
     for (size_t i = 0; i < passes.size() && (int)i < cap; i++) {
         const Pass &p = passes[i];
         const PassRegion &r = p.region;
@@ -149,6 +173,39 @@ extern "C" int qsim_plan_regions(const qsim_circuit *c, int fuse, int tile_bits,
         o.visited = r.on ? r.visited : p.visited;
         o.read_share = r.on ? r.read_share : p.read_share;
     }
+}
+
+// The probes of one candidate of the planning step: the blocks and the regions of the schedule under that setting (level 3).
+extern "C" int qsim_schedule_circuit_with(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                                          const qsim_sched_setting *setting, qsim_sched_cb cb, void *user, uint64_t *flip_mask) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(cb && setting && flip_mask, c, 3, {tile_bits, tile_low_bits, tile_max_ops, initial_support, false, false, setting}, passes, nullptr, flip_mask));
+    return report_schedule(passes, cb, user);
+}
+
+extern "C" int qsim_plan_regions_with(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                                      const qsim_sched_setting *setting, qsim_pass_region *out, int cap, int *count) {
+    std::vector<Pass> passes;
+    QSIM_TRY(probe_passes(count && setting && !(cap > 0 && !out), c, 3, {tile_bits, tile_low_bits, tile_max_ops, initial_support, false, true, setting}, passes));
+    *count = (int)passes.size();
+    fill_regions(c, passes, out, cap);
+    return QSIM_OK;
+}
+
+// What the planning step's model would choose for this circuit on a state with these options (qsim_choose_schedule without a state):
+// every candidate in candidate order with its price, which of them is chosen, and the host seconds the ranking took.
+extern "C" int qsim_plan_choice(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support, int f32, int with_defer,
+                                qsim_sched_setting *out, int cap, int *count, int *chosen, double *seconds) {
+    if (!c || !count || !chosen || (cap > 0 && !out)) return fail(QSIM_ERR_ARG, "NULL argument");
+    const SchedConfig cfg = engine_sched_config(c->num_q, 3, tile_bits, tile_low_bits, tile_max_ops, 10, f32 != 0, initial_support);
+    std::vector<SchedHint> variants;
+    std::vector<RankedVariant> ranked;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t best = rank_schedules(cfg, queue_of(c), f32 != 0, with_defer != 0, nullptr, variants, &ranked);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *count = (int)ranked.size(); // (every candidate is evaluated when nothing stops the search: ranked[i] is variants[i])
+    *chosen = (int)best;
+    for (size_t i = 0; i < ranked.size() && (int)i < cap; i++) out[i] = setting_of(ranked[i].hint, ranked[i].cost, ranked[i].is_default);
     return QSIM_OK;
 }
 

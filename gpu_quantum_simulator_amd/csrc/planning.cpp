@@ -13,32 +13,15 @@
 
 using namespace qsim;
 
-// Schedules the circuit under a few dozen scheduler settings, remembers the one whose passes are predicted to take the least
-// time (pass_time_cost) under the key qsim_flush will compute for the same gates on a state with this support, and hands its
-// passes back.
-static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedConfig &scfg, std::vector<Pass> *out,
-                            std::vector<RankedVariant> *ranked = nullptr, uint64_t *key_out = nullptr, const std::atomic<bool> *stop = nullptr) {
-    const std::vector<QueuedGate> q = queue_of(c);
-    if (s->fuse < 3) {
-        if (out) *out = schedule(scfg, q);
-        return;
-    }
-    const uint64_t key = flush_rule(s, q, scfg.initial_support, false, true).key;
-    if (key_out) *key_out = key;
-    // A circuit whose schedule was chosen by measurement keeps it: no candidate is scheduled again (80 schedules cost about a
-    // second at n = 30), and the hint is put back in case the hint table was emptied in between (kMaxSchedHints) — without
-    // it the circuit would silently run its default schedule with the geometries measured for another one.
-    RankedVariant kept{};
-    if (measured_choice(key, kept)) {
-        set_sched_hint(key, kept.hint, kept.is_default, scfg);
-        if (ranked) ranked->clear(); // nothing left to try
-        if (out) *out = schedule(with_hint(scfg, kept.hint), q);
-        return;
-    }
+// The candidates of the planning step and their prices: the circuit scheduled under a few dozen to a few hundred scheduler settings,
+// each priced by the pass-time model.  Needs no state: `f32` and `with_defer` (a flush of the state may leave X gates to the last
+// pass's stores) say what it has to know of one.  Returns the index of the choice in `variants` (0: the default).
+size_t qsim::rank_schedules(const SchedConfig &scfg, const std::vector<QueuedGate> &q, bool f32, bool with_defer, const std::atomic<bool> *stop,
+                            std::vector<SchedHint> &variants, std::vector<RankedVariant> *ranked) {
     // the variants: how many clusters a pass may take (where the engine sets a cap of its own: states of 4 GiB and more),
     // clusters may / may not overtake (commute), how eagerly passes inside the support are kept (cheap_margin), one more
     // pass of lookahead where the local search is on; the default comes first and wins ties
-    std::vector<SchedHint> variants;
+    variants.clear();
     std::vector<int> caps{0};
     if (scfg.tail_max_ops > scfg.tile_max_ops) // the engine's own cap is in force (engine_sched_config), not a caller's
         for (int cap : {24, 28, 32, 40})
@@ -48,16 +31,35 @@ static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedCon
     for (int com = 1; com >= 0; com--)
         for (int cap : caps)
             for (double mar : {scfg.cheap_margin, 2.0 * scfg.cheap_margin})
-                for (int la = scfg.lookahead; la <= scfg.lookahead + (scfg.lookahead >= 1 ? 1 : 0); la++) variants.push_back({com, mar, la, cap, 0, 0});
+                for (int la = scfg.lookahead; la <= scfg.lookahead + (scfg.lookahead >= 1 ? 1 : 0); la++) variants.push_back({com, mar, la, cap, 0, 0, 0});
     // ... and every one of them with the X gates left to the stores of the last tile pass (SchedConfig::defer_flips), where a flush
     // of this state may do that.  Fewer qubits are forced into tiles, but the greedy packing does not gain from it on every circuit.
-    // (Not on the cold path: the second buffer that out-of-place passes need cannot be asked for while the first is being allocated.)
-    if (!stop && s->defer_flips != 0 && may_defer_flips(s))
+    if (with_defer)
         for (size_t vi = 0, nv = variants.size(); vi < nv; vi++) {
             SchedHint h = variants[vi];
             h.defer = 1;
             variants.push_back(h);
         }
+    // A run that starts on a partial support and has the time (not the cold path, which keeps the candidates above) plans over how the
+    // support grows as well: passes inside the support kept twice as eagerly (cheap_margin x 0.5), and every variant with the packer
+    // weighing the support's growth (SchedConfig::support_weight 5 and 10).  On the bench circuit the schedules with four full sweeps
+    // instead of five are only found with a weight.  The candidates above stay first, in their order.
+    const bool partial_start = !stop && (scfg.initial_support & index_mask(scfg.n)) != index_mask(scfg.n);
+    if (partial_start) {
+        for (size_t vi = 0, nv = variants.size(); vi < nv; vi++)
+            if (variants[vi].cheap_margin == scfg.cheap_margin) {
+                SchedHint h = variants[vi];
+                h.cheap_margin = 0.5 * scfg.cheap_margin;
+                variants.push_back(h);
+            }
+        const size_t nv = variants.size();
+        for (int w : {5, 10})
+            for (size_t vi = 0; vi < nv; vi++) {
+                SchedHint h = variants[vi];
+                h.support_weight = w;
+                variants.push_back(h);
+            }
+    }
     // Every candidate is an independent run of the scheduler on the same gates: they are evaluated on up to 16 host threads
     // (80 schedules at n = 30: 0.9-1.3 s on one thread) and REDUCED in candidate order with the same rule as before — the default
     // first, a later one only when it is at least 0.5 % cheaper — so the choice does not depend on the thread count.  `stop`
@@ -75,7 +77,7 @@ static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedCon
                 Scheduler sv(with_hint(scfg, variants[vi]));
                 feed(sv, q);
                 double cost = 0;
-                sv.finish([&](Pass &&p) { cost += pass_time_cost(p, s->f32); });
+                sv.finish([&](Pass &&p) { cost += pass_time_cost(p, f32); });
                 costs[vi] = cost;
             }
         };
@@ -105,17 +107,52 @@ static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedCon
         for (size_t i = 0; i < variants.size(); i++)
             if (costs[i] >= 0) order.push_back(i);
         std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return costs[a] < costs[b]; });
-        const size_t base_count = std::min<size_t>(3, order.size()), first_seeded = variants.size();
+        const size_t first_seeded = variants.size();
         constexpr int kSeeds = 16;
-        for (size_t b = 0; b < base_count; b++)
-            for (int sd = 1; sd <= kSeeds; sd++) {
-                SchedHint h = variants[order[b]];
-                h.seed = (uint64_t)sd;
-                variants.push_back(h);
+        // (the best three of each weight family, not of the whole list: the model ranks the families against each other only roughly)
+        for (int w : {0, 5, 10}) {
+            size_t taken = 0;
+            for (size_t b = 0; b < order.size() && taken < 3; b++) {
+                if (variants[order[b]].support_weight != w) continue;
+                taken++;
+                for (int sd = 1; sd <= kSeeds; sd++) {
+                    SchedHint h = variants[order[b]];
+                    h.seed = (uint64_t)sd;
+                    variants.push_back(h);
+                }
             }
+        }
         evaluate(first_seeded, variants.size());
         reduce(first_seeded, variants.size());
     }
+    return best;
+}
+
+// Schedules the circuit under a few dozen scheduler settings, remembers the one whose passes are predicted to take the least
+// time (pass_time_cost) under the key qsim_flush will compute for the same gates on a state with this support, and hands its
+// passes back.
+static void choose_schedule(qsim_state *s, const qsim_circuit *c, const SchedConfig &scfg, std::vector<Pass> *out,
+                            std::vector<RankedVariant> *ranked = nullptr, uint64_t *key_out = nullptr, const std::atomic<bool> *stop = nullptr) {
+    const std::vector<QueuedGate> q = queue_of(c);
+    if (s->fuse < 3) {
+        if (out) *out = schedule(scfg, q);
+        return;
+    }
+    const uint64_t key = flush_rule(s, q, scfg.initial_support, false, true).key;
+    if (key_out) *key_out = key;
+    // A circuit whose schedule was chosen by measurement keeps it: no candidate is scheduled again (80 schedules cost about a
+    // second at n = 30), and the hint is put back in case the hint table was emptied in between (kMaxSchedHints) — without
+    // it the circuit would silently run its default schedule with the geometries measured for another one.
+    RankedVariant kept{};
+    if (measured_choice(key, kept)) {
+        set_sched_hint(key, kept.hint, kept.is_default, scfg);
+        if (ranked) ranked->clear(); // nothing left to try
+        if (out) *out = schedule(with_hint(scfg, kept.hint), q);
+        return;
+    }
+    // (Not on the cold path: the second buffer that out-of-place passes need cannot be asked for while the first is being allocated.)
+    std::vector<SchedHint> variants;
+    const size_t best = rank_schedules(scfg, q, s->f32, !stop && s->defer_flips != 0 && may_defer_flips(s), stop, variants, ranked);
     set_sched_hint(key, variants[best], best == 0, scfg);
     if (out) *out = schedule(with_hint(scfg, variants[best]), q); // one more run of the scheduler: the candidates kept their costs only
 }
@@ -243,10 +280,12 @@ static int keep_fastest_schedule(qsim_state *s, const qsim_circuit *c, const Sch
     if (const char *v = getenv("QSIM_TUNE_SCHEDULES")) s->tune_schedules = std::max(1, std::min(80, atoi(v)));
     // ... of the schedules without deferred X gates and of those with them alike: the model prices the flipping pass like any other and
     // ranks the two families against each other only roughly, so the best of the first family is always among the ones run
-    for (int defer = 0; defer < 2; defer++) {
+    // The same holds for the schedules packed with a support weight (SchedConfig::support_weight), with or without deferred X gates: the
+    // model prices a pass by the coordinate cube it visits, so what they save shows only in part — a third family, its best always run.
+    for (int family = 0; family < 3; family++) {
         size_t taken = 0;
         for (const RankedVariant &v : ranked) { // distinct predicted costs = (almost surely) distinct schedules
-            if (v.hint.defer != defer) continue;
+            if (family < 2 ? (v.hint.support_weight != 0 || v.hint.defer != family) : v.hint.support_weight == 0) continue;
             bool dup = false;
             for (const RankedVariant &t : tries) dup = dup || t.cost == v.cost;
             if (!dup) { tries.push_back(v); taken++; }

@@ -10,6 +10,8 @@
 #ifndef QSIM_PLANNING_H
 #define QSIM_PLANNING_H
 
+#include <atomic>
+
 #include "engine_state.h"
 
 namespace qsim {
@@ -17,7 +19,8 @@ namespace qsim {
 // ---- wisdom.cpp ------------------------------------------------------------------------------------------------------------
 // Scheduler variant per circuit, decided by the planning step: key -> the fields of SchedConfig that the variants differ in.
 struct SchedHint { int commute; double cheap_margin; int lookahead; int cap; /* clusters per pass; 0: the configuration's own */ uint64_t seed; /* SchedConfig::seed */
-                   int defer; /* SchedConfig::defer_flips (the engine still asks whether the flush at hand may: may_defer_flips) */ };
+                   int defer; /* SchedConfig::defer_flips (the engine still asks whether the flush at hand may: may_defer_flips) */
+                   int support_weight; /* SchedConfig::support_weight */ };
 struct RankedVariant { SchedHint hint; double cost; bool is_default; };
 SchedConfig with_hint(SchedConfig v, const SchedHint &h);
 // Files the choice under `key` (the default schedule is the absence of a hint; scfg says what the default is) and bumps the epoch
@@ -34,6 +37,11 @@ void enter_tile_order(const qsim_state *s, const TileGeom &g, uint64_t new_mask,
 // the pass-th tile pass, counted from 1.
 void shuffle_high(TileGeom &g, uint64_t seed);
 inline uint64_t probe_order_seed(uint64_t k, uint64_t pass) { return 0x9E3779B97F4A7C15ULL * (k + 1) + 0xD1B54A32D192ED03ULL * pass; }
+
+// ---- planning.cpp ----------------------------------------------------------------------------------------------------------
+// The candidates of the schedule choice and their prices by the pass-time model (the comment at the definition); no state, no HIP call.
+size_t rank_schedules(const SchedConfig &scfg, const std::vector<QueuedGate> &q, bool f32, bool with_defer, const std::atomic<bool> *stop,
+                      std::vector<SchedHint> &variants, std::vector<RankedVariant> *ranked);
 
 // ---- plan_probe.cpp --------------------------------------------------------------------------------------------------------
 // The circuit as the gate queue qsim_run_circuit would leave in a state (what the plan and schedule-hint keys are computed from).

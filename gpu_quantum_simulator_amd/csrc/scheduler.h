@@ -198,6 +198,13 @@ struct SchedConfig {
     int commute = 1;
     uint64_t seed = 0; // != 0: ties between equally good candidates (which cluster to admit next, which qubit to swap) are broken pseudo-randomly
                        // instead of in index order — another valid schedule of the same circuit per seed, for the planning step to choose among
+    // > 0: while the support is partial (neither empty nor complete) the packer weighs its growth.  Every index bit a pass adds to the
+    // support doubles the share of the register that pass and every later one visits, so a cluster that needs tile slots outside the
+    // support ranks as if it needed support_weight more slots per such qubit (scan, the rollout candidates of grow_greedy), and the
+    // local search scores a qubit set less support_weight per qubit outside it.  What fits a tile is still decided by the true slot
+    // count.  0: the term is not evaluated at all — the schedule is what it was before the field existed.  Nothing changes on a dense
+    // start or once the support is complete.  The planning step tries 5 and 10 beside 0 (choose_schedule).
+    int support_weight = 0;
     // Level 3: 1 = X gates are not scheduled at all.  X only relabels the index, and it moves past any later gate exactly
     // (U X_q = X_q (X_q U X_q), the conjugate being U with rows and columns permuted), so the feed keeps a flip bit per qubit:
     // an exact X toggles it, an anti-diagonal 2x2 A is fed as the diagonal X A and toggles it, every other gate is fed conjugated
@@ -238,7 +245,7 @@ SchedConfig engine_sched_config(int n, int fuse, int tile_bits, int tile_low_bit
 // applying and comparing all go over it.
 struct SchedEnv {
     uint32_t set = 0;
-    int lookahead = 0, rollout = 0, window = 0, local_iters = 0, objective = 0, merge = 0, merge_qubits = 0, cap = 0, seed = 0;
+    int lookahead = 0, rollout = 0, window = 0, local_iters = 0, objective = 0, merge = 0, merge_qubits = 0, cap = 0, seed = 0, support_weight = 0;
     double cheap_margin = 0;
     __attribute__((visibility("hidden"))) bool operator==(const SchedEnv &o) const;
 };

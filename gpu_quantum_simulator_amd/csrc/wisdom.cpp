@@ -111,6 +111,7 @@ static std::map<uint64_t, RankedVariant> g_sched_measured; // guarded by g_hints
 
 SchedConfig qsim::with_hint(SchedConfig v, const SchedHint &h) {
     v.commute = h.commute; v.cheap_margin = h.cheap_margin; v.lookahead = h.lookahead; v.seed = h.seed; v.defer_flips = h.defer;
+    v.support_weight = h.support_weight;
     if (h.cap > 0) { v.tile_max_ops = h.cap; v.tail_max_ops = std::max(v.tail_max_ops, h.cap); }
     return v;
 }
@@ -135,7 +136,7 @@ static void put_hint(uint64_t key, const SchedHint &h, bool is_default, bool res
 void qsim::set_sched_hint(uint64_t key, const SchedHint &now, bool is_default, const SchedConfig &scfg) {
     std::lock_guard<std::mutex> lock(g_hints_mu);
     const auto it = g_sched_hints.find(key);
-    const SchedHint dflt{scfg.commute, scfg.cheap_margin, scfg.lookahead, 0, 0, 0};
+    const SchedHint dflt{scfg.commute, scfg.cheap_margin, scfg.lookahead, 0, 0, 0, scfg.support_weight};
     const SchedHint before = it == g_sched_hints.end() ? dflt : it->second;
     if (!is_default && g_sched_hints.size() >= kMaxSchedHints && it == g_sched_hints.end()) { // full: both tables start over together — a
         g_sched_hints.clear();                                              // measured entry without its hint would pin a schedule nobody runs
@@ -146,7 +147,8 @@ void qsim::set_sched_hint(uint64_t key, const SchedHint &now, bool is_default, c
         if (keep) g_sched_measured[key] = kept;
     }
     put_hint(key, now, is_default, before.commute != now.commute || before.cheap_margin != now.cheap_margin || before.lookahead != now.lookahead ||
-                                       before.cap != now.cap || before.seed != now.seed || before.defer != now.defer);
+                                       before.cap != now.cap || before.seed != now.seed || before.defer != now.defer ||
+                                       before.support_weight != now.support_weight);
 }
 
 bool qsim::measured_choice(uint64_t key, RankedVariant &out) {
@@ -163,6 +165,25 @@ void qsim::remember_measured_choice(uint64_t key, const RankedVariant &choice) {
     g_sched_measured[key] = choice;
 }
 
+// The measured schedule choice filed under a key (what a "sched" line of the file holds): 1 and the setting, or 0.
+extern "C" int qsim_sched_choice_lookup(uint64_t key, qsim_sched_setting *out) {
+    RankedVariant rv{};
+    if (!out || !measured_choice(key, rv)) return 0;
+    *out = qsim_sched_setting{};
+    out->commute = rv.hint.commute; out->lookahead = rv.hint.lookahead; out->cap = rv.hint.cap; out->defer = rv.hint.defer;
+    out->support_weight = rv.hint.support_weight; out->is_default = rv.is_default ? 1 : 0; out->seed = rv.hint.seed; out->cheap_margin = rv.hint.cheap_margin;
+    return 1;
+}
+// ... and a choice filed as if it had been measured (the planning step does this on a device; tests of the file format do it here)
+extern "C" int qsim_sched_choice_enter(uint64_t key, const qsim_sched_setting *in) {
+    if (!in || !(in->cheap_margin > 0) || in->lookahead < 0 || in->commute < 0 || in->cap < 0 || in->support_weight < 0) return fail(QSIM_ERR_ARG, "scheduler setting out of range");
+    RankedVariant rv{};
+    rv.hint = {in->commute, in->cheap_margin, in->lookahead, in->cap, in->seed, in->defer != 0 ? 1 : 0, in->support_weight};
+    rv.is_default = in->is_default != 0;
+    remember_measured_choice(key, rv);
+    return QSIM_OK;
+}
+
 extern "C" long qsim_tune_table_size(void) {
     std::lock_guard<std::mutex> lock(g_wisdom_mu);
     return (long)g_wisdom.size();
@@ -174,12 +195,17 @@ extern "C" int qsim_tune_table_save(const char *path) {
     if (!path) return fail(QSIM_ERR_ARG, "NULL path");
     FILE *f = fopen(path, "w");
     if (!f) return fail(QSIM_ERR_OPEN, "cannot write %s", path);
-    {   // measured schedule choices: "sched <key> <commute> <cheap_margin> <lookahead> <cap> <is_default>"
+    {   // measured schedule choices: "sched <key> <commute> <cheap_margin> <lookahead> <cap> <is_default> <seed> [<defer> [<support_weight>]]"
         std::lock_guard<std::mutex> lock(g_hints_mu);
-        for (const auto &kv : g_sched_measured)
-            fprintf(f, "sched %llx %d %.17g %d %d %d %llu%s\n", (unsigned long long)kv.first, kv.second.hint.commute, kv.second.hint.cheap_margin,
-                    kv.second.hint.lookahead, kv.second.hint.cap, kv.second.is_default ? 1 : 0, (unsigned long long)kv.second.hint.seed,
-                    kv.second.hint.defer ? " 1" : ""); // an eighth field only where X gates are deferred: other lines stay what older files hold
+        for (const auto &kv : g_sched_measured) {
+            fprintf(f, "sched %llx %d %.17g %d %d %d %llu", (unsigned long long)kv.first, kv.second.hint.commute, kv.second.hint.cheap_margin,
+                    kv.second.hint.lookahead, kv.second.hint.cap, kv.second.is_default ? 1 : 0, (unsigned long long)kv.second.hint.seed);
+            // an eighth field only where X gates are deferred, a ninth (SchedConfig::support_weight, the eighth then always in front of
+            // it) only where the weight is not 0: other lines stay what older files hold
+            if (kv.second.hint.support_weight) fprintf(f, " %d %d", kv.second.hint.defer ? 1 : 0, kv.second.hint.support_weight);
+            else if (kv.second.hint.defer) fprintf(f, " 1");
+            fprintf(f, "\n");
+        }
     }
     std::lock_guard<std::mutex> lock(g_wisdom_mu);
     for (const auto &kv : g_wisdom) {
@@ -205,8 +231,9 @@ extern "C" long qsim_tune_table_load(const char *path) {
             unsigned long long key = 0, seed = 0;
             RankedVariant rv{};
             int isd = 0;
-            if (sscanf(line + 6, "%llx %d %lf %d %d %d %llu %d", &key, &rv.hint.commute, &rv.hint.cheap_margin, &rv.hint.lookahead, &rv.hint.cap, &isd, &seed, &rv.hint.defer) >= 6 &&
-                (rv.hint.defer == 0 || rv.hint.defer == 1) &&
+            if (sscanf(line + 6, "%llx %d %lf %d %d %d %llu %d %d", &key, &rv.hint.commute, &rv.hint.cheap_margin, &rv.hint.lookahead, &rv.hint.cap, &isd, &seed, &rv.hint.defer,
+                       &rv.hint.support_weight) >= 6 && // (fewer than nine fields: an older line, weight 0)
+                (rv.hint.defer == 0 || rv.hint.defer == 1) && rv.hint.support_weight >= 0 && rv.hint.support_weight <= 1024 &&
                 rv.hint.cheap_margin > 0 && rv.hint.lookahead >= 0 && rv.hint.lookahead <= 8 && rv.hint.cap >= 0 && rv.hint.cap <= 512) {
                 rv.is_default = isd != 0;
                 rv.hint.seed = seed;

@@ -121,27 +121,47 @@ class Circuit:
                 for i in range(min(n.value, cap))]
 
     def regions(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, initial_support: int = 0,
-                defer: bool = False) -> list:
+                defer: bool = False, setting: dict = None) -> list:
         """qsim_plan_regions: per pass of schedule() with the same arguments (defer: of schedule(flips=[])) what
         QSIM_OPT_AFFINE_SUPPORT adds — the tiles to visit (origin, gen), the parity checks of the region the previous pass wrote
-        as (mask, parity) pairs, and the shares of the register written and read."""
+        as (mask, parity) pairs, and the shares of the register written and read.  setting: of schedule(setting=...)."""
         from ctypes import c_int
         cap = 4096
         buf = (_lib.QsimPassRegion * cap)()
         n = c_int()
-        check(_lib.load().qsim_plan_regions(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(defer)), buf, cap, byref(n)))
+        if setting is not None:
+            if fuse != 3 or defer:
+                raise ValueError("regions: a setting goes with fuse=3 and states its own defer")
+            check(_lib.load().qsim_plan_regions_with(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support,
+                                                     byref(_lib.QsimSchedSetting.of(setting)), buf, cap, byref(n)))
+        else:
+            check(_lib.load().qsim_plan_regions(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(defer)), buf, cap, byref(n)))
         return [{"kernel": _lib.K_NAMES[r.kernel_class], "on": bool(r.on), "refined": bool(r.refined), "tile_mask": int(r.tile_mask),
                  "support_before": int(r.support_before), "origin": int(r.origin), "gen": [int(r.gen[j]) for j in range(r.n_gen)],
                  "checks": [(int(r.check_mask[j]), int(r.check_parity >> j & 1)) for j in range(r.n_checks)],
                  "visited": float(r.visited), "read_share": float(r.read_share)}
                 for r in (buf[i] for i in range(min(n.value, cap)))]
 
+    def plan_choice(self, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, initial_support: int = 0, f32: bool = False,
+                    with_defer: bool = True) -> dict:
+        """qsim_plan_choice: what the planning step's model would choose for this circuit (host only) — every candidate setting in
+        candidate order with its price ("candidates"), the index of the choice ("chosen") and the host seconds of the ranking."""
+        from ctypes import c_int, c_double
+        cap = 4096
+        buf = (_lib.QsimSchedSetting * cap)()
+        n, chosen, seconds = c_int(), c_int(), c_double()
+        check(_lib.load().qsim_plan_choice(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(f32)), int(bool(with_defer)),
+                                           buf, cap, byref(n), byref(chosen), byref(seconds)))
+        return {"candidates": [buf[i].as_dict() for i in range(min(n.value, cap))], "chosen": chosen.value, "seconds": seconds.value}
+
     def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, flips: list = None,
-                 initial_support: int = 0) -> list:
+                 initial_support: int = 0, setting: dict = None) -> list:
         """Fused blocks in launch order: (pass, kernel_class, kind, qubits, matrix|None, gates_folded); kind is
         "u1" / "cx" / "u2" ... "u8", qubits most significant first (cx: control, target).  flips: a list — the schedule with
         the X gates deferred (qsim_schedule_circuit_deferred); the residual index mask is appended to it.  initial_support
-        (without flips): the index bits that may be 1 in the state the circuit finds (qsim_schedule_circuit_from)."""
+        (without flips): the index bits that may be 1 in the state the circuit finds (qsim_schedule_circuit_from).  setting: a
+        candidate of the planning step as a dict (fields of qsim_sched_setting; those left out are the options' own) — the level-3
+        schedule under it (qsim_schedule_circuit_with); where it defers, pass flips=[] to receive the mask."""
         out = []
 
         def cb(_user, pass_i, kclass, kind, qubits, nq, U, folded):
@@ -152,6 +172,15 @@ class Circuit:
                 m = np.ctypeslib.as_array(U, shape=(2 * d * d,)).copy().view(np.complex128).reshape(d, d)
             out.append((pass_i, _lib.K_NAMES[kclass], {1: "u1", 2: "cx", 3: "u2", 4: "u3", 5: "u4", 6: "u5", 7: "u6", 8: "u7", 9: "u8"}[kind], qs, m, folded))
 
+        if setting is not None:
+            if fuse != 3 or (flips is None) != (not setting.get("defer")):
+                raise ValueError("schedule: a setting goes with fuse=3, and with flips=[] exactly when it defers")
+            mask = ctypes.c_uint64()
+            check(_lib.load().qsim_schedule_circuit_with(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support,
+                                                         byref(_lib.QsimSchedSetting.of(setting)), _lib.SCHED_CB(cb), None, byref(mask)))
+            if flips is not None:
+                flips.append(int(mask.value))
+            return out
         if flips is None:
             check(_lib.load().qsim_schedule_circuit_from(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, _lib.SCHED_CB(cb), None))
             return out

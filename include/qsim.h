@@ -929,6 +929,27 @@ typedef struct {
 } qsim_pass_region;
 int qsim_plan_regions(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support, int defer,
                       qsim_pass_region *out, int cap, int *count);
+/* One candidate of the planning step (qsim_choose_schedule): the scheduler setting a schedule choice consists of.  commute < 0,
+ * lookahead < 0, cheap_margin <= 0: the value the state's options give.  cap: clusters per pass (0: the options' own); seed: the
+ * tie-break seed; defer: X gates left to the last pass's stores; support_weight: what a tile slot outside a partial support costs
+ * the packer beyond its place (0: not weighed).  cost_bytes / is_default: filled in by qsim_plan_choice. */
+typedef struct {
+    int32_t commute, lookahead, cap, defer, support_weight, is_default;
+    uint64_t seed;
+    double cheap_margin, cost_bytes;
+} qsim_sched_setting;
+/* qsim_plan_regions for the level-3 schedule under a setting (its defer counts). */
+int qsim_plan_regions_with(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                           const qsim_sched_setting *setting, qsim_pass_region *out, int cap, int *count);
+/* What the pass-time model of the planning step would choose for this circuit on an fp64 (f32 != 0: fp32) state with these options
+ * that has the given support, with_defer != 0: the candidates with deferred X gates take part.  out[i]: candidate i with its price
+ * (at most cap are written, *count receives their number), *chosen: the index of the choice, *seconds: host time of the ranking. */
+int qsim_plan_choice(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support, int f32, int with_defer,
+                     qsim_sched_setting *out, int cap, int *count, int *chosen, double *seconds);
+/* The measured schedule choice filed under a circuit's key, as a "sched" line of the table file states it: lookup returns 1 and the
+ * setting or 0; enter files one (on a device qsim_tune_circuit does). */
+int qsim_sched_choice_lookup(uint64_t key, qsim_sched_setting *out);
+int qsim_sched_choice_enter(uint64_t key, const qsim_sched_setting *in);
 /* Same scheduler, op by op: calls `cb` for every fused block in launch order with the pass it belongs to, the
  * kernel class of that pass, the block kind (QSIM_GATE_U1 / _CX / _U2 .. _U8 by qubit count), its qubits (most
  * significant first; CX: control, target) and its matrix (2^nq x 2^nq complex, row-major; NULL for CX).  A block of a
@@ -948,6 +969,10 @@ int qsim_schedule_circuit_from(const qsim_circuit *c, int fuse, int tile_bits, i
  * deferred statements are counted in gates_folded of the last block reported. */
 int qsim_schedule_circuit_deferred(const qsim_circuit *c, int fuse, int tile_bits, int tile_low_bits, int tile_max_ops,
                                    qsim_sched_cb cb, void *user, uint64_t *flip_mask);
+/* The level-3 schedule under a setting (qsim_sched_setting above): its blocks, and in *flip_mask what qsim_schedule_circuit_deferred
+ * reports there (0 unless the setting defers). */
+int qsim_schedule_circuit_with(const qsim_circuit *c, int tile_bits, int tile_low_bits, int tile_max_ops, uint64_t initial_support,
+                               const qsim_sched_setting *setting, qsim_sched_cb cb, void *user, uint64_t *flip_mask);
 /* The same schedule (same arguments) as the records the tile kernel reads: `cb` is called for every block of every tile pass,
  * the tile-uniform factors included, with the pass, the geometry the record was encoded under (geom[0..2] = tile bits B, low
  * bits L, number of high bits; high[j] = global bit of tile-local bit L+j, IN ORDER), the block's qubits outside the tile

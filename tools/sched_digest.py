@@ -34,7 +34,7 @@ GEOMETRIES = ((12, 3), (11, 3), (13, 3), (12, 5), (8, 2))
 TILE_MAX_OPS = (1, 8, 32)
 # every QSIM_SCHED_* variable with a value that is not its default (scheduler.h SchedConfig, fusion.cpp engine_sched_config)
 KNOBS = (("LOOKAHEAD", "2"), ("ROLLOUT", "2"), ("WINDOW", "48"), ("LOCAL", "2"), ("OBJ", "1"), ("MERGE", "0"), ("MERGEQ", "4"),
-         ("CAP", "12"), ("CHEAP", "0.25"), ("NOCOMMUTE", "1"), ("SEED", "7"))
+         ("CAP", "12"), ("CHEAP", "0.25"), ("NOCOMMUTE", "1"), ("SEED", "7"), ("SUPW", "5"))
 
 
 def digest(circuit, n, fuse, tile_bits, low_bits):
