@@ -2,12 +2,11 @@
  * qsim_measure.h — projective measurement on the device: post-selection, measurement by a draw, the plan probe.
  * Part of the C ABI of libqsim.so: qsim.h pulls this file in with one #include line, and a program includes qsim.h, never this.
  *
- * Why a header of its own.  Two tests take a census of the TEXT of qsim.h: one holds it to the ctypes table _lib.SIGNATURES, one to
- * the lazy-state table tests/lazy_cases.py.  The change that added these calls left every existing test file as it was, the lazy
- * table included, so the declarations live here and their ctypes signatures in _lib.MEASURE_SIGNATURES (qsim_qft.h and
- * _lib.QFT_SIGNATURES are the precedent).  The substance of the lazy-state contract is met all the same: both calls open with
- * settle(), and tests/test_gpu_measure.py runs them from every lazy start over poisoned memory against a dense twin, bit for bit.
- * Folding the entries into the lazy table, and these lines into qsim.h, is left to a change that may touch that table.
+ * A header of its own keeps one feature's declarations and contract in one place; its ctypes signatures are _lib.MEASURE_SIGNATURES.
+ * The lazy-state census (tests/test_lazy_cases_cpu.py) follows the #include "qsim_*.h" lines of qsim.h, so a call declared here that
+ * takes a qsim_state needs its entry in tests/lazy_cases.py like any other: qsim_postselect and qsim_measure open with settle() and
+ * have their cases there, which tests/test_gpu_lazy_states.py runs from every lazy start over poisoned memory against a dense twin,
+ * bit for bit.
  */
 #ifndef QSIM_MEASURE_H_ABI
 #define QSIM_MEASURE_H_ABI

@@ -2,12 +2,11 @@
  * qsim_qft.h — the quantum Fourier transform on any qubits of a state, one sweep per digit of at most ten bits.
  * Part of the C ABI of libqsim.so: qsim.h pulls this file in with one #include line, and a program includes qsim.h, never this.
  *
- * Why a header of its own.  Two tests take a census of the TEXT of qsim.h: one holds it to the ctypes table _lib.SIGNATURES, one to
- * the lazy-state table tests/lazy_cases.py.  The change that added these calls left every existing test file as it was, the lazy
- * table included, so the declarations live here and their ctypes signatures in _lib.QFT_SIGNATURES (qsim_legacy.h and
- * _lib.LEGACY_SYMBOLS are the precedent).  The substance of the lazy-state contract is met all the same: qsim_apply_qft opens with
- * settle(), and tests/test_gpu_qft.py runs it from every lazy start over poisoned memory against a dense twin, bit for bit.  Folding
- * the entry into the lazy table, and these lines into qsim.h, is left to a change that may touch that table.
+ * A header of its own keeps one feature's declarations and contract in one place; its ctypes signatures are _lib.QFT_SIGNATURES.
+ * The lazy-state census (tests/test_lazy_cases_cpu.py) follows the #include "qsim_*.h" lines of qsim.h, so a call declared here that
+ * takes a qsim_state needs its entry in tests/lazy_cases.py like any other: qsim_apply_qft opens with settle() and has its cases there
+ * (an in-place one and a moving one), which tests/test_gpu_lazy_states.py runs from every lazy start over poisoned memory against a
+ * dense twin, bit for bit.
  */
 #ifndef QSIM_QFT_H_ABI
 #define QSIM_QFT_H_ABI

@@ -1,4 +1,5 @@
-"""The one table of the lazy-state contract: every exported function of include/qsim.h whose first parameter is a qsim_state.
+"""The one table of the lazy-state contract: every exported function of include/qsim.h, and of the headers it pulls in with
+#include "qsim_*.h", whose first parameter is a qsim_state.
 
 A state handle does not always hold its amplitudes in memory (engine_state.h): |0...0> may be PENDING, the state may be PARTIAL —
 written only inside `support`, the memory outside it zero by definition and never written — or it may hold nothing.  Every entry
@@ -100,6 +101,16 @@ GRADIENT_CONTROLLED = [(0.8, "X1 X13", (2,)), (0.6, "X14 X0"), (-0.6, "Z5", (0, 
 # (gamma, "diagonal") stands for a step exp(-i gamma D) on the table of DIAGONAL_TERMS
 GRADIENT_DIAGONAL = [(0.6, "X14 X0"), (0.35, "diagonal"), (-1.2, "Y3 Z9"), (-0.2, "diagonal"), (0.7, "X7 Y8")]
 
+# the Fourier transform's register: its first ten qubits are one in-place sweep, all twelve under a cap of 4 bits a digit are three
+# sweeps, two of them into the second buffer
+QFT_REGISTER = (14, 0, 3, 7, 9, 1, 12, 5, 13, 10, 4, 8)
+# measured qubits: one set inside SUPPORT_LOW; no qubit lies outside BOTH partial supports (together they cover the register), so the
+# other set has a qubit outside each of them — 4 outside SUPPORT_LOW, 0 outside SUPPORT_HIGH, both outside what `pending` holds
+MEASURE_INSIDE_LOW = (9, 0, 5)
+MEASURE_OUTSIDE = (4, 14, 0)
+assert set(MEASURE_INSIDE_LOW) <= set(SUPPORT_LOW)
+assert set(MEASURE_OUTSIDE) - set(SUPPORT_LOW) and set(MEASURE_OUTSIDE) - set(SUPPORT_HIGH)
+
 CASES = {
     # ---- read-only ----------------------------------------------------------------------------------------------------------------
     "qsim_read": [Case("read_subrange", "read", READ, first=1001, count=20000)],
@@ -137,6 +148,15 @@ CASES = {
         Case("permutation_ten", "apply_permutation", IN_PLACE, targets=(14, 0, 3, 7, 9, 1, 12, 5, 13, 10), controls=(), table=affine_table(10, 421, 77), plan=PLAN_MAIN),
         Case("permutation_small", "apply_permutation", IN_PLACE, targets=(14, 0, 6), controls=(1, 2, 4, 8), table=affine_table(3, 7, 1), plan=PLAN_SMALL)],
     "qsim_apply_diagonal_phase": [Case("diagonal_phase", "apply_diagonal_phase", IN_PLACE, terms=DIAGONAL_TERMS, gamma=0.37)],
+    # (qft.cpp queues nothing: settle(), then one sweep per digit.  The operands are tests/test_gpu_qft.py's LAZY_SINGLE and LAZY_MOVING)
+    "qsim_apply_qft": [Case("qft_single", "apply_qft", IN_PLACE, qubits=QFT_REGISTER[:10], max_digit_bits=0, moving=False),
+                       Case("qft_moving", "apply_qft", IN_PLACE, qubits=QFT_REGISTER, max_digit_bits=4, moving=True)],
+    # (measure.hip queues nothing: settle(), the weight sweep, the collapse sweep.  The outcome post-selected is the most probable one
+    # of the start's state, which the driver works out; the qubit sets and the draw are tests/test_gpu_measure.py's)
+    "qsim_postselect": [Case("postselect_inside_low", "postselect", IN_PLACE, qubits=MEASURE_INSIDE_LOW),
+                        Case("postselect_outside", "postselect", IN_PLACE, qubits=MEASURE_OUTSIDE)],
+    "qsim_measure": [Case("measure_inside_low", "measure", IN_PLACE, qubits=MEASURE_INSIDE_LOW, draw=0.37),
+                     Case("measure_outside", "measure", IN_PLACE, qubits=MEASURE_OUTSIDE, draw=0.37)],
     "qsim_scale": [Case("scale", "scale", IN_PLACE, "ref", "engine.cpp qsim_scale: `return qsim_apply_1q(s, U, 0)` — diag(z, z) on qubit 0, queued",
                         z=(0.6, -0.35))],
     # (lanczos.cpp queues nothing: settle(), then sweeps on buffers — both forms compare as bits)

@@ -210,6 +210,26 @@ def _queued_as_gates(rotations, precision):
     return gates.value
 
 
+def _qft_moves(case, precision):
+    """Whether the plan of the case's Fourier transform has a sweep that writes the second buffer (host only)."""
+    from ctypes import byref, c_int, c_long, c_uint64
+    qs = case.operands["qubits"]
+    passes, digits, oop, masks = c_int(-1), (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
+    tiles, units, trips = c_uint64(), c_uint64(), c_long()
+    _lib.check(_lib.load().qsim_apply_qft_plan((c_int * len(qs))(*qs), len(qs), N, precision, case.operands["max_digit_bits"], byref(passes), digits, oop,
+                                               masks, byref(tiles), byref(units), byref(trips)))
+    return any(oop[p] for p in range(passes.value))
+
+
+def _likely_outcome(start, precision, qubits):
+    """The most probable outcome of `qubits` on the state a start stands for: non-zero probability, and bits of 0 on every qubit
+    outside a sparse start's support, where a 1 never happens."""
+    p = np.abs(_dense(start, precision)) ** 2
+    idx = np.arange(p.size)
+    outcome_of = sum(((idx >> q) & 1) << j for j, q in enumerate(qubits))
+    return int(np.argmax(np.bincount(outcome_of, weights=p, minlength=1 << len(qubits))))
+
+
 def _others(start, count):
     """The starts of a case's further states: each a different one."""
     at = L.STARTS.index(start)
@@ -258,6 +278,13 @@ def _drive(case, side, start):
         sim.apply_permutation(o["table"], o["targets"], o["controls"])
     elif m == "apply_diagonal_phase":
         sim.apply_diagonal_phase(side.diagonal(o["terms"]), o["gamma"])
+    elif m == "apply_qft":
+        sim.apply_qft(o["qubits"], max_digit_bits=o["max_digit_bits"])
+    elif m == "postselect":
+        out["weight"] = np.array(sim.postselect(o["qubits"], _likely_outcome(start, side.precision, o["qubits"])))
+    elif m == "measure":
+        outcome, probability = sim.measure(o["qubits"], draw=o["draw"], return_probability=True)
+        out["outcome"], out["probability"] = np.array(outcome, dtype=np.uint64), np.array(probability)
     elif m == "scale":
         sim.scale(complex(*o["z"]))
     elif m == "ground_state":
@@ -341,6 +368,8 @@ def test_lazy_state(precision, start, case):
         assert _plan_path(case, precision) == case.operands["plan"], label
     if "queued" in case.operands:
         assert _queued_as_gates(case.operands["rotations"], precision) == case.operands["queued"], label
+    if "moving" in case.operands:
+        assert _qft_moves(case, precision) == case.operands["moving"], label
     if case.method == "energy_and_gradient":  # the forward pass of a gradient case queues nothing: it compares as bits
         assert _queued_as_gates([r for r in case.operands["rotations"] if r[1] != "diagonal"], precision) == 0, label
     with Side(precision, lazy=True) as lazy, Side(precision, lazy=False) as twin:
