@@ -347,3 +347,31 @@ def check(rc: int) -> None:
         if rc in (ERR_OPEN, ERR_PARSE) and not msg:
             msg = lib.qsim_circuit_error() or b""
         raise QsimError(rc, msg.decode(errors="replace"))
+
+
+class Handle:
+    """An owned C handle in `_h`: `_free` names the call that releases it.  close() may be called twice; `with` and collection close."""
+    _free = ""
+
+    def close(self) -> None:
+        if self._h:
+            getattr(load(), self._free)(self._h)
+            self._h = c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def check_cluster(rc: int) -> None:
+    """check for the sharding calls, which report through qsim_cluster_error()."""
+    if rc:
+        raise QsimError(rc, (load().qsim_cluster_error() or b"").decode())

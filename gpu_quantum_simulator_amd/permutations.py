@@ -10,7 +10,7 @@ import operator
 
 import numpy as np
 
-MAX_QUBITS = 10  # qsim_apply_permutation_max_qubits()
+MAX_QUBITS = 10  # plans.apply_permutation_max_qubits()
 
 
 def _int(value, what: str) -> int:

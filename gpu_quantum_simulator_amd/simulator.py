@@ -1,479 +1,29 @@
 """Python mirror of the C host: thin objects over the C ABI handles, nothing computed in Python.
 
-`Circuit` = qsim_circuit (the tokenizer of quantum_simulator.c:115-254 and the gate table :184-211),
 `Simulator` = qsim_state (state vector in HBM; execute_single_qubit_gate :81-92 -> apply_1q,
-execute_cnot :94-106 -> apply_cx, kernel_gate_4 quantum_simulator_4x4.cu:109-146 -> apply_2q).
-"""
+execute_cnot :94-106 -> apply_cx, kernel_gate_4 quantum_simulator_4x4.cu:109-146 -> apply_2q).  `Circuit` lives in circuit.py, the
+Pauli-list arguments in pauli_args.py, `Diagonal` in diagonal.py and the sharding handles in sharding.py; their names are re-exported
+here, where they used to live."""
 from __future__ import annotations
 
 import ctypes
-from ctypes import byref, c_double, c_int, c_void_p
-from typing import Iterable, Optional, Sequence
+from ctypes import byref, c_double, c_int, c_ubyte, c_uint32, c_uint64, c_void_p
+from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib, channels, permutations
 from ._lib import QsimStats, check
+from ._marshal import dp as _dp, ints as _ints, mat as _mat, u64p as _u64p
+from .circuit import Circuit, gate_matrix
+from .diagonal import Diagonal, _split_diagonal_observable, _split_diagonal_steps
+from .pauli_args import _control_masks, _hamiltonian_arrays, _PauliStrings, _rotation_arrays, _split_controls
+from .sharding import Cluster, RankComm, ShardPlanHandle  # noqa: F401  (re-exported)
 
 
-def _dp(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(c_double))
-
-
-def _mat(U, dim: int) -> np.ndarray:
-    m = np.ascontiguousarray(np.asarray(U, dtype=np.complex128).reshape(dim * dim))
-    return m.view(np.float64)
-
-
-def gate_matrix(token: str) -> Optional[np.ndarray]:
-    """2x2 for a gate token of the reference's vocabulary (None for cx / unknown)."""
-    u = np.zeros(8)
-    kind = _lib.load().qsim_gate_matrix(token.encode(), _dp(u))
-    return u.view(np.complex128).reshape(2, 2).copy() if kind == _lib.GATE_U1 else None
-
-
-class Circuit:
-    def __init__(self, handle: c_void_p):
-        self._h = handle
-
-    @classmethod
-    def empty(cls, num_q: int) -> "Circuit":
-        h = c_void_p()
-        check(_lib.load().qsim_circuit_create(num_q, byref(h)))
-        return cls(h)
-
-    @classmethod
-    def from_file(cls, path: str) -> "Circuit":
-        h = c_void_p()
-        rc = _lib.load().qsim_circuit_parse_file(path.encode(), byref(h))
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_circuit_error() or b"").decode())
-        return cls(h)
-
-    @classmethod
-    def from_text(cls, text: str) -> "Circuit":
-        h = c_void_p()
-        raw = text.encode()
-        rc = _lib.load().qsim_circuit_parse_text(raw, len(raw), byref(h))
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_circuit_error() or b"").decode())
-        return cls(h)
-
-    @classmethod
-    def from_gates(cls, num_q: int, gates: Iterable[Sequence]) -> "Circuit":
-        """gates in the tuple form of circuits.random_gates."""
-        c = cls.empty(num_q)
-        cache = {}
-        for g in gates:
-            if g[0] == "cx":
-                c.append_cx(g[1], g[2])
-            elif g[0] == "rz":
-                c.append_1q(gate_matrix(f"rz({g[1]!r})"), g[2])
-            else:
-                if g[0] not in cache:
-                    cache[g[0]] = gate_matrix(g[0])
-                c.append_1q(cache[g[0]], g[1])
-        return c
-
-    def append_1q(self, U, target: int) -> None:
-        check(_lib.load().qsim_circuit_append_1q(self._h, _dp(_mat(U, 2)), target))
-
-    def append_cx(self, control: int, target: int) -> None:
-        check(_lib.load().qsim_circuit_append_cx(self._h, control, target))
-
-    def append_2q(self, U, q_hi: int, q_lo: int) -> None:
-        check(_lib.load().qsim_circuit_append_2q(self._h, _dp(_mat(U, 4)), q_hi, q_lo))
-
-    @property
-    def num_qubits(self) -> int:
-        return _lib.load().qsim_circuit_num_qubits(self._h)
-
-    def __len__(self) -> int:
-        return int(_lib.load().qsim_circuit_num_gates(self._h))
-
-    def gate(self, i: int):
-        kind, q0, q1 = c_int(), c_int(), c_int()
-        u = np.zeros(32)
-        check(_lib.load().qsim_circuit_gate(self._h, i, byref(kind), byref(q0), byref(q1), _dp(u)))
-        if kind.value == _lib.GATE_U1:
-            return ("u1", q0.value, u[:8].view(np.complex128).reshape(2, 2).copy())
-        if kind.value == _lib.GATE_CX:
-            return ("cx", q0.value, q1.value)
-        return ("u2", q0.value, q1.value, u.view(np.complex128).reshape(4, 4).copy())
-
-    def plan(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, initial_support: int = 0) -> dict:
-        """Launches and algorithmic bytes of the schedule (host only).  initial_support: index bits that may be 1 in the state
-        the circuit finds (0: fresh from a reset; all ones: dense)."""
-        st = QsimStats()
-        check(_lib.load().qsim_plan_circuit_from(self._h, fuse, tile_bits, tile_low_bits, initial_support, byref(st)))
-        return st.as_dict()
-
-    def passes(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, initial_support: int = 0) -> list:
-        """qsim_plan_passes: the schedule pass by pass (host only) — kernel class, blocks, the index bits inside the tile, the
-        fraction of the register visited, algorithmic bytes and the bytes-equivalent of the pass-time model."""
-        from ctypes import c_int
-        cap = 4096
-        buf = (_lib.QsimPassInfo * cap)()
-        n = c_int()
-        check(_lib.load().qsim_plan_passes(self._h, fuse, tile_bits, tile_low_bits, initial_support, buf, cap, byref(n)))
-        return [{"kernel": _lib.K_NAMES[buf[i].kernel_class], "blocks": int(buf[i].blocks), "tile_mask": int(buf[i].tile_mask),
-                 "visited": float(buf[i].visited), "bytes": float(buf[i].bytes), "cost_bytes": float(buf[i].cost_bytes)}
-                for i in range(min(n.value, cap))]
-
-    def regions(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, initial_support: int = 0,
-                defer: bool = False, setting: dict = None) -> list:
-        """qsim_plan_regions: per pass of schedule() with the same arguments (defer: of schedule(flips=[])) what
-        QSIM_OPT_AFFINE_SUPPORT adds — the tiles to visit (origin, gen), the parity checks of the region the previous pass wrote
-        as (mask, parity) pairs, and the shares of the register written and read.  setting: of schedule(setting=...)."""
-        from ctypes import c_int
-        cap = 4096
-        buf = (_lib.QsimPassRegion * cap)()
-        n = c_int()
-        if setting is not None:
-            if fuse != 3 or defer:
-                raise ValueError("regions: a setting goes with fuse=3 and states its own defer")
-            check(_lib.load().qsim_plan_regions_with(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support,
-                                                     byref(_lib.QsimSchedSetting.of(setting)), buf, cap, byref(n)))
-        else:
-            check(_lib.load().qsim_plan_regions(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(defer)), buf, cap, byref(n)))
-        return [{"kernel": _lib.K_NAMES[r.kernel_class], "on": bool(r.on), "refined": bool(r.refined), "tile_mask": int(r.tile_mask),
-                 "support_before": int(r.support_before), "origin": int(r.origin), "gen": [int(r.gen[j]) for j in range(r.n_gen)],
-                 "checks": [(int(r.check_mask[j]), int(r.check_parity >> j & 1)) for j in range(r.n_checks)],
-                 "visited": float(r.visited), "read_share": float(r.read_share)}
-                for r in (buf[i] for i in range(min(n.value, cap)))]
-
-    def plan_choice(self, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, initial_support: int = 0, f32: bool = False,
-                    with_defer: bool = True) -> dict:
-        """qsim_plan_choice: what the planning step's model would choose for this circuit (host only) — every candidate setting in
-        candidate order with its price ("candidates"), the index of the choice ("chosen") and the host seconds of the ranking."""
-        from ctypes import c_int, c_double
-        cap = 4096
-        buf = (_lib.QsimSchedSetting * cap)()
-        n, chosen, seconds = c_int(), c_int(), c_double()
-        check(_lib.load().qsim_plan_choice(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support, int(bool(f32)), int(bool(with_defer)),
-                                           buf, cap, byref(n), byref(chosen), byref(seconds)))
-        return {"candidates": [buf[i].as_dict() for i in range(min(n.value, cap))], "chosen": chosen.value, "seconds": seconds.value}
-
-    def schedule(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, flips: list = None,
-                 initial_support: int = 0, setting: dict = None) -> list:
-        """Fused blocks in launch order: (pass, kernel_class, kind, qubits, matrix|None, gates_folded); kind is
-        "u1" / "cx" / "u2" ... "u8", qubits most significant first (cx: control, target).  flips: a list — the schedule with
-        the X gates deferred (qsim_schedule_circuit_deferred); the residual index mask is appended to it.  initial_support
-        (without flips): the index bits that may be 1 in the state the circuit finds (qsim_schedule_circuit_from).  setting: a
-        candidate of the planning step as a dict (fields of qsim_sched_setting; those left out are the options' own) — the level-3
-        schedule under it (qsim_schedule_circuit_with); where it defers, pass flips=[] to receive the mask."""
-        out = []
-
-        def cb(_user, pass_i, kclass, kind, qubits, nq, U, folded):
-            qs = tuple(qubits[i] for i in range(nq))
-            m = None
-            if kind != _lib.GATE_CX:
-                d = 1 << nq
-                m = np.ctypeslib.as_array(U, shape=(2 * d * d,)).copy().view(np.complex128).reshape(d, d)
-            out.append((pass_i, _lib.K_NAMES[kclass], {1: "u1", 2: "cx", 3: "u2", 4: "u3", 5: "u4", 6: "u5", 7: "u6", 8: "u7", 9: "u8"}[kind], qs, m, folded))
-
-        if setting is not None:
-            if fuse != 3 or (flips is None) != (not setting.get("defer")):
-                raise ValueError("schedule: a setting goes with fuse=3, and with flips=[] exactly when it defers")
-            mask = ctypes.c_uint64()
-            check(_lib.load().qsim_schedule_circuit_with(self._h, tile_bits, tile_low_bits, tile_max_ops, initial_support,
-                                                         byref(_lib.QsimSchedSetting.of(setting)), _lib.SCHED_CB(cb), None, byref(mask)))
-            if flips is not None:
-                flips.append(int(mask.value))
-            return out
-        if flips is None:
-            check(_lib.load().qsim_schedule_circuit_from(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, initial_support, _lib.SCHED_CB(cb), None))
-            return out
-        if initial_support:
-            raise ValueError("schedule: initial_support goes with flips=None")
-        mask = ctypes.c_uint64()
-        check(_lib.load().qsim_schedule_circuit_deferred(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, _lib.SCHED_CB(cb), None,
-                                                         byref(mask)))
-        flips.append(int(mask.value))
-        return out
-
-    def tile_records(self, fuse: int = 3, tile_bits: int = 12, tile_low_bits: int = 3, tile_max_ops: int = 32, f32: bool = False,
-                     order_seed: int = 0) -> list:
-        """qsim_tile_records: every block of every tile pass of the schedule() with the same arguments, as a dict: pass,
-        tile_bits, low_bits, high (global bit of each high tile-local bit, in order), selectors and qubits (most significant
-        first), matrix (on selectors + qubits) and record, the encoded TileOp as bytes.  order_seed != 0 shuffles each pass's
-        high bits before encoding.  Host only."""
-        out = []
-
-        def cb(_user, pass_i, geom, high, sel, nsel, tq, nq, U, record, nbytes):
-            d = 1 << (nsel + nq)
-            out.append({"pass": pass_i, "tile_bits": geom[0], "low_bits": geom[1], "high": tuple(high[j] for j in range(geom[2])),
-                        "selectors": tuple(sel[a] for a in range(nsel)), "qubits": tuple(tq[a] for a in range(nq)),
-                        "matrix": np.ctypeslib.as_array(U, shape=(2 * d * d,)).copy().view(np.complex128).reshape(d, d),
-                        "record": ctypes.string_at(record, nbytes)})
-
-        check(_lib.load().qsim_tile_records(self._h, fuse, tile_bits, tile_low_bits, tile_max_ops, int(bool(f32)), order_seed,
-                                            _lib.TILE_RECORD_CB(cb), None))
-        return out
-
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_circuit_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-
-def _mask_arrays(masks):
-    """[(x, z)] as two uint64 arrays and their pointers: xs, zs, xp, zp."""
-    from ctypes import c_uint64
-    xs = np.array([m[0] for m in masks], dtype=np.uint64)
-    zs = np.array([m[1] for m in masks], dtype=np.uint64)
-    up = ctypes.POINTER(c_uint64)
-    return xs, zs, xs.ctypes.data_as(up), zs.ctypes.data_as(up)
-
-
-def _pauli_term_masks(paulis, num_q: int):
-    """Distinct strings of `paulis` as mask arrays, and for every entry the position of its string among them."""
-    from .pauli import pauli_masks
-    index, where = {}, []
-    for text in paulis:
-        where.append(index.setdefault(pauli_masks(text, num_q), len(index)))
-    return _mask_arrays(index) + (np.array(where, dtype=np.intp),)
-
-
-def _rotation_arrays(rotations, num_q: int):
-    """(theta, string) pairs as the arrays qsim_apply_pauli_rotations takes, in order: xs, zs, thetas and their pointers."""
-    from .pauli import pauli_masks
-    rotations = list(rotations)
-    xs, zs, xp, zp = _mask_arrays([pauli_masks(text, num_q) for _, text in rotations])
-    thetas = np.array([float(theta) for theta, _ in rotations], dtype=np.float64)
-    return xs, zs, thetas, xp, zp, _dp(thetas)
-
-
-def _split_controls(rotations):
-    """(theta, string) and (theta, string, controls) entries, mixed, as ([(theta, string)], [controls]); controls () where none."""
-    pairs, controls = [], []
-    for entry in rotations:
-        entry = tuple(entry)
-        if len(entry) not in (2, 3):
-            raise ValueError(f"a rotation is (theta, string) or (theta, string, controls), not {entry!r}")
-        pairs.append(entry[:2])
-        controls.append(tuple(entry[2]) if len(entry) == 3 else ())
-    return pairs, controls
-
-
-def _hamiltonian_arrays(terms, num_q: int):
-    """(real coefficient, string) pairs as the arrays qsim_pauli_gradient and qsim_pauli_sum_into take: xs, zs, coeffs and their
-    pointers.  ValueError for a complex coefficient."""
-    from .pauli import pauli_masks
-    terms = list(terms)
-    for coeff, text in terms:
-        if isinstance(coeff, complex) or (hasattr(coeff, "dtype") and coeff.dtype.kind == "c"):
-            raise ValueError(f"coefficient {coeff!r} of {text!r} is complex: a Hamiltonian's coefficients are real")
-    xs, zs, xp, zp = _mask_arrays([pauli_masks(text, num_q) for _, text in terms])
-    coeffs = np.array([float(c) for c, _ in terms], dtype=np.float64)
-    return xs, zs, coeffs, xp, zp, _dp(coeffs)
-
-
-def _weighted_sum(terms, evaluate):
-    """sum_t c_t <P_t> for (coefficient, string) pairs: a float when every coefficient is real, else a complex."""
-    terms = list(terms)
-    coeffs = [c for c, _ in terms]
-    values = evaluate([p for _, p in terms])
-    if all(isinstance(c, (int, float, np.integer, np.floating)) for c in coeffs):
-        return float(np.dot(np.asarray(coeffs, dtype=np.float64), values))
-    return complex(np.dot(np.asarray(coeffs, dtype=np.complex128), values))
-
-
-class _PauliStrings:
-    """Pauli strings on a state: what Simulator and Cluster share.  A class names its two C functions (_expect_fn, _rotate_fn) and
-    has _check(rc); the strings of a Cluster name LOGICAL qubits."""
-
-    def expectation_terms(self, paulis) -> np.ndarray:
-        """<psi|P|psi> for every Pauli string of `paulis` ("X0 Z3 Y17", see pauli_masks), computed on the device
-        (qsim_expect_paulis, qsim_cluster_expect_paulis): one float64 per string, in the caller's order.  Equal strings are
-        evaluated once.  On a Cluster the strings name LOGICAL qubits."""
-        xs, zs, xp, zp, where = _pauli_term_masks(paulis, self.num_qubits)
-        out = np.empty(xs.size, dtype=np.float64)
-        self._check(getattr(_lib.load(), self._expect_fn)(self._h, xp, zp, xs.size, _dp(out)))
-        return out[where]
-
-    def expectation(self, terms):
-        """sum_t c_t <P_t> for an iterable of (coefficient, Pauli string): <psi|H|psi> of H = sum_t c_t P_t.  A float when
-        every coefficient is real, else a complex."""
-        return _weighted_sum(terms, self.expectation_terms)
-
-    def apply_pauli_rotation(self, theta: float, pauli: str, controls=()) -> None:
-        """state <- exp(-i theta/2 P) state for the Pauli string P ("X0 Y3 Z17", see pauli_masks); on a Cluster the string
-        names LOGICAL qubits.  `controls` (a Simulator only): qubit numbers; the rotation then acts where all of them are 1."""
-        self.apply_pauli_rotations([(theta, pauli, controls)])
-
-    def apply_pauli_rotations(self, rotations) -> None:
-        """exp(-i theta/2 P) for every (theta, string) of `rotations`, the first one first, as ONE call of
-        qsim_apply_pauli_rotations (qsim_cluster_apply_pauli_rotations): consecutive strings with X/Y on the same qubits share
-        a sweep of the state.  Returns without waiting.
-        An entry may be (theta, string, controls) instead, controls being qubit numbers: that rotation acts only where every
-        control qubit is 1 (qsim_apply_controlled_pauli_rotations: a sweep of 2^-c of the state for c controls; consecutive
-        terms share it under one control set).  ValueError for a control named twice, outside the register, or named by the
-        string too — and for any control on a Cluster: sharded states have no controlled rotations yet."""
-        pairs, controls = _split_controls(rotations)
-        xs, zs, thetas, xp, zp, tp = _rotation_arrays(pairs, self.num_qubits)
-        if any(controls):
-            self._apply_controlled(pairs, controls, xp, zp, tp)
-        else:
-            self._check(getattr(_lib.load(), self._rotate_fn)(self._h, xp, zp, tp, xs.size))
-
-    def _apply_controlled(self, pairs, controls, xp, zp, tp) -> None:
-        raise ValueError("sharded states have no controlled rotations yet")
-
-    def evolve(self, terms, time: float, steps: int = 1, order: int = 1) -> None:
-        """A product formula for exp(-i H time) with H = sum_k c_k P_k given as (c_k, string) pairs, real c_k
-        (pauli.trotter_rotations builds the list: order 1 or 2, `steps` steps), applied as one call."""
-        from .pauli import trotter_rotations
-        self.apply_pauli_rotations(trotter_rotations(terms, time, steps, order))
-
-
-def _diagonal_term_arrays(terms, num_q: int):
-    """(real coefficient, string of I and Z) pairs as the arrays qsim_diagonal_add_terms takes: zs, coeffs and their pointers.
-    ValueError for an X or Y factor or a complex coefficient — pure Python, before anything touches the library."""
-    from ctypes import c_uint64
-    from .pauli import pauli_masks
-    terms = list(terms)
-    masks = []
-    for coeff, text in terms:
-        if isinstance(coeff, complex) or (hasattr(coeff, "dtype") and coeff.dtype.kind == "c"):
-            raise ValueError(f"coefficient {coeff!r} of {text!r} is complex: a diagonal table is real")
-        x, z = pauli_masks(text, num_q)
-        if x:
-            raise ValueError(f"{text!r} has an X or Y factor: a diagonal operator is a sum of strings of I and Z")
-        masks.append(z)
-    zs = np.array(masks, dtype=np.uint64)
-    coeffs = np.array([float(c) for c, _ in terms], dtype=np.float64)
-    return zs, coeffs, zs.ctypes.data_as(ctypes.POINTER(c_uint64)), _dp(coeffs)
-
-
-class Diagonal:
-    """A real table d[0..2^n) of float64 on one GPU: the operator D = sum_i d_i |i><i| on a register of n qubits (qsim_diagonal).
-    Simulator.apply_diagonal_phase applies exp(-i gamma D) and Simulator.expectation_diagonal returns <D>, each in one sweep
-    whatever the number of terms D has.  `ptr` adopts 2^n float64 values already on the device (tensor.data_ptr() of a torch
-    tensor, say); the caller keeps them alive and nothing is freed.  Calls take effect in the order issued."""
-
-    def __init__(self, num_q: int, device: int = 0, ptr: Optional[int] = None):
-        self._h = c_void_p()
-        lib = _lib.load()
-        if ptr is None:
-            check(lib.qsim_diagonal_create(byref(self._h), num_q, device))
-        else:
-            check(lib.qsim_diagonal_create_external(byref(self._h), num_q, device, c_void_p(ptr)))
-        self.num_qubits = num_q
-
-    @classmethod
-    def from_terms(cls, num_q: int, terms, device: int = 0) -> "Diagonal":
-        """The diagonal of sum_k c_k P_k for (c_k, string) pairs, strings of I and Z only ("Z0 Z7"): ValueError for X or Y,
-        before any launch."""
-        arrays = _diagonal_term_arrays(terms, num_q)
-        diag = cls(num_q, device)
-        diag._add(arrays)
-        return diag
-
-    def _add(self, arrays) -> None:
-        zs, coeffs, zp, cp = arrays
-        check(_lib.load().qsim_diagonal_add_terms(self._h, zp, cp, zs.size))
-
-    def add_terms(self, terms) -> None:
-        """d_i += c_k (-1)^popcount(i & z_k), term after term in the order given: bit for bit the sequential sum."""
-        self._add(_diagonal_term_arrays(terms, self.num_qubits))
-
-    def write(self, values, first: int = 0) -> None:
-        v = np.ascontiguousarray(values, dtype=np.float64)
-        check(_lib.load().qsim_diagonal_write(self._h, first, v.size, _dp(v)))
-
-    def read(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
-        if count is None:
-            count = (1 << self.num_qubits) - first
-        out = np.empty(count, dtype=np.float64)
-        check(_lib.load().qsim_diagonal_read(self._h, first, count, _dp(out)))
-        return out
-
-    def extrema(self) -> dict:
-        """{"min", "argmin", "max", "argmax"} of the table, one reduction on the device; among equal values the lowest index."""
-        from ctypes import c_uint64
-        lo, hi, ilo, ihi = c_double(), c_double(), c_uint64(), c_uint64()
-        check(_lib.load().qsim_diagonal_extrema(self._h, byref(lo), byref(ilo), byref(hi), byref(ihi)))
-        return {"min": float(lo.value), "argmin": int(ilo.value), "max": float(hi.value), "argmax": int(ihi.value)}
-
-    def device_ptr(self) -> int:
-        return int(_lib.load().qsim_diagonal_device_ptr(self._h) or 0)
-
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_diagonal_destroy(self._h)
-            self._h = c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _is_complex(number) -> bool:
-    return isinstance(number, complex) or (hasattr(number, "dtype") and number.dtype.kind == "c")
-
-
-def _split_diagonal_steps(rotations):
-    """The entries of energy_and_gradient's `rotations`, (gamma, Diagonal) steps among them, as (entries, tables): an entry that is
-    a diagonal phase has its table in `tables` (None elsewhere) and (gamma, "") — the identity string, which the library does not
-    look at — in its place.  ValueError for controls on a diagonal entry, a complex gamma, a closed table.  Pure Python."""
-    entries, tables = [], []
-    for entry in rotations:
-        entry = tuple(entry)
-        if len(entry) >= 2 and isinstance(entry[1], Diagonal):
-            if len(entry) > 3 or (len(entry) == 3 and tuple(entry[2])):
-                raise ValueError(f"a diagonal step is (gamma, diag): it takes no controls, got {entry[2:]!r}")
-            if _is_complex(entry[0]):
-                raise ValueError(f"gamma {entry[0]!r} of a diagonal step is complex")
-            if not entry[1]._h:
-                raise ValueError("a diagonal step names a closed Diagonal")
-            tables.append(entry[1])
-            entries.append((entry[0], ""))
-        else:
-            tables.append(None)
-            entries.append(entry)
-    return entries, tables
-
-
-def _split_diagonal_observable(terms):
-    """energy_and_gradient's `terms` as (Pauli terms, table or None, weight): a Diagonal alone is the whole observable with weight 1,
-    and a list may hold one (w, Diagonal) among its (coefficient, string) pairs.  ValueError for two diagonal parts, a complex
-    weight, a closed table.  Pure Python."""
-    if isinstance(terms, Diagonal):
-        terms = [(1.0, terms)]
-    paulis, table, weight = [], None, 0.0
-    for term in terms:
-        if len(term) == 2 and isinstance(term[1], Diagonal):
-            if table is not None:
-                raise ValueError("the observable has two diagonal parts: add the tables up into one Diagonal")
-            if _is_complex(term[0]):
-                raise ValueError(f"weight {term[0]!r} of the diagonal part is complex: a Hamiltonian's coefficients are real")
-            if not term[1]._h:
-                raise ValueError("the observable names a closed Diagonal")
-            table, weight = term[1], float(term[0])
-        else:
-            paulis.append(term)
-    return paulis, table, weight
-
-
-class Simulator(_PauliStrings):
+class Simulator(_PauliStrings, _lib.Handle):
     """One state vector resident on one GPU."""
-    _expect_fn, _rotate_fn, _check = "qsim_expect_paulis", "qsim_apply_pauli_rotations", staticmethod(check)
+    _expect_fn, _rotate_fn, _check, _free = "qsim_expect_paulis", "qsim_apply_pauli_rotations", staticmethod(check), "qsim_destroy"
 
     def __init__(self, num_q: int, device: int = 0, *, fuse: Optional[int] = None, profile: bool = False,
                  external_ptr: Optional[int] = None, precision: int = 64, **options):
@@ -529,12 +79,7 @@ class Simulator(_PauliStrings):
         rxs, rzs, thetas, rxp, rzp, tp = _rotation_arrays(pairs, self.num_qubits)
         hxs, hzs, coeffs, hxp, hzp, cp = _hamiltonian_arrays(terms, self.num_qubits)
         energy, grad = c_double(0.0), np.zeros(rxs.size, dtype=np.float64)
-        cs = csp = None  # the control masks, where any entry has controls
-        if any(controls):
-            from ctypes import c_uint64
-            from .pauli import control_mask
-            cs = np.array([control_mask(c, self.num_qubits, text) for (_, text), c in zip(pairs, controls)], dtype=np.uint64)
-            csp = cs.ctypes.data_as(ctypes.POINTER(c_uint64))
+        cs, csp = _control_masks(pairs, controls, self.num_qubits)  # None where no entry has controls
         if obs is not None or any(t is not None for t in tables):
             steps = (c_void_p * max(len(tables), 1))(*[t._h.value if t is not None else None for t in tables])
             check(_lib.load().qsim_diagonal_gradient(self._h, rxs.size, steps, csp, rxp, rzp, tp, hxp, hzp, cp, hxs.size, obs._h if obs is not None else None,
@@ -588,10 +133,8 @@ class Simulator(_PauliStrings):
 
     # -- controlled rotations (single states only)
     def _apply_controlled(self, pairs, controls, xp, zp, tp) -> None:
-        from ctypes import c_uint64
-        from .pauli import control_mask
-        cs = np.array([control_mask(c, self.num_qubits, text) for (_, text), c in zip(pairs, controls)], dtype=np.uint64)
-        check(_lib.load().qsim_apply_controlled_pauli_rotations(self._h, cs.ctypes.data_as(ctypes.POINTER(c_uint64)), xp, zp, tp, cs.size))
+        cs, csp = _control_masks(pairs, controls, self.num_qubits)
+        check(_lib.load().qsim_apply_controlled_pauli_rotations(self._h, csp, xp, zp, tp, cs.size))
 
     def apply_mcphase(self, phi: float, qubits) -> None:
         """diag(1, ..., 1, e^(i phi)) on `qubits`: the phase e^(i phi) where all of them are 1 — the controlled identity string
@@ -625,23 +168,6 @@ class Simulator(_PauliStrings):
     def reset(self, holds_index0: bool = True) -> None:
         check(_lib.load().qsim_reset_shard(self._h, 1 if holds_index0 else 0))
 
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_destroy(self._h)
-            self._h = c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- gates
     def apply_1q(self, U, target: int) -> None:
         check(_lib.load().qsim_apply_1q(self._h, _dp(_mat(U, 2)), target))
@@ -664,8 +190,7 @@ class Simulator(_PauliStrings):
         dim = 1 << min(len(ts), 5)
         if len(ts) > 5 or m.size != dim * dim or m.ndim > 2 or (m.ndim == 2 and m.shape != (dim, dim)):
             raise ValueError(f"apply_matrix: at most 5 targets and a matrix of shape (2^k, 2^k); got {len(ts)} targets and shape {m.shape}")
-        flat = np.ascontiguousarray(m.reshape(-1)).view(np.float64)
-        check(_lib.load().qsim_apply_matrix(self._h, _dp(flat), (c_int * max(len(ts), 1))(*ts), len(ts), (c_int * max(len(cs), 1))(*cs), len(cs)))
+        check(_lib.load().qsim_apply_matrix(self._h, _dp(_mat(m, dim)), _ints(ts), len(ts), _ints(cs), len(cs)))
 
     # -- permutations of the basis states of up to ten qubits (single states only: a Cluster has no counterpart)
     def apply_permutation(self, perm, targets, controls=(), inverse: bool = False) -> None:
@@ -682,8 +207,8 @@ class Simulator(_PauliStrings):
         if inverse:
             table = permutations.inverse_table(table)
         table = np.ascontiguousarray(table, dtype=np.uint32)
-        check(_lib.load().qsim_apply_permutation(self._h, table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), (c_int * max(len(ts), 1))(*ts), len(ts),
-                                                 (c_int * max(len(cs), 1))(*cs), len(cs)))
+        check(_lib.load().qsim_apply_permutation(self._h, table.ctypes.data_as(ctypes.POINTER(c_uint32)), _ints(ts), len(ts),
+                                                 _ints(cs), len(cs)))
 
     def apply_function_xor(self, values, inputs, outputs, controls=()) -> None:
         """|x>|y> -> |x>|y ^ values[x]>: bit i of x is inputs[i], bit i of y is outputs[i]; a bit oracle for any function of up to
@@ -712,7 +237,7 @@ class Simulator(_PauliStrings):
         launched after the queued gates and not waited for; it does not pass through the gate queue.  max_digit_bits (1 ... 10) caps
         the digits, for tests and tuning; 0 leaves the choice to the plan.  An empty register is accepted and does nothing."""
         qs = [int(q) for q in qubits]
-        check(_lib.load().qsim_apply_qft(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), 1 if inverse else 0, int(max_digit_bits)))
+        check(_lib.load().qsim_apply_qft(self._h, _ints(qs), len(qs), 1 if inverse else 0, int(max_digit_bits)))
 
     # -- whole-register diagonal operators from a table (single states only: a Cluster has no counterpart)
     def apply_diagonal_phase(self, diag: Diagonal, gamma: float) -> None:
@@ -742,7 +267,6 @@ class Simulator(_PauliStrings):
 
     def plan_cache_stats(self) -> dict:
         """qsim_plan_cache_stats: plans held, replays, key matches rejected by the identity check."""
-        from ctypes import c_uint64
         a, b, c = c_uint64(), c_uint64(), c_uint64()
         check(_lib.load().qsim_plan_cache_stats(self._h, byref(a), byref(b), byref(c)))
         return {"plans": int(a.value), "replays": int(b.value), "key_collisions": int(c.value)}
@@ -750,7 +274,6 @@ class Simulator(_PauliStrings):
     def deferred_flip_stats(self) -> dict:
         """qsim_deferred_flip_stats: flushes whose last tile pass applied the deferred X gates' index flip, and flushes that
         had to run them in a pass of their own."""
-        from ctypes import c_uint64
         a, b = c_uint64(), c_uint64()
         check(_lib.load().qsim_deferred_flip_stats(self._h, byref(a), byref(b)))
         return {"applied": int(a.value), "fallbacks": int(b.value)}
@@ -772,15 +295,15 @@ class Simulator(_PauliStrings):
         """qsim_flush_pack: everything queued is launched and the state ends re-laid-out in `out_ptr` (default: the spare
         buffer); returns (buffer holding the packed state, whether the last tile pass did the re-layout)."""
         k = len(bits)
-        arr = (c_int * k)(*bits)
-        to = (c_int * k)(*to_bits) if to_bits is not None else None
+        arr = _ints(bits)
+        to = _ints(to_bits) if to_bits is not None else None
         at, fused = c_void_p(), c_int()
         check(_lib.load().qsim_flush_pack(self._h, arr, k, to, konst, c_void_p(out_ptr or 0), needed, skip_blocks, byref(at), byref(fused)))
         return int(at.value or 0), bool(fused.value)
 
     def pack_bits_to(self, bits: Sequence[int], dst_ptrs: Sequence[int]) -> None:
         """qsim_pack_bits_to: block b of the packed layout goes to dst_ptrs[b]."""
-        arr = (c_int * len(bits))(*bits)
+        arr = _ints(bits)
         ptrs = (c_void_p * len(dst_ptrs))(*dst_ptrs)
         check(_lib.load().qsim_pack_bits_to(self._h, arr, len(bits), ptrs))
 
@@ -791,14 +314,12 @@ class Simulator(_PauliStrings):
     def support_after(self, circuit: Circuit, support: int = 0) -> int:
         """qsim_support_after: where the state can be non-zero after `circuit` ran on a state with this support, as the engine
         will track it (scheduled as a flush would schedule it; nothing runs)."""
-        from ctypes import c_uint64
         out = c_uint64()
         check(_lib.load().qsim_support_after(self._h, circuit._h, support & 0xFFFFFFFFFFFFFFFF, byref(out)))
         return int(out.value)
 
     def get_support(self):
         """(support mask, pending basis state?, its amplitude) — qsim_get_support."""
-        from ctypes import c_uint64
         m, k, a = c_uint64(), c_int(), c_double()
         check(_lib.load().qsim_get_support(self._h, byref(m), byref(k), byref(a)))
         return int(m.value), bool(k.value), float(a.value)
@@ -829,7 +350,7 @@ class Simulator(_PauliStrings):
         row or column index is qubits[j].  One read-only sweep of the state on the device (qsim_reduced_density); exactly
         Hermitian, fp64 sums in both precisions, equal calls return equal bits.  Not normalised: its trace is norm2()."""
         qs = [int(q) for q in qubits]
-        arr = (c_int * max(len(qs), 1))(*qs)
+        arr = _ints(qs)
         out = np.zeros(2 << (2 * len(qs)) if len(qs) <= 5 else 2, dtype=np.float64)  # more than 5: the library refuses
         check(_lib.load().qsim_reduced_density(self._h, arr, len(qs), _dp(out)))
         return out.view(np.complex128).reshape(1 << len(qs), 1 << len(qs))
@@ -854,7 +375,7 @@ class Simulator(_PauliStrings):
         reduced_density_matrix, bit for bit; 6 to 10 run R R^T in blocks and slices on the matrix cores (qsim_subsystem_density;
         DESIGN §7m) and read the state 2^(k-6) times."""
         qs = [int(q) for q in qubits]
-        arr = (c_int * max(len(qs), 1))(*qs)
+        arr = _ints(qs)
         out = np.zeros(2 << (2 * len(qs)) if len(qs) <= 10 else 2, dtype=np.float64)  # more than 10: the library refuses
         check(_lib.load().qsim_subsystem_density(self._h, arr, len(qs), _dp(out)))
         return out.view(np.complex128).reshape(1 << len(qs), 1 << len(qs))
@@ -892,7 +413,7 @@ class Simulator(_PauliStrings):
 
     def pack_bits(self, bits: Sequence[int], dst_ptr: int) -> None:
         """Shard re-layout ahead of a global<->local qubit exchange (qsim_pack_bits)."""
-        arr = (c_int * len(bits))(*bits)
+        arr = _ints(bits)
         check(_lib.load().qsim_pack_bits(self._h, arr, len(bits), c_void_p(dst_ptr)))
 
     def scale(self, z: complex) -> None:
@@ -915,10 +436,9 @@ class Simulator(_PauliStrings):
 
     def sample(self, randoms) -> np.ndarray:
         """Basis index measurement() (quantum_simulator.c:270-283) returns for each random number in [0, 1]."""
-        from ctypes import c_uint64
         r = np.ascontiguousarray(randoms, dtype=np.float64)
         out = np.zeros(r.size, dtype=np.uint64)
-        check(_lib.load().qsim_sample(self._h, _dp(r), r.size, out.ctypes.data_as(ctypes.POINTER(c_uint64))))
+        check(_lib.load().qsim_sample(self._h, _dp(r), r.size, _u64p(out)))
         return out
 
     def sample_shots(self, shots: Optional[int] = None, qubits=None, *, seed=None, draws=None) -> np.ndarray:
@@ -927,7 +447,6 @@ class Simulator(_PauliStrings):
         reproducible pipeline), or `shots`, for which np.random.default_rng(seed).random(shots) is drawn here.  The draws are scaled by
         the state's own total, so an unnormalised state samples |a|^2 / norm2; an index of probability zero is never returned.  Pending
         gates are launched first; the state is not changed."""
-        from ctypes import c_uint64
         if (draws is None) == (shots is None):
             raise ValueError("sample_shots takes either shots or draws")
         if draws is None:
@@ -938,9 +457,9 @@ class Simulator(_PauliStrings):
             raise ValueError("a seed goes with shots, not with draws")
         u = np.ascontiguousarray(draws, dtype=np.float64).reshape(-1)
         qs = [] if qubits is None else [int(q) for q in qubits]
-        arr = (c_int * len(qs))(*qs) if qs else None
+        arr = _ints(qs) if qs else None
         out = np.zeros(u.size, dtype=np.uint64)
-        check(_lib.load().qsim_sample_shots(self._h, _dp(u), u.size, arr, len(qs), out.ctypes.data_as(ctypes.POINTER(c_uint64))))
+        check(_lib.load().qsim_sample_shots(self._h, _dp(u), u.size, arr, len(qs), _u64p(out)))
         return out
 
     def sample_counts(self, shots: int, qubits=None, seed=None) -> dict:
@@ -969,7 +488,7 @@ class Simulator(_PauliStrings):
         if int(outcome) < 0 or int(outcome) >> 64:
             raise ValueError(f"postselect: the outcome is a non-negative integer below 2^k, got {outcome!r}")
         w = c_double()
-        check(_lib.load().qsim_postselect(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), int(outcome), byref(w)))
+        check(_lib.load().qsim_postselect(self._h, _ints(qs), len(qs), int(outcome), byref(w)))
         return w.value
 
     def measure(self, qubits, *, seed=None, draw=None, return_probability: bool = False):
@@ -978,10 +497,9 @@ class Simulator(_PauliStrings):
         qubits=qubits)[0] for the same state and number u in [0, 1]: `draw` is that number (a reproducible pipeline), otherwise it comes
         from `seed` the way sample_shots(1, seed=seed) makes its draw.  An unnormalised state measures |a|^2 / norm2; afterwards the
         state has norm 1 (qsim_measure)."""
-        from ctypes import c_uint64
         qs = [int(q) for q in qubits]
         out, p = c_uint64(), c_double()
-        check(_lib.load().qsim_measure(self._h, (c_int * max(len(qs), 1))(*qs), len(qs), self._one_draw("measure", seed, draw), byref(out), byref(p)))
+        check(_lib.load().qsim_measure(self._h, _ints(qs), len(qs), self._one_draw("measure", seed, draw), byref(out), byref(p)))
         return (int(out.value), p.value) if return_probability else int(out.value)
 
     def reset_qubits(self, qubits, *, seed=None, draw=None) -> int:
@@ -1038,7 +556,6 @@ class Simulator(_PauliStrings):
 
     def launch_log(self) -> list:
         """[(kernel, n_ops, high_mask, ms)] per launch since reset_stats (profile mode)."""
-        from ctypes import c_uint64
         lib = _lib.load()
         n = lib.qsim_launch_log(self._h, -1, None, None, None, None)
         out = []
@@ -1062,7 +579,6 @@ class Simulator(_PauliStrings):
     def launch_log_blocks(self) -> list:
         """Per launch since reset_stats: [(entries_per_row, tile_qubits, mostly_identity, selector_qubits)] of a tile pass's blocks
         ([] for other kernels) — qsim_launch_log_blocks, the data behind the pass-time model."""
-        from ctypes import c_ubyte
         lib = _lib.load()
         n = lib.qsim_launch_log(self._h, -1, None, None, None, None)
         out = []
@@ -1076,7 +592,6 @@ class Simulator(_PauliStrings):
         """Per launch since reset_stats: [(nq, terms, nsel, flags, info)] of a tile pass's blocks ([] for other kernels), read from
         the headers of the records the kernel was given — nq after padding, entries per row, selector qubits, TileOp::flags and
         b[7] (qsim_launch_log_block_flags; profile = 2)."""
-        from ctypes import c_ubyte
         lib = _lib.load()
         n = lib.qsim_launch_log(self._h, -1, None, None, None, None)
         out = []
@@ -1088,253 +603,6 @@ class Simulator(_PauliStrings):
 
     def reset_stats(self) -> None:
         check(_lib.load().qsim_reset_stats(self._h))
-
-
-class Cluster(_PauliStrings):
-    """qsim_cluster: P shards driven by this one process (the C host's multi-GPU path; repeat a device for virtual shards)."""
-    _expect_fn, _rotate_fn = "qsim_cluster_expect_paulis", "qsim_cluster_apply_pauli_rotations"
-
-    def __init__(self, num_q: int, num_shards: int, devices: Optional[Sequence[int]] = None, **options):
-        self._h = c_void_p()
-        lib = _lib.load()
-        arr = (c_int * num_shards)(*devices) if devices is not None else None
-        rc = lib.qsim_cluster_create(byref(self._h), num_q, num_shards, arr)
-        if rc:
-            raise _lib.QsimError(rc, (lib.qsim_cluster_error() or b"").decode())
-        self.num_qubits, self.num_shards = num_q, num_shards
-        names = {"fuse": _lib.OPT_FUSE, "tile_bits": _lib.OPT_TILE_BITS, "tile_low_bits": _lib.OPT_TILE_LOW_BITS,
-                 "tile_max_ops": _lib.OPT_TILE_MAX_OPS, "profile": _lib.OPT_PROFILE, "pingpong": _lib.OPT_PINGPONG,
-                 "affine_support": _lib.OPT_AFFINE_SUPPORT}
-        for key in sorted(options, key=lambda k: k != "tile_low_bits"):
-            self._check(lib.qsim_cluster_set_option(self._h, names[key], int(options[key])))
-
-    def _check(self, rc):
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-
-    def run(self, circuit: Circuit) -> None:
-        lib = _lib.load()
-        self._check(lib.qsim_cluster_reset(self._h))
-        self._check(lib.qsim_cluster_run_circuit(self._h, circuit._h))
-        self._check(lib.qsim_cluster_sync(self._h))
-
-    def plan(self, circuit: Circuit, max_candidates: int = 1, budget_ms: float = 0.0) -> None:
-        """qsim_cluster_plan: schedule choice (and, with max_candidates > 1, measured tile-bit orders) for every shard's local steps."""
-        self._check(_lib.load().qsim_cluster_plan(self._h, circuit._h, max_candidates, budget_ms))
-
-    def read(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
-        if count is None:
-            count = (1 << self.num_qubits) - first
-        out = np.empty(2 * count, dtype=np.float64)
-        self._check(_lib.load().qsim_cluster_read(self._h, first, count, _dp(out)))
-        return out.view(np.complex128)
-
-    def norm2(self) -> float:
-        v = c_double()
-        self._check(_lib.load().qsim_cluster_norm2(self._h, byref(v)))
-        return v.value
-
-    def sample(self, randoms) -> np.ndarray:
-        """measurement() (quantum_simulator.c:270-283) on the sharded state, indices in logical order."""
-        from ctypes import c_uint64
-        r = np.ascontiguousarray(randoms, dtype=np.float64)
-        out = np.zeros(r.size, dtype=np.uint64)
-        self._check(_lib.load().qsim_cluster_sample(self._h, _dp(r), r.size, out.ctypes.data_as(ctypes.POINTER(c_uint64))))
-        return out
-
-    def exchange_stats(self):
-        from ctypes import c_uint64
-        n, b = c_uint64(), c_double()
-        _lib.load().qsim_cluster_exchange_stats(self._h, byref(n), byref(b))
-        return int(n.value), float(b.value)
-
-    def pack_counts(self):
-        """(re-layouts done by the last tile pass in front of an exchange, by the separate pack kernel) per shard and exchange."""
-        from ctypes import c_uint64
-        a, b = c_uint64(), c_uint64()
-        _lib.load().qsim_cluster_pack_counts(self._h, byref(a), byref(b))
-        return int(a.value), int(b.value)
-
-    def exchange_bytes_moved(self) -> float:
-        """Bytes all shards together really sent (blocks of / for shards that hold nothing stay home)."""
-        b = c_double()
-        _lib.load().qsim_cluster_exchange_bytes_moved(self._h, byref(b))
-        return float(b.value)
-
-    @property
-    def exchange_mode(self) -> str:
-        """"rccl" | "direct" | "copies" | "none" (qsim_cluster_exchange_mode)."""
-        return (_lib.load().qsim_cluster_exchange_mode(self._h) or b"").decode()
-
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_cluster_destroy(self._h)
-            self._h = c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ShardPlanHandle:
-    """qsim_shard_plan: the C++ planner's output for one circuit and shard count (host only)."""
-
-    def __init__(self, circuit: Circuit, num_shards: int):
-        self._h = c_void_p()
-        lib = _lib.load()
-        rc = lib.qsim_shard_plan_create(byref(self._h), circuit._h, num_shards)
-        if rc:
-            raise _lib.QsimError(rc, (lib.qsim_cluster_error() or b"").decode())
-        self.num_shards = num_shards
-        self.num_qubits = circuit.num_qubits
-        self.num_steps = lib.qsim_shard_plan_num_steps(self._h)
-
-    def step(self, i: int):
-        """("local",) or ("exchange", shard_bits, local_positions)."""
-        kind, k = c_int(), c_int()
-        J, L = (c_int * 16)(), (c_int * 16)()
-        check(_lib.load().qsim_shard_plan_step(self._h, i, byref(kind), byref(k), J, L))
-        if kind.value == 0:
-            return ("local",)
-        return ("exchange", tuple(J[: k.value]), tuple(L[: k.value]))
-
-    def local_ops(self, i: int, shard: int) -> list:
-        """[("u1", pos, U) | ("cx", a, b) | ("scale", z)] for one shard."""
-        out = []
-
-        def cb(_u, kind, a, b, m):
-            if kind == 1:
-                out.append(("u1", a, np.ctypeslib.as_array(m, shape=(8,)).copy().view(np.complex128).reshape(2, 2)))
-            elif kind == 2:
-                out.append(("cx", a, b))
-            else:
-                out.append(("scale", complex(m[0], m[1])))
-
-        check(_lib.load().qsim_shard_plan_local_ops(self._h, i, shard, _lib.LOCAL_OP_CB(cb), None))
-        return out
-
-    def apply_local(self, i: int, shard: int, sim: "Simulator") -> None:
-        rc = _lib.load().qsim_shard_plan_apply_local(self._h, i, shard, sim._h)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-
-    def step_support(self, i: int):
-        """(mixed_local, mixed_rank) of an exchange step: where the register can be non-zero just before it."""
-        from ctypes import c_uint64
-        a, b = c_uint64(), c_uint64()
-        check(_lib.load().qsim_shard_plan_step_support(self._h, i, byref(a), byref(b)))
-        return int(a.value), int(b.value)
-
-    def exchange_roles(self, i: int, shard: int) -> dict:
-        """qsim_shard_plan_exchange_roles: what one shard sends, receives and holds afterwards in the exchange of step i."""
-        r = _lib.QsimExchangeRoles()
-        check(_lib.load().qsim_shard_plan_exchange_roles(self._h, i, shard, byref(r)))
-        return r.as_dict()
-
-    def final_pos(self) -> list:
-        pos = (c_int * self.num_qubits)()
-        check(_lib.load().qsim_shard_plan_final_pos(self._h, pos))
-        return list(pos)
-
-    def tune(self, shard: int, sim: "Simulator", max_candidates: int = 32, budget_ms: float = 6000.0) -> dict:
-        """qsim_shard_plan_tune: geometry planning for one shard's local steps (leaves `sim` reset)."""
-        rep = _lib.QsimTuneReport()
-        rc = _lib.load().qsim_shard_plan_tune(self._h, shard, sim._h, max_candidates, budget_ms, byref(rep))
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-        return rep.as_dict()
-
-    def predict(self, link_gbps: float = 50.0, pack_gbps: float = 5000.0):
-        """(bytes each rank sends, seconds spent in exchanges) under the planner's cost model (qsim_shard_plan_predict)."""
-        b, t = c_double(), c_double()
-        check(_lib.load().qsim_shard_plan_predict(self._h, link_gbps, pack_gbps, byref(b), byref(t)))
-        return b.value, t.value
-
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_shard_plan_free(self._h)
-            self._h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RankComm:
-    """qsim_rank_comm: this rank's end of the exchanges in a one-process-per-GPU job — RCCL send/recv issued by libqsim
-    on the shard's own stream.  `unique_id()` (rank 0) produces the bytes every rank passes to the constructor."""
-
-    @staticmethod
-    def unique_id() -> bytes:
-        buf = ctypes.create_string_buffer(128)
-        rc = _lib.load().qsim_rccl_unique_id(buf)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-        return buf.raw
-
-    def __init__(self, sim: "Simulator", device: int, world: int, rank: int, uid: bytes, scratch_ptr: Optional[int] = None):
-        self._h = c_void_p()
-        lib = _lib.load()
-        buf = ctypes.create_string_buffer(bytes(uid), 128)
-        rc = lib.qsim_rank_comm_create(byref(self._h), sim._h, device, world, rank, buf,
-                                       c_void_p(scratch_ptr) if scratch_ptr else None)
-        if rc:
-            raise _lib.QsimError(rc, (lib.qsim_cluster_error() or b"").decode())
-
-    def exchange(self, shard_bits: Sequence[int], local_bits: Sequence[int]) -> None:
-        k = len(shard_bits)
-        rc = _lib.load().qsim_rank_comm_exchange(self._h, (c_int * k)(*shard_bits), (c_int * k)(*local_bits), k)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-
-    def exchange_step(self, plan: "ShardPlanHandle", step: int) -> None:
-        """qsim_rank_comm_exchange_step: the exchange of one plan step, leaving out what the plan knows to be zero."""
-        rc = _lib.load().qsim_rank_comm_exchange_step(self._h, plan._h, step)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-
-    def loopback(self, count: int) -> None:
-        """`count` doubles of the shard through ncclSend -> ncclRecv to this same rank (qsim_rank_comm_loopback)."""
-        rc = _lib.load().qsim_rank_comm_loopback(self._h, count)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-
-    def pack_counts(self):
-        """(re-layouts done by the last tile pass in front of an exchange, by the separate pack kernel)."""
-        from ctypes import c_uint64
-        a, b = c_uint64(), c_uint64()
-        _lib.load().qsim_rank_comm_pack_counts(self._h, byref(a), byref(b))
-        return int(a.value), int(b.value)
-
-    def stats(self, reset: bool = False):
-        """(exchanges, bytes sent by this rank, seconds its stream spent in exchanges)."""
-        from ctypes import c_uint64
-        n, b, t = c_uint64(), c_double(), c_double()
-        rc = _lib.load().qsim_rank_comm_stats(self._h, byref(n), byref(b), byref(t), 1 if reset else 0)
-        if rc:
-            raise _lib.QsimError(rc, (_lib.load().qsim_cluster_error() or b"").decode())
-        return int(n.value), float(b.value), float(t.value)
-
-    def close(self) -> None:
-        if self._h:
-            _lib.load().qsim_rank_comm_destroy(self._h)
-            self._h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def run_qasm(path: str, device: int = 0, **sim_options) -> np.ndarray:

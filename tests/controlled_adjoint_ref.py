@@ -174,16 +174,11 @@ def energy_tol(precision, terms, finals=None):
 
 
 def plan(rotations, terms, n, precision=64, null_controls=False):
-    """(adjoint sweeps, sum sweeps, units visited) of [(theta, c, x, z)] and H on n qubits: qsim_controlled_gradient_plan."""
-    import ctypes
-    from gpu_quantum_simulator_amd import _lib
-    up = ctypes.POINTER(ctypes.c_uint64)
-    cs, xs = (np.array([r[i] for r in rotations], dtype=np.uint64) for i in (1, 2))
-    hx = np.array([x for _, x, _ in terms], dtype=np.uint64)
-    a, s, units = ctypes.c_long(-1), ctypes.c_long(-1), ctypes.c_uint64(0)
-    _lib.check(_lib.load().qsim_controlled_gradient_plan(None if null_controls else cs.ctypes.data_as(up), xs.ctypes.data_as(up), xs.size, hx.ctypes.data_as(up),
-                                                         hx.size, n, precision, ctypes.byref(a), ctypes.byref(s), ctypes.byref(units)))
-    return a.value, s.value, units.value
+    """(adjoint sweeps, sum sweeps, units visited) of [(theta, c, x, z)] and H on n qubits: plans.controlled_gradient_plan."""
+    from gpu_quantum_simulator_amd import plans
+    p = plans.ok(plans.controlled_gradient_plan(None if null_controls else [r[1] for r in rotations], [r[2] for r in rotations],
+                                                [x for _, x, _ in terms], n, precision))
+    return p["adjoint_sweeps"], p["sum_sweeps"], p["units_visited"]
 
 
 def weighted_state(n, seed, c, outside=0.1):

@@ -54,15 +54,11 @@ def uncontrolled(rotations):
 
 
 def plan(rotations, n, precision=64):
-    """(sweeps, terms queued as gates, units visited) of [(theta, c, x, z)] on n qubits: qsim_controlled_rotation_plan."""
-    import ctypes
-    from gpu_quantum_simulator_amd import _lib
-    up = ctypes.POINTER(ctypes.c_uint64)
-    cs, xs, zs = (np.array([r[i] for r in rotations], dtype=np.uint64) for i in (1, 2, 3))
-    sweeps, gates, units = ctypes.c_long(-1), ctypes.c_long(-1), ctypes.c_uint64(0)
-    _lib.check(_lib.load().qsim_controlled_rotation_plan(cs.ctypes.data_as(up), xs.ctypes.data_as(up), zs.ctypes.data_as(up), cs.size, n, precision,
-                                                         ctypes.byref(sweeps), ctypes.byref(gates), ctypes.byref(units)))
-    return sweeps.value, gates.value, units.value
+    """(sweeps, terms queued as gates, units visited) of [(theta, c, x, z)] on n qubits: plans.controlled_rotation_plan."""
+    from gpu_quantum_simulator_amd import plans
+    cs, xs, zs = ([r[i] for r in rotations] for i in (1, 2, 3))
+    p = plans.ok(plans.controlled_rotation_plan(cs, xs, zs, n, precision, num_terms=len(cs)))
+    return p["sweeps"], p["queued_as_gates"], p["units_visited"]
 
 
 def takes_the_gate_queue(c, x, z):

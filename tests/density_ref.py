@@ -52,7 +52,7 @@ def shape(f32, kk, q0_in):
 
 
 def plan(qubits, n, f32):
-    """What qsim_reduced_density_plan reports, or None where it refuses."""
+    """What plans.reduced_density_plan reports, or None where it refuses."""
     qubits = list(qubits)
     k = len(qubits)
     if not 0 <= n <= 40 or k > MAX_QUBITS or k > n or len(set(qubits)) != k or any(q < 0 or q >= n for q in qubits):

@@ -10,7 +10,6 @@ U = exp(-i gamma D), dU/dgamma = -i D U, so with |lambda_K> = H |psi_K> and |lam
 taken from psi_k and lambda_k BEFORE the step back (D commutes with U: the product conj(lambda_i) psi_i is the same after it).
 complex64: the factor of a phase is formed in fp64 and rounded once (diagonal_ref.apply_phase), w d_i likewise; every inner product in
 fp64."""
-import ctypes
 from collections import namedtuple
 
 import numpy as np
@@ -147,17 +146,9 @@ def observable_weight(terms, obs):
 
 # ---- the plan probe (host only) -------------------------------------------------------------------------------------------------------
 def plan_call(is_diag_flags, cs, xs, ham_x, has_obs, n, precision, null_flags=False, null_controls=False):
-    """qsim_diagonal_gradient_plan with arrays: (return code, dict)."""
-    from gpu_quantum_simulator_amd import _lib
-    up, bp = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_ubyte)
-    flags = np.array(is_diag_flags, dtype=np.uint8)
-    cs, xs, hx = (np.array(a, dtype=np.uint64) for a in (cs, xs, ham_x))
-    pa, da, ss, tr = (ctypes.c_long(-1) for _ in range(4))
-    per = ctypes.c_int(-1)
-    rc = _lib.load().qsim_diagonal_gradient_plan(None if null_flags else flags.ctypes.data_as(bp), None if null_controls else cs.ctypes.data_as(up),
-                                                  xs.ctypes.data_as(up), xs.size, hx.ctypes.data_as(up), hx.size, 1 if has_obs else 0, n, precision,
-                                                  ctypes.byref(pa), ctypes.byref(da), ctypes.byref(ss), ctypes.byref(per), ctypes.byref(tr))
-    return rc, dict(pauli_adjoint=pa.value, diag_adjoint=da.value, sum_sweeps=ss.value, per_trip=per.value, trips=tr.value)
+    """plans.diagonal_gradient_plan with arrays: (return code, dict)."""
+    from gpu_quantum_simulator_amd import plans
+    return plans.diagonal_gradient_plan(None if null_flags else is_diag_flags, None if null_controls else cs, xs, ham_x, 1 if has_obs else 0, n, precision)
 
 
 def plan(steps, terms, obs, n, precision=64):
@@ -174,7 +165,7 @@ def plan(steps, terms, obs, n, precision=64):
 def loop_n(precision):
     """The smallest n at which the backward diagonal sweep makes more than one trip per workgroup with the grid at its cap."""
     for n in range(41):
-        if plan([Diag(0.0, None)], [], None, n, precision)["trips"] > 1:
+        if plan([Diag(0.0, None)], [], None, n, precision)["diag_adjoint_trips_at_cap"] > 1:
             return n
     raise AssertionError("no register size makes the sweep loop")
 

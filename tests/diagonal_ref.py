@@ -6,7 +6,6 @@ The table of D = sum_k c_k P_k (strings of I and Z): d_i = (...((0 + c_0 s_0(i))
 added in the caller's order — c s is an exact sign flip, so a device that adds in that order returns these bits exactly.
 The phase: a_i <- exp(-i gamma d_i) a_i; for an fp32 state the factor is formed in fp64, rounded once to complex64, and multiplied
 in complex64."""
-from ctypes import byref, c_int, c_long, c_uint64
 
 import numpy as np
 
@@ -56,17 +55,15 @@ def extrema(d):
 
 
 def plan(n, precision):
-    """qsim_diagonal_plan as a dict (host only)."""
-    from gpu_quantum_simulator_amd import _lib
-    items, ip, ie, tp, te = c_uint64(0), c_int(-1), c_int(-1), c_long(-1), c_long(-1)
-    _lib.check(_lib.load().qsim_diagonal_plan(n, precision, byref(items), byref(ip), byref(ie), byref(tp), byref(te)))
-    return dict(items=items.value, per_trip_phase=ip.value, per_trip_expect=ie.value, trips_phase=tp.value, trips_expect=te.value)
+    """plans.diagonal_plan as a dict (host only)."""
+    from gpu_quantum_simulator_amd import plans
+    return plans.ok(plans.diagonal_plan(n, precision))
 
 
 def loop_n(precision):
     """The smallest n at which both sweeps make more than one trip per workgroup with the grid at its cap."""
     for n in range(41):
         p = plan(n, precision)
-        if p["trips_phase"] > 1 and p["trips_expect"] > 1:
+        if p["trips_at_cap_phase"] > 1 and p["trips_at_cap_expect"] > 1:
             return n
     raise AssertionError("no register size makes the sweeps loop")

@@ -90,7 +90,7 @@ HAMILTONIAN = [(-1.0, "Z0 Z1"), (-0.7, "X0"), (-0.7, "X14"), (0.5, "Y3 Z9"), (0.
 DIAGONAL_TERMS = [(0.8, "Z0"), (-0.6, "Z14"), (0.45, "Z3 Z7"), (0.3, "Z1 Z8 Z13"), (-0.2, "Z5 Z9"), (0.15, "")]
 DRAWS = [0.0, 1e-9, 0.03, 0.1, 0.25, 0.4, 0.5, 0.61, 0.75, 0.9, 0.999, 0.9999999, 1.0]
 
-# multi-qubit strings only: every term goes to a sweep (qsim_pauli_rotation_plan reports no term queued as a gate)
+# multi-qubit strings only: every term goes to a sweep (plans.pauli_rotation_plan reports no term queued as a gate)
 ROTATIONS_MULTI = [(0.6, "X14 X0"), (-1.2, "X14 X0 Z9"), (0.4, "Z12 Z3"), (2.2, "Y10 X5"), (0.3, "Z7 Z13"), (-0.9, "X4 Y8 Z1"), (1.1, "Y13 Y2")]
 # single-qubit X / Y strings travel through the gate queue; from either partial start some of their qubits lie outside the support
 ROTATIONS_MIXED = [(0.7, "X4"), (0.6, "X14 X0"), (-0.5, "Y13"), (0.4, "Z12 Z3"), (0.9, "X0"), (2.2, "Y10 X5"), (-1.3, "Y9"), (0.3, "X2 Z11")]

@@ -6,7 +6,7 @@ else keeps its bits.  `apply_matrix` is the same through reshaped views and one 
 tests/test_matrix_cpu.py pins both against dense Kronecker operators and the helpers of the 1q / 2q / cx tests, and each other.
 
 `emulate_operand` restates, lane by lane, what the kernel's matrix path does with the operand the library hands it
-(qsim_apply_matrix_operand): R' = M R in 16 x 16 tiles by 16 x 16 x 4 products in the layout of the fp64 matrix instruction
+(plans.apply_matrix_operand): R' = M R in 16 x 16 tiles by 16 x 16 x 4 products in the layout of the fp64 matrix instruction
 (A[l & 15][l >> 4], B[l >> 4][l & 15]; C/D col = l & 15, row = (l >> 4) + 4 reg), every lane feeding components of units it loaded
 and storing what the D map gives it."""
 import numpy as np

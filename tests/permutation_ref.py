@@ -5,8 +5,8 @@ csrc/permutation.cpp).
 gather the 2^k amplitudes of every environment (bit j of a table index is qubit targets[j]), index, scatter:
 new[e | dep(perm[j])] = old[e | dep(j)].  Everything else keeps its bits; nothing is computed, so the dtype's bits move as they are.
 
-`walk_tiles` restates what the kernel does with the plan and the operand the library reports (qsim_apply_permutation_plan,
-qsim_apply_permutation_operand): tile by tile, amplitudes move inside the tile by the tile-local map."""
+`walk_tiles` restates what the kernel does with the plan and the operand the library reports (plans.apply_permutation_plan,
+plans.apply_permutation_operand): tile by tile, amplitudes move inside the tile by the tile-local map."""
 import numpy as np
 
 

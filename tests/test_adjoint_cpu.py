@@ -1,6 +1,6 @@
 """Pins tests/adjoint_ref.py, the checker of the GPU gradient tests, on the CPU: against the exact shift rule built from
 pauli_rot_ref.replay and pauli_ref.pauli_expectation, and against dense operators; and checks the host-only sweep plan of
-qsim_pauli_gradient (qsim_pauli_gradient_plan)."""
+qsim_pauli_gradient (plans.pauli_gradient_plan)."""
 import ctypes
 import math
 
@@ -11,7 +11,7 @@ import adjoint_ref as ref
 import fp32_ref
 import pauli_ref
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 
 UP = ctypes.POINTER(ctypes.c_uint64)
 
@@ -69,15 +69,13 @@ def test_fp32_checker_stays_under_the_reference_cap():
 
 
 def _plan(rot_x, ham_x):
-    rx, hx = np.array(rot_x, dtype=np.uint64), np.array(ham_x, dtype=np.uint64)
-    a, s = ctypes.c_long(-1), ctypes.c_long(-1)
-    _lib.check(_lib.load().qsim_pauli_gradient_plan(rx.ctypes.data_as(UP), rx.size, hx.ctypes.data_as(UP), hx.size, ctypes.byref(a), ctypes.byref(s)))
-    return a.value, s.value
+    p = plans.ok(plans.pauli_gradient_plan(rot_x, ham_x))
+    return p["adjoint_sweeps"], p["sum_sweeps"]
 
 
 def test_gradient_plan():
     lib = _lib.load()
-    K, KH = lib.qsim_pauli_rotations_per_sweep(), lib.qsim_pauli_terms_per_sweep()
+    K, KH = plans.pauli_rotations_per_sweep(), plans.pauli_terms_per_sweep()
     assert _plan([], []) == (0, 0)
     # maximal runs of consecutive equal x: single X / Y terms are sweeps too; equal x apart from each other do not share
     assert _plan([1, 1, 2, 1, 0, 0, 0], []) == (4, 0)
@@ -90,6 +88,8 @@ def test_gradient_plan():
     assert _plan([x for _, x, _ in diag + paired], [0]) == (2 * math.ceil((3 * K + 5) / K), 1)
     a, s = ctypes.c_long(), ctypes.c_long()
     ok = np.array([1, 2], dtype=np.uint64).ctypes.data_as(UP)
-    for args in ((ok, -1, ok, 2, ctypes.byref(a), ctypes.byref(s)), (ok, 2, ok, -1, ctypes.byref(a), ctypes.byref(s)), (None, 2, ok, 2, ctypes.byref(a), ctypes.byref(s)),
-                 (ok, 2, None, 2, ctypes.byref(a), ctypes.byref(s)), (ok, 2, ok, 2, None, ctypes.byref(s)), (ok, 2, ok, 2, ctypes.byref(a), None)):
-        assert lib.qsim_pauli_gradient_plan(*args) == _lib.ERR_ARG
+    for rot_x, ham_x, counts in (([1, 2], [1, 2], dict(num_rot=-1)), ([1, 2], [1, 2], dict(num_ham=-1)), (None, [1, 2], dict(num_rot=2)),
+                                 ([1, 2], None, dict(num_ham=2))):
+        assert plans.pauli_gradient_plan(rot_x, ham_x, **counts)[0] == _lib.ERR_ARG
+    for args in ((ok, 2, ok, 2, None, ctypes.byref(s)), (ok, 2, ok, 2, ctypes.byref(a), None)):
+        assert lib.qsim_pauli_gradient_plan(*args) == _lib.ERR_ARG  # raw: NULL for an out-parameter

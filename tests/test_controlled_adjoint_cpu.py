@@ -1,6 +1,6 @@
 """Adjoint gradients through controlled Pauli rotations, the parts that need no GPU: the numpy checker
 (tests/controlled_adjoint_ref.py) pinned against dense operators and the four-term shift rule, the two-term rule shown wrong (the
-reason the feature exists), the host-only plan qsim_controlled_gradient_plan, and the fp32 legality of every case the GPU tests run."""
+reason the feature exists), the host-only plan plans.controlled_gradient_plan, and the fp32 legality of every case the GPU tests run."""
 import ctypes
 import itertools
 import math
@@ -12,7 +12,7 @@ import controlled_adjoint_ref as ref
 import controlled_rot_ref as crot
 import fp32_ref
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 
 UP = ctypes.POINTER(ctypes.c_uint64)
 
@@ -70,8 +70,8 @@ def test_checker_matches_the_four_term_rule_and_the_two_term_rule_does_not():
 
 
 def test_plan_sweeps():
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
-    KH = _lib.load().qsim_pauli_terms_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
+    KH = plans.pauli_terms_per_sweep()
     n = ref.RUN_N
     a, b = ref.RUN_CONTROLS
     x = pauli_rot_ref.LONG_RUN_X
@@ -89,17 +89,15 @@ def test_plan_sweeps():
 
 
 def test_plan_without_controls_is_the_uncontrolled_plan():
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     diag, paired = pauli_rot_ref.long_run_rotations(K)
     rotations, terms = ref.uncontrolled_case()
     for old, n in ((diag + paired, 13), ([(t, x, z) for t, _, x, z in rotations], ref.BITS_N), (pauli_rot_ref.single_bit_rotations(13), 13)):
-        rx, hx = np.array([x for _, x, _ in old], dtype=np.uint64), np.array([x for _, x, _ in terms], dtype=np.uint64)
-        a, s = ctypes.c_long(-1), ctypes.c_long(-1)
-        _lib.check(_lib.load().qsim_pauli_gradient_plan(rx.ctypes.data_as(UP), rx.size, hx.ctypes.data_as(UP), hx.size, ctypes.byref(a), ctypes.byref(s)))
+        plain = plans.ok(plans.pauli_gradient_plan([x for _, x, _ in old], [x for _, x, _ in terms]))
         zero = [(t, 0, x, z) for t, x, z in old]
         for precision in (64, 32):
             got = ref.plan(zero, terms, n, precision)
-            assert got[:2] == (a.value, s.value)
+            assert got[:2] == (plain["adjoint_sweeps"], plain["sum_sweeps"])
             assert got == ref.plan(zero, terms, n, precision, null_controls=True)
 
 
@@ -146,7 +144,7 @@ def test_plan_units_against_an_enumeration(precision):
             checked += 1
     assert checked > 150
     # units add up over the sweeps of a call, pieces of a long run and uncontrolled sweeps included
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     run = ref.run_terms(K)
     sweeps, _, units = ref.plan(run + [(0.2, 0, 0, 1)], [], ref.RUN_N, precision)
     assert sweeps == -(-len(run) // K) + 1
@@ -157,36 +155,38 @@ def test_plan_units_against_an_enumeration(precision):
 
 def test_plan_argument_errors():
     lib = _lib.load()
-    ok = np.array([1, 2], dtype=np.uint64).ctypes.data_as(UP)
-    cs = np.array([4, 8], dtype=np.uint64).ctypes.data_as(UP)
-    a, s, u = ctypes.c_long(), ctypes.c_long(), ctypes.c_uint64()
-    out = (ctypes.byref(a), ctypes.byref(s), ctypes.byref(u))
+    ok, cs = [1, 2], [4, 8]
+    probe = plans.controlled_gradient_plan
 
-    def refused(word, *args):
-        assert lib.qsim_controlled_gradient_plan(*args) == _lib.ERR_ARG
+    def refused(word, *args, **counts):
+        assert probe(*args, **counts)[0] == _lib.ERR_ARG
         assert word in lib.qsim_last_error(), lib.qsim_last_error()
 
-    assert lib.qsim_controlled_gradient_plan(cs, ok, 2, ok, 2, 5, 64, *out) == 0 and (a.value, s.value) == (2, 2)
-    refused(b"negative", cs, ok, -1, ok, 2, 5, 64, *out)
-    refused(b"negative", cs, ok, 2, ok, -1, 5, 64, *out)
-    refused(b"NULL", cs, None, 2, ok, 2, 5, 64, *out)
-    refused(b"NULL", cs, ok, 2, None, 2, 5, 64, *out)
+    rc, got = probe(cs, ok, ok, 5, 64)
+    assert rc == 0 and (got["adjoint_sweeps"], got["sum_sweeps"]) == (2, 2)
+    refused(b"negative", cs, ok, ok, 5, 64, num_rot=-1)
+    refused(b"negative", cs, ok, ok, 5, 64, num_ham=-1)
+    refused(b"NULL", cs, None, ok, 5, 64, num_rot=2)
+    refused(b"NULL", cs, ok, None, 5, 64, num_ham=2)
+    okp, csp = (np.array(v, dtype=np.uint64).ctypes.data_as(UP) for v in (ok, cs))
+    out = (ctypes.byref(ctypes.c_long()), ctypes.byref(ctypes.c_long()), ctypes.byref(ctypes.c_uint64()))
     for i in range(3):
-        refused(b"NULL", cs, ok, 2, ok, 2, 5, 64, *(None if k == i else p for k, p in enumerate(out)))
-    refused(b"precision", cs, ok, 2, ok, 2, 5, 16, *out)
-    refused(b"qubits", cs, ok, 2, ok, 2, -1, 64, *out)
-    refused(b"qubits", cs, ok, 2, ok, 2, 41, 64, *out)
-    refused(b"outside", cs, ok, 2, ok, 2, 1, 64, *out)  # a string's qubit outside the register
-    refused(b"control qubit outside", cs, ok, 2, ok, 2, 3, 64, *out)  # control 3 on three qubits
-    overlap_x = np.array([4, 2], dtype=np.uint64).ctypes.data_as(UP)
-    refused(b"term 1: a control qubit carries a Pauli factor", overlap_x, ok, 2, ok, 2, 5, 64, *out)
-    assert lib.qsim_controlled_gradient_plan(None, None, 0, None, 0, 5, 64, *out) == 0 and (a.value, s.value, u.value) == (0, 0, 0)
+        missing = (None if k == i else p for k, p in enumerate(out))
+        assert lib.qsim_controlled_gradient_plan(csp, okp, 2, okp, 2, 5, 64, *missing) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+        assert b"NULL" in lib.qsim_last_error(), lib.qsim_last_error()
+    refused(b"precision", cs, ok, ok, 5, 16)
+    refused(b"qubits", cs, ok, ok, -1, 64)
+    refused(b"qubits", cs, ok, ok, 41, 64)
+    refused(b"outside", cs, ok, ok, 1, 64)  # a string's qubit outside the register
+    refused(b"control qubit outside", cs, ok, ok, 3, 64)  # control 3 on three qubits
+    refused(b"term 1: a control qubit carries a Pauli factor", [4, 2], ok, ok, 5, 64)
+    assert probe(None, None, None, 5, 64) == (0, dict(adjoint_sweeps=0, sum_sweeps=0, units_visited=0))
 
 
 def test_fp32_cases_stay_under_the_reference_cap():
     """The complex64 run of the checker, which the fp32 GPU tests use as ref32, is within fp32_ref.REF_CAP of the fp64 one on every
     case; every case is legal and has a gradient that is no comparison of zeros."""
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     labels = []
     for label, start, rotations, terms in ref.fp32_cases(K):
         n = start.size.bit_length() - 1

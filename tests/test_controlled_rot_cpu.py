@@ -1,6 +1,6 @@
 """Controlled Pauli rotations, the parts that need no GPU: the numpy checker (tests/controlled_rot_ref.py) pinned against dense
 operators, the fp32 legality of every sequence the GPU tests run, the routing and the units visited as
-qsim_controlled_rotation_plan reports them, and the Python front end's argument checks."""
+plans.controlled_rotation_plan reports them, and the Python front end's argument checks."""
 import ctypes
 import itertools
 import math
@@ -12,7 +12,7 @@ import controlled_rot_ref as ref
 import fp32_ref
 import pauli_ref
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 from gpu_quantum_simulator_amd.pauli import control_mask
 
 UP = ctypes.POINTER(ctypes.c_uint64)
@@ -66,7 +66,7 @@ def test_mcx_and_mcz_constructions_on_the_checker():
 
 
 def test_fp32_sequences_are_legal():
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     labels = []
     for label, n, start, rotations in ref.fp32_sequences(K):
         assert all(c & (x | z) == 0 and (c | x | z) < 1 << n for _, c, x, z in rotations), label
@@ -85,14 +85,12 @@ _plan = ref.plan
 
 
 def _old_plan(rotations):
-    xs, zs = (np.array([r[i] for r in rotations], dtype=np.uint64) for i in (2, 3))
-    sweeps, gates = ctypes.c_long(-1), ctypes.c_long(-1)
-    _lib.check(_lib.load().qsim_pauli_rotation_plan(xs.ctypes.data_as(UP), zs.ctypes.data_as(UP), xs.size, ctypes.byref(sweeps), ctypes.byref(gates)))
-    return sweeps.value, gates.value
+    p = plans.ok(plans.pauli_rotation_plan([r[2] for r in rotations], [r[3] for r in rotations]))
+    return p["sweeps"], p["queued_as_gates"]
 
 
 def test_routing_plan():
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     n = ref.RUN_N
     run = ref.run_terms(K)
     assert len(run) == 3 * K + 5 and len({(c, x) for _, c, x, _ in run}) == 1
@@ -112,7 +110,7 @@ def test_routing_plan():
     assert _plan([(0.1, 1 << 5, 1 << 2, 1 << 3)], n)[:2] == (1, 0)  # X2 Z3
     assert _plan([(0.1, 1 << 5, 0b11, 0), (0.1, 1 << 5, 1, 0), (0.1, 1 << 5, 0b11, 0)], n)[:2] == (2, 1)  # a queued 4x4 cuts a run
     assert _plan([], n) == (0, 0, 0)
-    # no controls anywhere: qsim_pauli_rotation_plan, with c_masks all zero and with c_masks NULL
+    # no controls anywhere: plans.pauli_rotation_plan, with c_masks all zero and with c_masks NULL
     diag, paired = pauli_rot_ref.long_run_rotations(K)
     rng = np.random.default_rng(71)
     mixed = [(0.1,) + pauli_ref.random_masks(rng, n, 1 + i % 3) for i in range(60)]
@@ -121,10 +119,7 @@ def test_routing_plan():
         for precision in (64, 32):
             got = _plan(rotations, n, precision)
             assert got[:2] == _old_plan(rotations)
-        xs, zs = (np.array([r[i] for r in rotations], dtype=np.uint64) for i in (2, 3))
-        s, g, u = ctypes.c_long(), ctypes.c_long(), ctypes.c_uint64()
-        _lib.check(_lib.load().qsim_controlled_rotation_plan(None, xs.ctypes.data_as(UP), zs.ctypes.data_as(UP), xs.size, n, 32, ctypes.byref(s), ctypes.byref(g), ctypes.byref(u)))
-        assert (s.value, g.value, u.value) == got
+        assert tuple(plans.ok(plans.controlled_rotation_plan(None, [r[2] for r in rotations], [r[3] for r in rotations], n, 32)).values()) == got
 
 
 def _units_by_enumeration(n, precision, c, x):
@@ -157,7 +152,7 @@ def test_units_visited_against_an_enumeration(precision):
             checked += 1
     assert checked > 150
     # units add up over the sweeps of a call, pieces of a long run included
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     run = ref.run_terms(K)
     sweeps, _, units = _plan(run, ref.RUN_N, precision)
     assert units == sweeps * _units_by_enumeration(ref.RUN_N, precision, run[0][1], run[0][2])
@@ -168,31 +163,31 @@ def test_units_visited_against_an_enumeration(precision):
 
 def test_plan_argument_errors():
     lib = _lib.load()
-    ok = np.array([1, 2], dtype=np.uint64).ctypes.data_as(UP)
-    cs = np.array([4, 8], dtype=np.uint64).ctypes.data_as(UP)
-    s, g, u = ctypes.c_long(), ctypes.c_long(), ctypes.c_uint64()
-    out = (ctypes.byref(s), ctypes.byref(g), ctypes.byref(u))
+    ok, cs = [1, 2], [4, 8]
+    probe = plans.controlled_rotation_plan
 
-    def refused(word, *args):
-        assert lib.qsim_controlled_rotation_plan(*args) == _lib.ERR_ARG
+    def refused(word, *args, **counts):
+        assert probe(*args, **counts)[0] == _lib.ERR_ARG
         assert word in lib.qsim_last_error(), lib.qsim_last_error()
 
-    assert lib.qsim_controlled_rotation_plan(cs, ok, ok, 2, 5, 64, *out) == 0
-    refused(b"negative", cs, ok, ok, -1, 5, 64, *out)
-    refused(b"NULL", cs, None, ok, 2, 5, 64, *out)
-    refused(b"NULL", cs, ok, None, 2, 5, 64, *out)
+    assert probe(cs, ok, ok, 5, 64)[0] == 0
+    refused(b"negative", cs, ok, ok, 5, 64, num_terms=-1)
+    refused(b"NULL", cs, None, ok, 5, 64, num_terms=2)
+    refused(b"NULL", cs, ok, None, 5, 64)
+    okp, csp = (np.array(v, dtype=np.uint64).ctypes.data_as(UP) for v in (ok, cs))
+    out = (ctypes.byref(ctypes.c_long()), ctypes.byref(ctypes.c_long()), ctypes.byref(ctypes.c_uint64()))
     for i in range(3):
-        refused(b"NULL", cs, ok, ok, 2, 5, 64, *(None if k == i else p for k, p in enumerate(out)))
-    refused(b"precision", cs, ok, ok, 2, 5, 16, *out)
-    refused(b"qubits", cs, ok, ok, 2, -1, 64, *out)
-    refused(b"qubits", cs, ok, ok, 2, 41, 64, *out)
-    refused(b"outside", cs, ok, ok, 2, 1, 64, *out)  # a string's qubit outside the register
-    refused(b"control qubit outside", cs, ok, ok, 2, 3, 64, *out)  # control 3 on three qubits
-    overlap_x = np.array([4, 2], dtype=np.uint64).ctypes.data_as(UP)
-    refused(b"term 1: a control qubit carries a Pauli factor", overlap_x, ok, ok, 2, 5, 64, *out)
-    overlap_z = np.array([1, 8], dtype=np.uint64).ctypes.data_as(UP)
-    refused(b"term 0: a control qubit carries a Pauli factor", overlap_z, np.array([2, 2], dtype=np.uint64).ctypes.data_as(UP), ok, 2, 5, 64, *out)
-    assert lib.qsim_controlled_rotation_plan(None, None, None, 0, 5, 64, *out) == 0 and (s.value, g.value, u.value) == (0, 0, 0)
+        missing = (None if k == i else p for k, p in enumerate(out))
+        assert lib.qsim_controlled_rotation_plan(csp, okp, okp, 2, 5, 64, *missing) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+        assert b"NULL" in lib.qsim_last_error(), lib.qsim_last_error()
+    refused(b"precision", cs, ok, ok, 5, 16)
+    refused(b"qubits", cs, ok, ok, -1, 64)
+    refused(b"qubits", cs, ok, ok, 41, 64)
+    refused(b"outside", cs, ok, ok, 1, 64)  # a string's qubit outside the register
+    refused(b"control qubit outside", cs, ok, ok, 3, 64)  # control 3 on three qubits
+    refused(b"term 1: a control qubit carries a Pauli factor", [4, 2], ok, ok, 5, 64)
+    refused(b"term 0: a control qubit carries a Pauli factor", [1, 8], [2, 2], ok, 5, 64)
+    assert probe(None, None, None, 5, 64) == (0, dict(sweeps=0, queued_as_gates=0, units_visited=0))
 
 
 def test_control_mask_checks():

@@ -1,6 +1,6 @@
 """Reduced density matrices, checked on the CPU: the checker of tests/test_gpu_density.py against dense constructions, the numpy
 emulation of the kernel's decomposition (tests/density_ref.py) against the checker, and the host-only plan call
-(qsim_reduced_density_plan) against the emulation's geometry."""
+(plans.reduced_density_plan) against the emulation's geometry."""
 import ctypes
 import itertools
 from ctypes import byref, c_int, c_long, c_uint64
@@ -9,18 +9,11 @@ import numpy as np
 import pytest
 
 import density_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 from pauli_rot_ref import rand_state
 
-NEW_NAMES = ("qsim_reduced_density", "qsim_reduced_density_max_qubits", "qsim_reduced_density_plan", "qsim_density_sweeps_launched")
-
-
-def _c_plan(qubits, n, bits):
-    lib = _lib.load()
-    arr = (c_int * max(len(qubits), 1))(*qubits)
-    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = lib.qsim_reduced_density_plan(arr, len(qubits), n, bits, byref(path), byref(padded), byref(mask), byref(units), byref(trips))
-    return rc, dict(path=path.value, padded_k=padded.value, mask=mask.value, units=units.value, trips=trips.value)
+NEW_NAMES = ("qsim_reduced_density", "qsim_reduced_density_max_qubits", "qsim_reduced_density_plan", "qsim_density_sweeps_launched")  # census of the signature table
+MODEL_KEYS = {"kernel_mask": "mask", "units_visited": "units", "trips_per_workgroup_at_grid_cap": "trips"}  # header name -> density_ref.plan's key
 
 
 def _partial_trace_dense(psi, qubits):
@@ -43,7 +36,7 @@ def _partial_trace_dense(psi, qubits):
 def test_signatures_have_the_new_names():
     for name in NEW_NAMES:
         assert name in _lib.SIGNATURES
-    assert _lib.load().qsim_reduced_density_max_qubits() == 5
+    assert plans.reduced_density_max_qubits() == 5
 
 
 def test_checker_on_product_states():
@@ -95,13 +88,13 @@ def test_plan_call_matches_the_emulation(bits):
         for k in range(0, min(n, 5) + 1):
             for qs in density_ref.subsets(n, k):
                 for order in (qs, qs[::-1]) if k > 1 else (qs,):
-                    rc, got = _c_plan(order, n, bits)
+                    rc, got = plans.reduced_density_plan(order, n, bits)
                     want = density_ref.plan(order, n, bits == 32)
                     assert rc == _lib.QSIM_OK, (n, order)
-                    assert got == {key: want[key] for key in got}, (n, order, got, want)
+                    assert got == {key: want[MODEL_KEYS.get(key, key)] for key in got}, (n, order, got, want)
                     # the padding qubits are the lowest bits that are free
                     free = [q for q in range(n) if q not in order]
-                    pad = [q for q in range(n) if got["mask"] >> q & 1 and q not in order]
+                    pad = [q for q in range(n) if got["kernel_mask"] >> q & 1 and q not in order]
                     assert pad == free[:len(pad)] and len(pad) == got["padded_k"] - k
                     assert got["path"] == (1 if n >= 3 and n - max(k, 3) >= 2 else 0)
 
@@ -110,14 +103,14 @@ def test_plan_call_trips_at_the_looping_sizes():
     """Where tests/test_gpu_density.py expects every workgroup to walk its loop more than once."""
     for bits, n in ((64, 22), (32, 23)):
         for qs in ([0, 1, 2], [n - 3, n - 2, n - 1], [0, 1, 2, 3, 4], [n - 5, n - 4, n - 3, n - 2, n - 1]):
-            rc, got = _c_plan(qs, n, bits)
-            assert rc == _lib.QSIM_OK and got["path"] == 1 and got["trips"] >= 2, (bits, qs, got)
-            assert got["trips"] == density_ref.plan(qs, n, bits == 32)["trips"]
-    assert _c_plan([0, 1, 2], 12, 64)[1]["trips"] == 1
+            rc, got = plans.reduced_density_plan(qs, n, bits)
+            assert rc == _lib.QSIM_OK and got["path"] == 1 and got["trips_per_workgroup_at_grid_cap"] >= 2, (bits, qs, got)
+            assert got["trips_per_workgroup_at_grid_cap"] == density_ref.plan(qs, n, bits == 32)["trips"]
+    assert plans.reduced_density_plan([0, 1, 2], 12, 64)[1]["trips_per_workgroup_at_grid_cap"] == 1
 
 
 def test_plan_call_refusals():
-    ok = lambda *a: _c_plan(*a)[0]
+    ok = lambda *a: plans.reduced_density_plan(*a)[0]
     assert ok([0, 1], 6, 64) == _lib.QSIM_OK
     assert ok([0, 0], 6, 64) == _lib.ERR_ARG                     # a repeated qubit
     assert ok([0, 6], 6, 64) == _lib.ERR_ARG                     # outside [0, n)
@@ -128,12 +121,12 @@ def test_plan_call_refusals():
     assert ok([0], 40, 64) == _lib.QSIM_OK and ok([], 0, 32) == _lib.QSIM_OK
     assert ok([0], 6, 16) == _lib.ERR_ARG                        # precision_bits
     lib = _lib.load()
-    path, padded, mask, units, trips = c_int(), c_int(), c_uint64(), c_uint64(), c_long()
-    assert lib.qsim_reduced_density_plan(None, 1, 6, 64, byref(path), byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG
-    assert lib.qsim_reduced_density_plan(None, -1, 6, 64, byref(path), byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG
-    assert lib.qsim_reduced_density_plan(None, 0, 6, 64, byref(path), byref(padded), byref(mask), byref(units), byref(trips)) == _lib.QSIM_OK
+    padded, mask, units, trips = c_int(), c_uint64(), c_uint64(), c_long()
+    assert plans.reduced_density_plan(None, 6, 64, k=1)[0] == _lib.ERR_ARG
+    assert plans.reduced_density_plan(None, 6, 64, k=-1)[0] == _lib.ERR_ARG
+    assert plans.reduced_density_plan(None, 6, 64, k=0)[0] == _lib.QSIM_OK
     arr = (c_int * 1)(0)
-    assert lib.qsim_reduced_density_plan(arr, 1, 6, 64, None, byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG
+    assert lib.qsim_reduced_density_plan(arr, 1, 6, 64, None, byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
     # the call itself refuses a NULL state before it looks at anything else
     out = (ctypes.c_double * 8)()
     assert lib.qsim_reduced_density(None, arr, 1, out) == _lib.ERR_ARG

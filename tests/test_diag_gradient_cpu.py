@@ -1,11 +1,10 @@
 """Adjoint gradients through diagonal phases, checked on the CPU: the checker of tests/test_gpu_diag_gradient.py (diag_adjoint_ref)
 against the exact chain rule through the Z rotations that a table of terms stands for and against dense operators, the host-only plan
-call (qsim_diagonal_gradient_plan) against its rules, the refusals that need no device, and the ValueErrors that
+call (plans.diagonal_gradient_plan) against its rules, the refusals that need no device, and the ValueErrors that
 Simulator.energy_and_gradient raises in pure Python.
 
 The tolerance of the checker-against-checker comparisons is 1e-12, DESIGN §7d's figure for these checkers: sums of at most 2^6
 products of numbers of order one in fp64."""
-import ctypes
 from ctypes import byref, c_double, c_int, c_long, c_void_p
 
 import numpy as np
@@ -16,11 +15,11 @@ import controlled_adjoint_ref
 import diag_adjoint_ref as ref
 import diagonal_ref
 from diag_adjoint_ref import Diag
-from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib
+from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib, plans
 from pauli_rot_ref import rand_state
 
 CHECKER_TOL = 1e-12
-NEW_NAMES = ("qsim_diagonal_gradient", "qsim_diagonal_gradient_plan", "qsim_diagonal_adjoint_sweeps_launched", "qsim_diagonal_apply_into")
+NEW_NAMES = ("qsim_diagonal_gradient", "qsim_diagonal_gradient_plan", "qsim_diagonal_adjoint_sweeps_launched", "qsim_diagonal_apply_into")  # census of the signature table
 
 
 def test_signatures_and_exports_have_the_new_names():
@@ -115,8 +114,8 @@ def _per_trip(precision):
 
 @pytest.mark.parametrize("precision", [64, 32])
 def test_plan_counts_sweeps(precision):
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
-    T = _lib.load().qsim_pauli_terms_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
+    T = plans.pauli_terms_per_sweep()
     n = 9
     d = None
     x = 0b101
@@ -133,16 +132,16 @@ def test_plan_counts_sweeps(precision):
     ]
     for steps, terms, obs, (pauli, diag, sums) in cases:
         got = ref.plan(steps, terms, obs, n, precision)
-        assert (got["pauli_adjoint"], got["diag_adjoint"], got["sum_sweeps"]) == (pauli, diag, sums), (steps, got)
-        assert got["diag_adjoint"] == sum(1 for s in steps if ref.is_diag(s))
-        assert got["per_trip"] == _per_trip(precision)
-    # without diagonal steps and without D_obs: qsim_controlled_gradient_plan's counts
+        assert (got["pauli_adjoint_sweeps"], got["diag_adjoint_sweeps"], got["sum_sweeps"]) == (pauli, diag, sums), (steps, got)
+        assert got["diag_adjoint_sweeps"] == sum(1 for s in steps if ref.is_diag(s))
+        assert got["diag_adjoint_items_per_trip"] == _per_trip(precision)
+    # without diagonal steps and without D_obs: plans.controlled_gradient_plan's counts
     rotations, terms = controlled_adjoint_ref.uncontrolled_case()
     got = ref.plan(rotations, terms, None, controlled_adjoint_ref.BITS_N, precision)
-    assert (got["pauli_adjoint"], got["sum_sweeps"]) == controlled_adjoint_ref.plan(rotations, terms, controlled_adjoint_ref.BITS_N, precision)[:2]
+    assert (got["pauli_adjoint_sweeps"], got["sum_sweeps"]) == controlled_adjoint_ref.plan(rotations, terms, controlled_adjoint_ref.BITS_N, precision)[:2]
     # NULL is_diag and NULL step_c: no diagonal step, no control
     rc, got = ref.plan_call([0, 0], [0, 0], [x, x], [], False, n, precision, null_flags=True, null_controls=True)
-    assert rc == 0 and (got["pauli_adjoint"], got["diag_adjoint"]) == (1, 0)
+    assert rc == 0 and (got["pauli_adjoint_sweeps"], got["diag_adjoint_sweeps"]) == (1, 0)
 
 
 @pytest.mark.parametrize("precision", [64, 32])
@@ -152,9 +151,9 @@ def test_plan_trips(precision):
         got = ref.plan([Diag(0.0, None)], [], None, n, precision)
         items = max(1, (1 << n) >> 1)
         if n <= 6:
-            assert got["trips"] == 1  # the plain path
+            assert got["diag_adjoint_trips_at_cap"] == 1  # the plain path
         else:
-            assert got["trips"] == -(-(-(-items // threads)) // (_per_trip(precision) * grid))
+            assert got["diag_adjoint_trips_at_cap"] == -(-(-(-items // threads)) // (_per_trip(precision) * grid))
     assert ref.loop_n(precision) == 21
 
 
@@ -175,13 +174,14 @@ def test_plan_refusals():
     assert rc([0], [0], [x], ham_x=[1 << n]) == _lib.ERR_ARG
     assert rc([0], [0], [x], n=41) == _lib.ERR_ARG and rc([0], [0], [x], n=-1) == _lib.ERR_ARG and rc([0], [0], [x], bits=16) == _lib.ERR_ARG
     out = [byref(c_long()), byref(c_long()), byref(c_long()), byref(c_int()), byref(c_long())]
-    assert lib.qsim_diagonal_gradient_plan(None, None, None, -1, None, 0, 0, n, 64, *out) == _lib.ERR_ARG and b"negative" in lib.qsim_last_error()
-    assert lib.qsim_diagonal_gradient_plan(None, None, None, 0, None, -1, 0, n, 64, *out) == _lib.ERR_ARG
-    assert lib.qsim_diagonal_gradient_plan(None, None, None, 1, None, 0, 0, n, 64, *out) == _lib.ERR_ARG   # a rotation step without masks
+    nothing = lambda **counts: plans.diagonal_gradient_plan(None, None, None, None, 0, n, 64, **counts)[0]
+    assert nothing(num_steps=-1) == _lib.ERR_ARG and b"negative" in lib.qsim_last_error()
+    assert nothing(num_ham=-1) == _lib.ERR_ARG
+    assert nothing(num_steps=1) == _lib.ERR_ARG   # a rotation step without masks
     for k in range(5):
         args = list(out)
         args[k] = None
-        assert lib.qsim_diagonal_gradient_plan(None, None, None, 0, None, 0, 0, n, 64, *args) == _lib.ERR_ARG
+        assert lib.qsim_diagonal_gradient_plan(None, None, None, 0, None, 0, 0, n, 64, *args) == _lib.ERR_ARG  # raw: NULL for an out-parameter
 
 
 def test_refusals_without_a_device():
@@ -189,7 +189,7 @@ def test_refusals_without_a_device():
     e, g = c_double(), c_double()
     assert lib.qsim_diagonal_gradient(None, 0, None, None, None, None, None, None, None, None, 0, None, 0.0, byref(e), byref(g)) == _lib.ERR_ARG
     assert lib.qsim_diagonal_apply_into(None, None, 1.0, c_void_p(4096), 0) == _lib.ERR_ARG
-    assert isinstance(lib.qsim_diagonal_adjoint_sweeps_launched(), int)   # a counter, no device
+    assert isinstance(plans.sweeps_launched("diagonal_adjoint"), int)   # a counter, no device
 
 
 # ---- pure Python ----------------------------------------------------------------------------------------------------------------------

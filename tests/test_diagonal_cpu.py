@@ -1,5 +1,5 @@
 """Whole-register diagonal operators from a table, checked on the CPU: the checker of tests/test_gpu_diagonal.py (diagonal_ref) against
-dense operators built with np.kron and against pauli_rot_ref's Z rotations, the host-only plan call (qsim_diagonal_plan) against its
+dense operators built with np.kron and against pauli_rot_ref's Z rotations, the host-only plan call (plans.diagonal_plan) against its
 rules, the argument refusals that need no device, and Diagonal.from_terms refusing X and Y before anything touches a device."""
 from ctypes import byref, c_double, c_int, c_long, c_uint64, c_void_p
 
@@ -9,12 +9,12 @@ import pytest
 import diagonal_ref
 import pauli_ref
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 from pauli_rot_ref import rand_state
 
 NEW_NAMES = ("qsim_diagonal_create", "qsim_diagonal_create_external", "qsim_diagonal_destroy", "qsim_diagonal_num_qubits",
              "qsim_diagonal_device_ptr", "qsim_diagonal_add_terms", "qsim_diagonal_write", "qsim_diagonal_read", "qsim_diagonal_extrema",
-             "qsim_apply_diagonal_phase", "qsim_expect_diagonal", "qsim_diagonal_sweeps_launched", "qsim_diagonal_plan")
+             "qsim_apply_diagonal_phase", "qsim_expect_diagonal", "qsim_diagonal_sweeps_launched", "qsim_diagonal_plan")  # census of the signature table
 
 
 def _terms(n, count, seed):
@@ -86,8 +86,8 @@ def _model(n, precision):
     per = 3 if precision == 64 else 4
     blocks = -(-items // 256)
     plain = items < 64
-    return dict(items=items, per_trip_phase=per, per_trip_expect=per, trips_phase=1 if plain else -(-blocks // (per * 2048)),
-                trips_expect=1 if plain else -(-blocks // (per * 1024)))
+    return dict(items=items, items_per_trip_phase=per, items_per_trip_expect=per, trips_at_cap_phase=1 if plain else -(-blocks // (per * 2048)),
+                trips_at_cap_expect=1 if plain else -(-blocks // (per * 1024)))
 
 
 @pytest.mark.parametrize("precision", [64, 32])
@@ -96,22 +96,22 @@ def test_plan(precision):
     for n in (0, 1, 2, 9, loop - 1, loop, 30, 40):
         assert diagonal_ref.plan(n, precision) == _model(n, precision), n
     assert diagonal_ref.plan(0, precision)["items"] == 1 and diagonal_ref.plan(1, precision)["items"] == 1 and diagonal_ref.plan(2, precision)["items"] == 2
-    assert diagonal_ref.plan(9, precision)["trips_phase"] == 1 and diagonal_ref.plan(9, precision)["trips_expect"] == 1
+    assert diagonal_ref.plan(9, precision)["trips_at_cap_phase"] == 1 and diagonal_ref.plan(9, precision)["trips_at_cap_expect"] == 1
     at = diagonal_ref.plan(loop, precision)
-    assert at["trips_phase"] > 1 and at["trips_expect"] > 1 and 20 <= loop <= 24
-    assert diagonal_ref.plan(loop - 1, precision)["trips_phase"] == 1   # the smallest such size
+    assert at["trips_at_cap_phase"] > 1 and at["trips_at_cap_expect"] > 1 and 20 <= loop <= 24
+    assert diagonal_ref.plan(loop - 1, precision)["trips_at_cap_phase"] == 1   # the smallest such size
 
 
 def test_plan_refusals():
     lib = _lib.load()
     items, a, b, c, d = c_uint64(), c_int(), c_int(), c_long(), c_long()
     ok = (byref(items), byref(a), byref(b), byref(c), byref(d))
-    assert lib.qsim_diagonal_plan(9, 64, *ok) == _lib.QSIM_OK
+    assert plans.diagonal_plan(9, 64)[0] == _lib.QSIM_OK
     for n, bits in ((-1, 64), (41, 64), (9, 16), (9, 0)):
-        assert lib.qsim_diagonal_plan(n, bits, *ok) == _lib.ERR_ARG
+        assert plans.diagonal_plan(n, bits)[0] == _lib.ERR_ARG
     for missing in range(5):
         args = [None if i == missing else p for i, p in enumerate(ok)]
-        assert lib.qsim_diagonal_plan(9, 64, *args) == _lib.ERR_ARG
+        assert lib.qsim_diagonal_plan(9, 64, *args) == _lib.ERR_ARG  # raw: NULL for an out-parameter
         assert b"NULL" in lib.qsim_last_error()
 
 
@@ -135,7 +135,7 @@ def test_refusals_without_a_device():
     assert lib.qsim_expect_diagonal(None, None, out) == _lib.ERR_ARG
     assert lib.qsim_diagonal_num_qubits(None) == -1 and not lib.qsim_diagonal_device_ptr(None)
     lib.qsim_diagonal_destroy(None)
-    assert isinstance(lib.qsim_diagonal_sweeps_launched(), int)
+    assert isinstance(plans.sweeps_launched("diagonal"), int)
 
 
 def test_from_terms_refuses_x_and_y_before_touching_a_device(monkeypatch):

@@ -25,7 +25,7 @@ import fp32_ref
 import pauli_ref
 import pauli_rot_ref
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -34,16 +34,9 @@ UP = ctypes.POINTER(ctypes.c_uint64)
 DP = ctypes.POINTER(ctypes.c_double)
 
 
-def _sweeps():
-    return _lib.load().qsim_pauli_adjoint_sweeps_launched()
-
-
 def _plan(rotations, terms):
-    rx = np.array([x for _, x, _ in rotations], dtype=np.uint64)
-    hx = np.array([x for _, x, _ in terms], dtype=np.uint64)
-    a, s = ctypes.c_long(-1), ctypes.c_long(-1)
-    _lib.check(_lib.load().qsim_pauli_gradient_plan(rx.ctypes.data_as(UP), rx.size, hx.ctypes.data_as(UP), hx.size, ctypes.byref(a), ctypes.byref(s)))
-    return a.value, s.value
+    p = plans.ok(plans.pauli_gradient_plan([x for _, x, _ in rotations], [x for _, x, _ in terms]))
+    return p["adjoint_sweeps"], p["sum_sweeps"]
 
 
 def _bits(sim):
@@ -107,9 +100,9 @@ def test_geometry_strings(n, precision):
         for x, z in ref.geometry_strings(n):
             rot = [(0.7, x, z)]
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_adjoint")
             energy, grad = _run(sim, n, rot, terms)
-            assert _sweeps() - count == 1
+            assert plans.sweeps_launched("pauli_adjoint") - count == 1
             e64, g64, _ = ref.gradient(before, rot, terms)
             _, g32, _ = ref.gradient(before.astype(np.complex64), rot, terms, np.complex64)
             print(f"n={n} p{precision} {pauli_ref.masks_to_text(x, z, n)!r}: grad {grad[0]:+.9e} want {g64[0]:+.9e}, energy err {abs(energy - e64):.3e}")
@@ -137,9 +130,9 @@ def test_every_weight(precision):
     with Simulator(n, precision=precision) as sim:
         sim.write(pauli_rot_ref.rand_state(n, 13))
         before = sim.read()
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         energy, grad = _run(sim, n, rotations, terms)
-        assert _sweeps() - count == _plan(rotations, terms)[0]
+        assert plans.sweeps_launched("pauli_adjoint") - count == _plan(rotations, terms)[0]
         after = sim.read()
     g64, component_tol = _check(precision, energy, grad, before, rotations, terms, "every weight n=13")
     identity = [k for k, (_, x, z) in enumerate(rotations) if x == 0 and z == 0]
@@ -158,9 +151,9 @@ def test_order_inside_a_run_matters(precision):
         with Simulator(n, precision=precision) as sim:
             sim.write(pauli_rot_ref.rand_state(n, 6))
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_adjoint")
             energy, grad = _run(sim, n, order, terms)
-            assert _sweeps() - count == 3  # the pair shares its sweep
+            assert plans.sweeps_launched("pauli_adjoint") - count == 3  # the pair shares its sweep
             _check(precision, energy, grad, before, order, terms, "order")
             results.append(grad)
     swapped_back = results[1][[0, 2, 1, 3]]  # component k of both belongs to the same string
@@ -170,16 +163,16 @@ def test_order_inside_a_run_matters(precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_runs_longer_than_k(precision):
     n = 12
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     diag, paired = pauli_rot_ref.long_run_rotations(K)
     terms = ref.random_hamiltonian(n, 10, 1200, 2)
     with Simulator(n, precision=precision) as sim:
         sim.write(pauli_rot_ref.rand_state(n, 12))
         for label, run in (("diagonal", diag), ("paired", paired), ("both", diag + paired)):
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_adjoint")
             energy, grad = _run(sim, n, run, terms)
-            taken = _sweeps() - count
+            taken = plans.sweeps_launched("pauli_adjoint") - count
             assert taken == _plan(run, terms)[0] == -(-len(diag) // K) * (len(run) // len(diag)), (label, taken)
             _check(precision, energy, grad, before, run, terms, f"run of {len(run)} {label}")
             _state_back(precision, sim.read(), before, run, f"run of {len(run)} {label}")
@@ -354,6 +347,6 @@ def test_errors_and_edge_cases(precision):
         assert energy == 0.0 and grad.size == 0
         # a shard that holds nothing: energy 0, gradient zeros, no sweep, the state untouched
         sim.reset(holds_index0=False)
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         energy, grad = sim.energy_and_gradient([(0.3, "Z0 Z1"), (0.2, "X0 X1")], [(1.0, "Z0"), (0.5, "X1")])
-        assert energy == 0.0 and not grad.any() and _sweeps() == count and sim.get_support()[1:] == (1, 0.0)
+        assert energy == 0.0 and not grad.any() and plans.sweeps_launched("pauli_adjoint") == count and sim.get_support()[1:] == (1, 0.0)

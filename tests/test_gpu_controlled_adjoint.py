@@ -17,17 +17,13 @@ import controlled_adjoint_ref as ref
 import controlled_rot_ref as crot
 import fp32_ref
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
 
 pytestmark = pytest.mark.gpu
 TOL = ref.TOL
 PRECISIONS = [64, 32]
 UP = ctypes.POINTER(ctypes.c_uint64)
 DP = ctypes.POINTER(ctypes.c_double)
-
-
-def _sweeps():
-    return _lib.load().qsim_pauli_adjoint_sweeps_launched()
 
 
 def _bits(sim):
@@ -83,9 +79,9 @@ def _one_call(precision, n, start, rotations, terms, label, sweeps=None):
         else:
             sim.write(start)
             before = sim.read()
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         energy, grad = _run(sim, n, rotations, terms)
-        taken = _sweeps() - count
+        taken = plans.sweeps_launched("pauli_adjoint") - count
         after = sim.read()
     assert taken == ref.plan(rotations, terms, n, precision)[0], (label, taken)
     if sweeps is not None:
@@ -121,9 +117,9 @@ def test_every_control_position(precision):
         for k, rot in enumerate(rotations):
             sim.write(start)
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_adjoint")
             energy, grad = _run(sim, n, [rot], terms)
-            assert _sweeps() - count == 1
+            assert plans.sweeps_launched("pauli_adjoint") - count == 1
             after = sim.read()
             label = f"control {{{k // 2}}} {'diagonal' if k % 2 else 'paired'}"
             g64, g32 = _check(precision, energy, grad, before, [rot], terms, label, fp32_criterion=False)
@@ -167,7 +163,7 @@ def test_several_controls_and_every_weight(precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_runs(precision):
     """Runs longer than K are cut into ceil(len / K) sweeps; a change of control mask ends a run, as the plan says."""
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     for label, (rotations, sweeps) in ref.run_cases(K).items():
         _one_call(precision, ref.RUN_N, ref.rand_state(ref.RUN_N, 12), rotations, ref.run_hamiltonian(), label, sweeps)
 
@@ -299,9 +295,9 @@ def test_where_the_sweep_loops(precision):
     with Simulator(n, precision=precision) as sim:
         sim.write(ref.loop_state())
         before = sim.read()
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         energy, grad = _run(sim, n, rotations, terms)
-        assert _sweeps() - count == 4
+        assert plans.sweeps_launched("pauli_adjoint") - count == 4
         after = sim.read()
     _check(precision, energy, grad, before, rotations, terms, "n=22", large=True)
     _state_back(precision, after, before, rotations, "n=22", large=True)
@@ -348,14 +344,14 @@ def test_errors_and_edge_cases(precision):
         rc, energy, grad = _c_call(lib, "controlled", h, cs, rotations, terms, grad=False)
         _lib.check(rc)
         assert abs(energy - want_e) < tol and np.all(grad == 7.0)
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         rc, energy, grad = _c_call(lib, "controlled", h, cs[:0], [], terms)
         _lib.check(rc)
-        assert abs(energy - sim.expectation(ref.term_texts(terms, n))) < tol and _sweeps() == count
+        assert abs(energy - sim.expectation(ref.term_texts(terms, n))) < tol and plans.sweeps_launched("pauli_adjoint") == count
         energy, grad = sim.energy_and_gradient([], [])
         assert energy == 0.0 and grad.size == 0
         # a shard that holds nothing: energy 0, gradient zeros, no sweep, the state untouched
         sim.reset(holds_index0=False)
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_adjoint")
         energy, grad = sim.energy_and_gradient(ref.entries(rotations, n), ref.term_texts(terms, n))
-        assert energy == 0.0 and grad.size == 2 and not grad.any() and _sweeps() == count and sim.get_support()[1:] == (1, 0.0)
+        assert energy == 0.0 and grad.size == 2 and not grad.any() and plans.sweeps_launched("pauli_adjoint") == count and sim.get_support()[1:] == (1, 0.0)

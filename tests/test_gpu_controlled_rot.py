@@ -16,7 +16,7 @@ import controlled_rot_ref as ref
 import fp32_ref
 import pauli_rot_ref
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, circuits
+from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, circuits, plans
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -38,10 +38,6 @@ def _check(precision, got, before, rotations, label, quiet=False):
         if not quiet:
             report(label, errs)
     return want
-
-
-def _sweeps():
-    return _lib.load().qsim_pauli_rotation_sweeps_launched()
 
 
 def _bits(sim):
@@ -134,7 +130,7 @@ def test_bit_exact_relation_to_the_uncontrolled_sweep(c, precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_runs(precision):
     n = ref.RUN_N
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     run, alternating = ref.run_terms(K), ref.run_terms(K, ref.RUN_CONTROLS)
     assert len(run) == 3 * K + 5 and {t for t, _, _, _ in run} >= set(pauli_rot_ref.SPECIAL_ANGLES)
     assert (run[10][2:], run[11][2:]) == ((pauli_rot_ref.LONG_RUN_X, 0), (pauli_rot_ref.LONG_RUN_X, 1))  # anticommuting neighbours
@@ -142,9 +138,9 @@ def test_runs(precision):
         sim.write(ref.rand_state(n, 12))
         for label, terms, want_sweeps in (("one control mask", run, -(-(3 * K + 5) // K)), ("alternating control masks", alternating, len(alternating))):
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             sim.apply_pauli_rotations(ref.entries(terms, n))
-            taken = _sweeps() - count
+            taken = plans.sweeps_launched("pauli_rotation") - count
             assert taken == ref.plan(terms, n, precision)[0] == want_sweeps, (label, taken)
             _check(precision, sim.read(), before, terms, f"run of {len(terms)}, {label} p{precision}")
     results = []
@@ -153,9 +149,9 @@ def test_runs(precision):
         with Simulator(ref.ORDER_N, precision=precision) as sim:
             sim.write(ref.rand_state(ref.ORDER_N, 6))
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             sim.apply_pauli_rotations(ref.entries(order, ref.ORDER_N))
-            assert _sweeps() - count == 1
+            assert plans.sweeps_launched("pauli_rotation") - count == 1
             results.append(sim.read())
             _check(precision, results[-1], before, order, f"order p{precision}")
     assert np.max(np.abs(results[0] - results[1])) > 1e-2
@@ -187,22 +183,22 @@ def test_gate_route(precision):
     with Simulator(n, precision=precision) as sim:
         sim.write(ref.rand_state(n, 7))
         before = sim.read()
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         sim.apply_pauli_rotations(ref.entries(ref.GATE_TERMS, n))
         got = sim.read()
-        assert _sweeps() == count  # 4x4s through the gate queue: no sweep
+        assert plans.sweeps_launched("pauli_rotation") == count  # 4x4s through the gate queue: no sweep
         _check(precision, got, before, ref.GATE_TERMS, f"gate route p{precision}")
     # queued between the two halves of a circuit
     circuit = Circuit.from_gates(n, circuits.random_gates(*ref.GATE_CIRCUIT))
     gates = [circuit.gate(i) for i in range(len(circuit))]
     half = len(gates) // 2
     with Simulator(n, precision=precision) as sim:
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         sim.run(circuit, 0, half)
         sim.apply_pauli_rotations(ref.entries(ref.GATE_TERMS, n))
         sim.run(circuit, half, -1)
         got = sim.read()
-        assert _sweeps() == count
+        assert plans.sweeps_launched("pauli_rotation") == count
 
     def truth(dt):
         return fp32_ref.replay(n, gates[half:], ref.replay(fp32_ref.replay(n, gates[:half], dtype=dt), ref.GATE_TERMS, dt), dt)
@@ -245,9 +241,9 @@ def test_fresh_state(n, precision):
     term = ref.fresh_term(n)
     assert ref.plan([term], n, precision)[:2] == (1, 0)
     with Simulator(n, precision=precision) as sim:  # never touched: |0...0> is still held lazily
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         sim.apply_pauli_rotations(ref.entries([term], n))
-        assert _sweeps() - count == 1
+        assert plans.sweeps_launched("pauli_rotation") - count == 1
         assert sim.get_support()[0] == (1 << n) - 1
         got = sim.read()
     want = np.zeros(1 << n, dtype=np.complex128)
@@ -292,12 +288,12 @@ def test_helpers(precision):
         sim.write(start)
         for controls, target in ref.MCX_CASES:
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             sim.apply_mcx(controls, target)
             got = sim.read()
             c = ref.mask_of(controls)
             want = before[np.where((j & c) == c, j ^ (1 << target), j)]
-            assert _sweeps() - count == (2 if len(controls) >= 2 else 0)
+            assert plans.sweeps_launched("pauli_rotation") - count == (2 if len(controls) >= 2 else 0)
             close(got, want, ref.mcx_terms(controls, target) if len(controls) >= 2 else [(math.pi, c, 1 << target, 0), (-math.pi, c, 0, 0)], before,
                   f"mcx {controls} -> {target}")
             assert np.max(np.abs(got - before)) > 1e-3
@@ -330,7 +326,7 @@ def test_zero_controls_take_the_uncontrolled_path(precision):
     for how in ("plain", "empty controls", "NULL", "zeros"):
         with Simulator(n, precision=precision) as sim:
             sim.write(ref.rand_state(n, 104))
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             if how == "plain":
                 sim.apply_pauli_rotations(texts)
             elif how == "empty controls":
@@ -338,7 +334,7 @@ def test_zero_controls_take_the_uncontrolled_path(precision):
             else:
                 cp = None if how == "NULL" else zeros.ctypes.data_as(UP)
                 _lib.check(lib.qsim_apply_controlled_pauli_rotations(sim._h, cp, xs.ctypes.data_as(UP), zs.ctypes.data_as(UP), thetas.ctypes.data_as(DP), xs.size))
-            out.append((_sweeps() - count, _bits(sim)))
+            out.append((plans.sweeps_launched("pauli_rotation") - count, _bits(sim)))
     for taken, bits in out[1:]:
         assert taken == out[0][0] and np.array_equal(bits, out[0][1])
 
@@ -361,7 +357,7 @@ def test_errors(precision):
     with Simulator(n, precision=precision) as sim:
         sim.write(ref.rand_state(n, 5))
         before = _bits(sim)
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         keep = []
         for word, c, x, z in (("outside", [4, 8], [1, 1 << n], [0, 0]), ("outside", [4, 8], [1, 2], [0, 1 << 63]),
                               ("control qubit outside", [4, 1 << n], [1, 2], [1, 2]), ("control qubit outside", [1 << 63, 8], [1, 2], [1, 2]),
@@ -387,10 +383,10 @@ def test_errors(precision):
                 sim.apply_pauli_rotations([(0.2, "X1 X2", (3,)), bad])  # the valid first term is not applied either
         with pytest.raises(ValueError):
             sim.apply_pauli_rotation(0.1, "X0", controls=(0,))
-        assert np.array_equal(_bits(sim), before) and _sweeps() == count
+        assert np.array_equal(_bits(sim), before) and plans.sweeps_launched("pauli_rotation") == count
         sim.reset(holds_index0=False)  # a shard that holds nothing stays untouched
         sim.apply_pauli_rotations([(0.3, "Z0 Z1", (2, 3)), (0.2, "X0 X1", (4,)), (0.1, "", (0, 1))])
-        assert _sweeps() == count and sim.get_support()[1:] == (1, 0.0)
+        assert plans.sweeps_launched("pauli_rotation") == count and sim.get_support()[1:] == (1, 0.0)
     with Cluster(n, 2, devices=[0, 0]) as cl:
         cl.run(Circuit.from_gates(n, circuits.random_gates(n, 40, 5, "all")))
         before = cl.read()

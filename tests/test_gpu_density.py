@@ -10,13 +10,14 @@ norm2().  Sizes: the plain path (n <= 4), both sides of the switch to the matrix
 plan call), n = 13 for the matrix path's subsets, and n = 22 (fp64) / 23 (fp32), where the plan call reports at least two trips
 per workgroup."""
 import ctypes
-from ctypes import byref, c_int, c_long, c_uint64
+from ctypes import c_int
 
 import numpy as np
 import pytest
 
 import density_ref
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from gpu_quantum_simulator_amd._lib import QsimError
 from helpers import np_apply_1q, np_apply_cx, random_unitary
 from pauli_rot_ref import rand_state
@@ -25,14 +26,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-10
 PRECISIONS = [64, 32]
 H = np.array([[1, 1], [1, -1]]) / np.sqrt(2.0)
-
-
-def _plan(qubits, n, precision):
-    arr = (c_int * max(len(qubits), 1))(*qubits)
-    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_reduced_density_plan(arr, len(qubits), n, precision, byref(path), byref(padded), byref(mask), byref(units), byref(trips))
-    assert rc == _lib.QSIM_OK
-    return dict(path=path.value, padded_k=padded.value, mask=mask.value, trips=trips.value)
 
 
 def _check(sim, psi, qubits, label=""):
@@ -63,7 +56,7 @@ def test_plain_path_every_subset(n, precision):
     with sim:
         for k in range(0, n + 1):
             for qs in density_ref.subsets(n, k):
-                assert _plan(qs, n, precision)["path"] == 0
+                assert plans.ok(plans.reduced_density_plan(qs, n, precision))["path"] == 0
                 _check(sim, psi, qs, "plain")
                 if k > 1:
                     _check(sim, psi, qs[::-1], "plain")
@@ -73,13 +66,13 @@ def test_plain_path_every_subset(n, precision):
 @pytest.mark.parametrize("k", [0, 3, 4, 5])
 def test_path_switch(k, precision):
     """The smallest register the matrix path takes for this subset size, and the one below it: both from the plan call."""
-    first = next(n for n in range(max(k, 1), 16) if _plan(list(range(k)), n, precision)["path"] == 1)
-    assert first - 1 >= k and _plan(list(range(k)), first - 1, precision)["path"] == 0
+    first = next(n for n in range(max(k, 1), 16) if plans.ok(plans.reduced_density_plan(list(range(k)), n, precision))["path"] == 1)
+    assert first - 1 >= k and plans.ok(plans.reduced_density_plan(list(range(k)), first - 1, precision))["path"] == 0
     for n in (first - 1, first):
         sim, psi = _sim_with(n, precision, 320 + n)
         with sim:
             for qs in {tuple(range(k)), tuple(range(n - k, n)), tuple(range(n - 1, n - 1 - k, -1))}:
-                assert _plan(list(qs), n, precision)["path"] == (1 if n == first else 0)
+                assert plans.ok(plans.reduced_density_plan(list(qs), n, precision))["path"] == (1 if n == first else 0)
                 _check(sim, psi, list(qs), "switch")
 
 
@@ -101,7 +94,7 @@ def test_matrix_path_subsets(precision):
     sim, psi = _sim_with(n, precision, 313)
     with sim:
         for qs in N13_SUBSETS:
-            assert _plan(qs, n, precision)["path"] == 1
+            assert plans.ok(plans.reduced_density_plan(qs, n, precision))["path"] == 1
             _check(sim, psi, qs, "matrix")
 
 
@@ -112,8 +105,8 @@ def test_looping(precision):
     sim, psi = _sim_with(n, precision, 322)
     with sim:
         for qs in ([0, 1, 2], [n - 3, n - 2, n - 1], [0, 1, 2, 3, 4], [n - 5, n - 4, n - 3, n - 2, n - 1], [n - 2, 3, n - 1, 7, 1]):
-            p = _plan(qs, n, precision)
-            assert p["path"] == 1 and p["trips"] >= 2
+            p = plans.ok(plans.reduced_density_plan(qs, n, precision))
+            assert p["path"] == 1 and p["trips_per_workgroup_at_grid_cap"] >= 2
             _check(sim, psi, qs, "looping")
 
 
@@ -197,16 +190,15 @@ def test_partial_support(precision):
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_a_shard_that_holds_nothing(precision):
-    lib = _lib.load()
     with Simulator(13, precision=precision) as sim:
         sim.reset(holds_index0=False)
-        before = lib.qsim_density_sweeps_launched()
+        before = plans.sweeps_launched("density")
         for qs in ([], [0], [12, 3, 4], [0, 1, 2, 3, 4]):
             assert np.array_equal(sim.reduced_density_matrix(qs), np.zeros((1 << len(qs), 1 << len(qs))))
-        assert lib.qsim_density_sweeps_launched() == before
+        assert plans.sweeps_launched("density") == before
         sim.reset()
         sim.reduced_density_matrix([12, 3, 4])
-        assert lib.qsim_density_sweeps_launched() == before + 1
+        assert plans.sweeps_launched("density") == before + 1
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -268,10 +260,10 @@ def test_errors(precision):
     out = (ctypes.c_double * 2048)()
     with Simulator(6, precision=precision) as sim:
         sim.write(rand_state(6, 1))
-        before = lib.qsim_density_sweeps_launched()
-        call = lambda qs, k=None: lib.qsim_reduced_density(sim._h, (c_int * max(len(qs), 1))(*qs), len(qs) if k is None else k, out)
+        before = plans.sweeps_launched("density")
+        call = lambda qs, k=None: lib.qsim_reduced_density(sim._h, _ints(qs), len(qs) if k is None else k, out)
         assert call([0, 1]) == _lib.QSIM_OK
-        assert lib.qsim_density_sweeps_launched() == before + 1
+        assert plans.sweeps_launched("density") == before + 1
         for qs in ([0, 0], [6], [-1], [2, 5, 2], [0, 1, 2, 3, 4, 5]):
             assert call(qs) == _lib.ERR_ARG
         assert call([0], -1) == _lib.ERR_ARG
@@ -279,7 +271,7 @@ def test_errors(precision):
         assert lib.qsim_reduced_density(sim._h, None, 0, out) == _lib.QSIM_OK
         assert lib.qsim_reduced_density(sim._h, (c_int * 1)(0), 1, None) == _lib.ERR_ARG
         assert lib.qsim_reduced_density(None, (c_int * 1)(0), 1, out) == _lib.ERR_ARG
-        assert lib.qsim_density_sweeps_launched() == before + 2  # nothing was launched for a refused call
+        assert plans.sweeps_launched("density") == before + 2  # nothing was launched for a refused call
         with pytest.raises(QsimError):
             sim.reduced_density_matrix([0, 1, 2, 3, 4, 5])
     with Simulator(2, precision=precision) as sim:

@@ -11,7 +11,7 @@ the calls on a register of ONE qubit are held to it together (test_energy_and_gr
 diagonal, whose gradient is zero, has a bound from the format's precision instead.  The energy by controlled_adjoint_ref.energy_tol with w D_obs counted as one more term of weight |w| max|d|.  The
 state afterwards by the two-sided rule of the rotation tests.
 Sizes: n = 1 and 6 (the plain path), 7 (exactly one wave block of 64 items), 10 (several workgroups) and the smallest n at which
-qsim_diagonal_gradient_plan reports more than one trip per workgroup with the grid at its cap."""
+plans.diagonal_gradient_plan reports more than one trip per workgroup with the grid at its cap."""
 import contextlib
 import ctypes
 import math
@@ -26,7 +26,7 @@ import diagonal_ref
 import fp32_ref
 from diag_adjoint_ref import Diag
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Circuit, Cluster, Diagonal, Simulator, _lib, circuits
+from gpu_quantum_simulator_amd import Circuit, Cluster, Diagonal, Simulator, _lib, circuits, plans
 from pauli_rot_ref import rand_state
 
 pytestmark = pytest.mark.gpu
@@ -39,8 +39,7 @@ DP = ctypes.POINTER(ctypes.c_double)
 
 
 def _counters():
-    lib = _lib.load()
-    return np.array([lib.qsim_diagonal_adjoint_sweeps_launched(), lib.qsim_pauli_adjoint_sweeps_launched(), lib.qsim_diagonal_sweeps_launched()], dtype=np.int64)
+    return np.array([plans.sweeps_launched("diagonal_adjoint"), plans.sweeps_launched("pauli_adjoint"), plans.sweeps_launched("diagonal")], dtype=np.int64)
 
 
 def _bits(sim):
@@ -134,8 +133,8 @@ def _one_call(precision, n, start, steps, terms, obs, label, nonzero=True, fp32_
         after = sim.read()
     plan = ref.plan(steps, terms, obs, n, precision)
     num_diag = sum(1 for s in steps if ref.is_diag(s))
-    assert taken[0] == plan["diag_adjoint"] == num_diag, (label, taken, plan)       # one backward diagonal sweep per diagonal step
-    assert taken[1] == plan["pauli_adjoint"], (label, taken, plan)                   # none of them in the Pauli counter
+    assert taken[0] == plan["diag_adjoint_sweeps"] == num_diag, (label, taken, plan)       # one backward diagonal sweep per diagonal step
+    assert taken[1] == plan["pauli_adjoint_sweeps"], (label, taken, plan)                   # none of them in the Pauli counter
     assert taken[2] == num_diag + (1 if obs is not None else 0), (label, taken)      # the forward phases and the k_diag_apply sweep
     g64, g32 = _check(precision, energy, grad, before, steps, terms, obs, label, nonzero, fp32_criterion)
     _state_back(precision, after, before, steps, label)
@@ -230,7 +229,7 @@ def test_where_the_sweep_loops(precision, loop_data):
     Every operator of that call is diagonal, so its gradient is zero; a second call puts a rotation between two such steps and adds a
     Pauli term to H, so that its gradient is not."""
     n, start, d_step, d_obs = loop_data
-    assert ref.plan([Diag(0.0, None)], [], None, n, precision)["trips"] > 1 and ref.plan([Diag(0.0, None)], [], None, n - 1, precision)["trips"] == 1
+    assert ref.plan([Diag(0.0, None)], [], None, n, precision)["diag_adjoint_trips_at_cap"] > 1 and ref.plan([Diag(0.0, None)], [], None, n - 1, precision)["diag_adjoint_trips_at_cap"] == 1
     steps = [Diag(0.61, d_step)]
     _, want, _ = _one_call(precision, n, start, steps, [], (1.0, d_obs), f"looping, H diagonal, n={n}", nonzero=False)
     assert np.max(np.abs(want)) < 1e-12
@@ -366,7 +365,7 @@ def test_without_a_diagonal_the_bits_of_the_pauli_gradient(precision):
                                                       ctypes.byref(e), g.ctypes.data_as(DP)))
                 energy = e.value
             taken = _counters() - count
-            assert taken[0] == 0 and taken[2] == 0 and taken[1] == ref.plan(rotations, terms, None, n, precision)["pauli_adjoint"]
+            assert taken[0] == 0 and taken[2] == 0 and taken[1] == ref.plan(rotations, terms, None, n, precision)["pauli_adjoint_sweeps"]
             out.append((np.float64(energy).view(np.uint64), g.view(np.uint64).copy(), _bits(sim)))
     assert np.max(np.abs(out[0][1].view(np.float64))) > 1e-3
     for other in out[1:]:

@@ -11,7 +11,7 @@ multiplied in complex64.
 Moments: |mean - numpy| <= 1e-10 max|d| and the second moment likewise with max d^2: sums of 2^n products of weights that add up to
 one, in fp64 — only the order of the additions differs.
 Sizes: n = 0 (no 16-byte unit of the table), 1, 2, 3, 6 (the largest register on the plain path), 7 (the smallest on the main one:
-one wave), 9, and per precision the smallest n at which qsim_diagonal_plan reports more than one trip per workgroup for both sweeps
+one wave), 9, and per precision the smallest n at which plans.diagonal_plan reports more than one trip per workgroup for both sweeps
 with the grid at its cap."""
 import numpy as np
 import pytest
@@ -20,7 +20,7 @@ import diagonal_ref
 import fp32_ref
 import pauli_rot_ref
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Circuit, Cluster, Diagonal, Simulator, _lib, circuits
+from gpu_quantum_simulator_amd import Circuit, Cluster, Diagonal, Simulator, _lib, circuits, plans
 from pauli_rot_ref import rand_state
 
 pytestmark = pytest.mark.gpu
@@ -160,9 +160,9 @@ def test_phase_equals_the_z_rotations(precision):
         for s in (sim, twin):
             s.write(rand_state(n, 120))
         before = sim.read()
-        sweeps = _lib.load().qsim_diagonal_sweeps_launched()
+        sweeps = plans.sweeps_launched("diagonal")
         sim.apply_diagonal_phase(diag, gamma)
-        assert _lib.load().qsim_diagonal_sweeps_launched() == sweeps + 1
+        assert plans.sweeps_launched("diagonal") == sweeps + 1
         twin.apply_pauli_rotations([(2.0 * gamma * c, text) for c, text in texts])
         got, rotated = sim.read(), twin.read()
         rotations = [(2.0 * gamma * c, 0, z) for c, z in terms]
@@ -293,10 +293,10 @@ def test_a_shard_that_holds_nothing_stays_untouched(precision):
     with Simulator(n, precision=precision) as sim, Diagonal(n) as diag:
         diag.write(_table(n, 520))
         sim.reset(holds_index0=False)
-        sweeps = _lib.load().qsim_diagonal_sweeps_launched()
+        sweeps = plans.sweeps_launched("diagonal")
         sim.apply_diagonal_phase(diag, GAMMA)
         assert sim.expectation_diagonal(diag, moments=True) == (0.0, 0.0)
-        assert _lib.load().qsim_diagonal_sweeps_launched() == sweeps
+        assert plans.sweeps_launched("diagonal") == sweeps
         assert _lib.load().qsim_holds_nothing(sim._h) == 1 and not sim.read().any()
 
 

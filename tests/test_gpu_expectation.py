@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import pauli_ref
-from gpu_quantum_simulator_amd import Circuit, Cluster, ShardPlanHandle, Simulator, _lib, circuits
+from gpu_quantum_simulator_amd import Circuit, Cluster, ShardPlanHandle, Simulator, _lib, circuits, plans
 from helpers import random_unitary
 
 pytestmark = pytest.mark.gpu
@@ -67,7 +67,7 @@ def test_random_strings_of_every_weight(n, precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_large_groups_duplicates_identity_and_order(precision):
     n = 12
-    K = _lib.load().qsim_pauli_terms_per_sweep()
+    K = plans.pauli_terms_per_sweep()
     rng = np.random.default_rng(7)
     big = 3 * K + 5
     diag = [(0, int(z)) for z in rng.choice(np.arange(1, 1 << n), size=big, replace=False)]

@@ -23,7 +23,7 @@ import pytest
 import diagonal_ref
 import fp32_ref
 import large_ref as lr
-from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib
+from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib, plans
 from gpu_quantum_simulator_amd._lib import QsimError
 
 pytestmark = pytest.mark.gpu
@@ -222,14 +222,11 @@ def test_postselect(precision, name):
 def test_density_matrices(precision):
     sim, emb, plan, s64, s32 = _run_case("density", precision)
     with sim:
-        from ctypes import byref, c_int, c_long, c_uint64
         for query in lr.CASES["density"][2]:                                # k = 10 runs in several slices (and blocks) at this size
             if query[0] == "sdm" and len(query[1]) == 10:
                 qs = emb.qubits(query[1])
-                path, rows, blocks, slices, read, scratch, trips = c_int(-1), c_int(-1), c_long(-1), c_long(-1), c_uint64(0), c_uint64(0), c_long(-1)
-                assert _lib.load().qsim_subsystem_density_plan((c_int * 10)(*qs), 10, emb.n, precision, byref(path), byref(rows), byref(blocks), byref(slices),
-                                                               byref(read), byref(scratch), byref(trips)) == _lib.QSIM_OK
-                assert path.value == 1 and slices.value > 1 and blocks.value > 1, (qs, slices.value, blocks.value)
+                p = plans.ok(plans.subsystem_density_plan(qs, emb.n, precision, k=10))
+                assert p["path"] == 1 and p["slices"] > 1 and p["upper_blocks"] > 1, (qs, p["slices"], p["upper_blocks"])
         bits = [np.ascontiguousarray(sim.read(f, c)).view(np.uint64) for f, c in plan[:12]]
         wide32, worst = s32.astype(np.complex128), 0.0
         spectator = emb.spectators[-1]                                     # the highest spectator: 31 > q > 21
@@ -570,12 +567,7 @@ def test_ground_state_for_a_few_steps(precision):
 
 
 def _matrix_path(targets, controls, n, precision):
-    from ctypes import byref, c_int, c_long, c_uint64
-    ints = lambda v: (c_int * max(len(v), 1))(*v)
-    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    assert _lib.load().qsim_apply_matrix_plan(ints(targets), len(targets), ints(controls), len(controls), n, precision, byref(path), byref(padded),
-                                              byref(mask), byref(units), byref(trips)) == _lib.QSIM_OK
-    return path.value
+    return plans.ok(plans.apply_matrix_plan(targets, controls, n, precision))["path"]
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)

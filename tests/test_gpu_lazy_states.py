@@ -24,7 +24,7 @@ import pytest
 import fp32_ref
 import lazy_cases as L
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import Circuit, Diagonal, Simulator, _lib, circuits, pauli_masks
+from gpu_quantum_simulator_amd import Circuit, Diagonal, Simulator, circuits, pauli_masks, plans
 from gpu_quantum_simulator_amd.pauli import control_mask
 
 pytestmark = pytest.mark.gpu
@@ -177,48 +177,29 @@ class Side:
 
 def _plan_path(case, precision):
     """The *path the feature's plan call reports for the case's operands at n = 15 (host only)."""
-    from ctypes import byref, c_int, c_long, c_uint64
-    lib, o = _lib.load(), case.operands
-    ints = lambda qs: (c_int * max(len(qs), 1))(*qs)
-    path, i0, l0, l1, l2, u0, u1, u2 = c_int(-1), c_int(), c_long(), c_long(), c_long(), c_uint64(), c_uint64(), c_uint64()
+    o = case.operands
     if case.method == "apply_matrix":
-        rc = lib.qsim_apply_matrix_plan(ints(o["targets"]), len(o["targets"]), ints(o["controls"]), len(o["controls"]), N, precision, byref(path), byref(i0),
-                                        byref(u0), byref(u1), byref(l0))
+        probe = plans.apply_matrix_plan(o["targets"], o["controls"], N, precision)
     elif case.method == "apply_permutation":
-        rc = lib.qsim_apply_permutation_plan(ints(o["targets"]), len(o["targets"]), ints(o["controls"]), len(o["controls"]), N, precision, byref(path),
-                                             byref(i0), byref(u0), byref(u1), byref(u2), byref(l0))
+        probe = plans.apply_permutation_plan(o["targets"], o["controls"], N, precision)
     elif case.method == "reduced_density_matrix":
-        rc = lib.qsim_reduced_density_plan(ints(o["qubits"]), len(o["qubits"]), N, precision, byref(path), byref(i0), byref(u0), byref(u1), byref(l0))
+        probe = plans.reduced_density_plan(o["qubits"], N, precision)
     else:
-        rc = lib.qsim_subsystem_density_plan(ints(o["qubits"]), len(o["qubits"]), N, precision, byref(path), byref(i0), byref(l0), byref(l1), byref(u0),
-                                             byref(u1), byref(l2))
-    assert rc == _lib.QSIM_OK
-    return path.value
+        probe = plans.subsystem_density_plan(o["qubits"], N, precision)
+    return plans.ok(probe)["path"]
 
 
 def _queued_as_gates(rotations, precision):
     """How many of the (theta, string[, controls]) entries the rotation calls send through the gate queue (host only)."""
-    from ctypes import byref, c_long, c_uint64
-    up = ctypes.POINTER(c_uint64)
     rotations = [tuple(r) + ((),) * (3 - len(r)) for r in rotations]
     masks = [pauli_masks(text, N) for _, text, _ in rotations]
-    cs = np.array([control_mask(c, N, text) for _, text, c in rotations], dtype=np.uint64)
-    xs, zs = np.array([m[0] for m in masks], dtype=np.uint64), np.array([m[1] for m in masks], dtype=np.uint64)
-    sweeps, gates, units = c_long(-1), c_long(-1), c_uint64(0)
-    _lib.check(_lib.load().qsim_controlled_rotation_plan(cs.ctypes.data_as(up), xs.ctypes.data_as(up), zs.ctypes.data_as(up), len(rotations), N, precision,
-                                                         byref(sweeps), byref(gates), byref(units)))
-    return gates.value
+    cs = [control_mask(c, N, text) for _, text, c in rotations]
+    return plans.ok(plans.controlled_rotation_plan(cs, [m[0] for m in masks], [m[1] for m in masks], N, precision, num_terms=len(rotations)))["queued_as_gates"]
 
 
 def _qft_moves(case, precision):
     """Whether the plan of the case's Fourier transform has a sweep that writes the second buffer (host only)."""
-    from ctypes import byref, c_int, c_long, c_uint64
-    qs = case.operands["qubits"]
-    passes, digits, oop, masks = c_int(-1), (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-    tiles, units, trips = c_uint64(), c_uint64(), c_long()
-    _lib.check(_lib.load().qsim_apply_qft_plan((c_int * len(qs))(*qs), len(qs), N, precision, case.operands["max_digit_bits"], byref(passes), digits, oop,
-                                               masks, byref(tiles), byref(units), byref(trips)))
-    return any(oop[p] for p in range(passes.value))
+    return any(plans.ok(plans.apply_qft_plan(case.operands["qubits"], N, precision, case.operands["max_digit_bits"]))["out_of_place"])
 
 
 def _likely_outcome(start, precision, qubits):

@@ -10,14 +10,15 @@ subset size (from the plan call), n = 13 for the matrix path's subsets and contr
 call reports at least two trips per workgroup."""
 import functools
 import itertools
-from ctypes import POINTER, byref, c_double, c_int, c_long, c_uint64
+from ctypes import POINTER, c_double
 
 import numpy as np
 import pytest
 
 import fp32_ref
 import matrix_ref
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from gpu_quantum_simulator_amd._lib import QsimError
 from helpers import np_apply_1q, np_apply_2q, np_apply_cx, random_unitary
 from pauli_rot_ref import rand_state
@@ -29,22 +30,6 @@ PRECISIONS = [64, 32]
 H = np.array([[1, 1], [1, -1]]) / np.sqrt(2.0)
 X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 Z = np.diag([1.0, -1.0]).astype(np.complex128)
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _plan(targets, controls, n, precision):
-    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_apply_matrix_plan(_ints(targets), len(targets), _ints(controls), len(controls), n, precision, byref(path), byref(padded),
-                                            byref(mask), byref(units), byref(trips))
-    assert rc == _lib.QSIM_OK
-    return dict(path=path.value, padded_k=padded.value, mask=mask.value, units=units.value, trips=trips.value)
-
-
-def _sweeps():
-    return _lib.load().qsim_matrix_sweeps_launched()
 
 
 def _compare(sim, got, before, U, targets, controls, label):
@@ -65,9 +50,9 @@ def _compare(sim, got, before, U, targets, controls, label):
 
 def _apply_and_check(sim, before, U, targets, controls=(), label=""):
     """One call on the device against the checker on `before` (the state as read back); returns the state after it."""
-    count = _sweeps()
+    count = plans.sweeps_launched("matrix")
     sim.apply_matrix(U, targets, controls)
-    assert _sweeps() == count + 1
+    assert plans.sweeps_launched("matrix") == count + 1
     got = sim.read()
     _compare(sim, got, before, U, targets, controls, label)
     return got
@@ -95,7 +80,7 @@ def test_plain_path_every_subset(n, precision):
         for k in range(0, n + 1):
             for ts in itertools.combinations(range(n), k):
                 for targets in ({ts, ts[::-1]}):
-                    assert _plan(targets, [], n, precision)["path"] == 0
+                    assert plans.ok(plans.apply_matrix_plan(targets, [], n, precision))["path"] == 0
                     psi = _apply_and_check(sim, psi, random_unitary(1 << k, rng), targets, (), "plain")
                 rest = [q for q in range(n) if q not in ts]
                 if rest:
@@ -109,18 +94,18 @@ def test_path_switch(k, precision):
     """The smallest register the matrix path takes for this subset size, and the one below it: both from the plan call."""
     rng = np.random.default_rng(520 + k)
     for low in (0, 1):                                           # fp32: with qubit 0 in the subset and without (one qubit later)
-        first = next(n for n in range(k + low, 16) if _plan(list(range(low, low + k)), [], n, precision)["path"] == 1)
-        assert _plan(list(range(low, low + k)), [], first - 1, precision)["path"] == 0
+        first = next(n for n in range(k + low, 16) if plans.ok(plans.apply_matrix_plan(list(range(low, low + k)), [], n, precision))["path"] == 1)
+        assert plans.ok(plans.apply_matrix_plan(list(range(low, low + k)), [], first - 1, precision))["path"] == 0
         for n in (first - 1, first):
             sim, psi = _sim_with(n, precision, 520 + n)
             with sim:
                 for targets in {tuple(range(low, low + k)), tuple(range(n - k, n)), tuple(range(n - 1, n - 1 - k, -1))}:
                     if precision == 64 or (0 in targets) == (low == 0):  # fp32: the switch depends on whether qubit 0 is in the subset
-                        assert _plan(targets, [], n, precision)["path"] == (1 if n == first else 0)
+                        assert plans.ok(plans.apply_matrix_plan(targets, [], n, precision))["path"] == (1 if n == first else 0)
                     psi = _apply_and_check(sim, psi, random_unitary(1 << k, rng), targets, (), "switch")
                 # one control on the larger register is the smaller one's count of environments
                 free = [q for q in range(n) if q >= low + k]
-                assert _plan(list(range(low, low + k)), free[-1:], n, precision)["path"] == 0
+                assert plans.ok(plans.apply_matrix_plan(list(range(low, low + k)), free[-1:], n, precision))["path"] == 0
                 psi = _apply_and_check(sim, psi, random_unitary(1 << k, rng), list(range(low, low + k)), free[-1:], "switch")
 
 
@@ -148,7 +133,7 @@ def test_matrix_path_subsets_and_controls(precision):
             assert [len(c) for c in sets].count(1) >= 1 and len(sets[-1]) == 3
             for controls in sets:
                 assert not set(controls) & set(targets)
-                assert _plan(targets, controls, n, precision)["path"] == 1
+                assert plans.ok(plans.apply_matrix_plan(targets, controls, n, precision))["path"] == 1
                 psi = _apply_and_check(sim, psi, random_unitary(1 << len(targets), rng), targets, controls, "matrix")
                 if len(controls) == 1:
                     seen["q0" if controls[0] == 0 else "q12" if controls[0] == 12 else "between"] += 1
@@ -167,7 +152,7 @@ def test_enough_controls_for_the_small_path(precision):
             paths = []
             for c in range(1, len(pool) + 1):
                 controls = pool[:c]
-                paths.append(_plan(targets, controls, n, precision)["path"])
+                paths.append(plans.ok(plans.apply_matrix_plan(targets, controls, n, precision))["path"])
                 if len(paths) >= 2 and paths[-2:] == [0, 0]:
                     break
                 psi = _apply_and_check(sim, psi, random_unitary(1 << len(targets), rng), targets, controls, "controls")
@@ -190,9 +175,9 @@ def test_exact_cases(precision):
                                      (X, [0], []), (X, [12], []), (X, [6], [0]), (X, [0], [3, 9]),
                                      (swap, [0, 12], []), (swap, [5, 4], [0]), (toffoli, [3, 8, 0], []), (toffoli, [12, 1, 6], [0]),
                                      (perm32, [1, 3, 6, 9, 12], []), (perm32, [4, 0, 3, 2, 1], [8]), (perm32, [8, 9, 10, 11, 12], [0, 1])):
-            count = _sweeps()
+            count = plans.sweeps_launched("matrix")
             sim.apply_matrix(U, targets, controls)
-            assert _sweeps() == count + 1
+            assert plans.sweeps_launched("matrix") == count + 1
             got = sim.read()
             want = matrix_ref.apply_matrix(psi, U, targets, controls)
             assert np.array_equal(got, want), (targets, controls)
@@ -302,8 +287,8 @@ def test_looping(k, controlled, precision):
         sim.write(_large_state(n))
         psi = sim.read()
         for targets in (list(range(k)), list(range(n - 1 - k, n - 1)), [n - 2, 3, 9, 7, 1][:k]):
-            p = _plan(targets, controls, n, precision)
-            assert p["path"] == 1 and p["trips"] >= 2
+            p = plans.ok(plans.apply_matrix_plan(targets, controls, n, precision))
+            assert p["path"] == 1 and p["trips_per_workgroup"] >= 2
             psi = _apply_and_check(sim, psi, random_unitary(1 << k, rng), targets, controls, "looping")
 
 
@@ -347,9 +332,9 @@ def test_queued_gates_before_and_after(precision):
         sim.apply_cx(12, 3)
         psi = np_apply_cx(psi, n, 12, 3)
         U = random_unitary(8, rng)
-        count = _sweeps()
+        count = plans.sweeps_launched("matrix")
         sim.apply_matrix(U, [12, 3, 0], [7])
-        assert _sweeps() == count + 1
+        assert plans.sweeps_launched("matrix") == count + 1
         psi = matrix_ref.apply_matrix(psi, U, [12, 3, 0], [7])
         v = random_unitary(4, rng)
         sim.apply_2q(v, 9, 0)                                    # queued behind the sweep: it sees the sweep's result
@@ -394,15 +379,15 @@ def test_a_shard_that_holds_nothing(precision):
     rng = np.random.default_rng(610)
     with Simulator(13, precision=precision) as sim:
         sim.reset(holds_index0=False)
-        before = _sweeps()
+        before = plans.sweeps_launched("matrix")
         for targets, controls in (([], []), ([0], []), ([12, 3, 4], [0]), ([0, 1, 2, 3, 4], [])):
             sim.apply_matrix(random_unitary(1 << len(targets), rng), targets, controls)
-        assert _sweeps() == before
+        assert plans.sweeps_launched("matrix") == before
         assert _lib.load().qsim_holds_nothing(sim._h) == 1
         assert np.array_equal(sim.read(), np.zeros(1 << 13))
         sim.reset()
         sim.apply_matrix(random_unitary(8, rng), [12, 3, 4])
-        assert _sweeps() == before + 1
+        assert plans.sweeps_launched("matrix") == before + 1
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------------
@@ -416,12 +401,12 @@ def test_refusals(precision):
     with Simulator(6, precision=precision) as sim:
         sim.write(rand_state(6, 1))
         state = sim.read().view(np.uint64).copy()
-        before = _sweeps()
+        before = plans.sweeps_launched("matrix")
         # the identity of the targets' size (of five qubits where the count itself is what is refused)
         call = lambda ts, cs=(), k=None, c=None: lib.qsim_apply_matrix(sim._h, eyes[min(len(ts), 5)].ctypes.data_as(DP), _ints(ts),
                                                                      len(ts) if k is None else k, _ints(cs), len(cs) if c is None else c)
         assert call([0, 1]) == _lib.QSIM_OK and call([0, 1], [5]) == _lib.QSIM_OK and call([], [2]) == _lib.QSIM_OK
-        assert _sweeps() == before + 3
+        assert plans.sweeps_launched("matrix") == before + 3
         assert np.array_equal(sim.read().view(np.uint64), state)  # the identity, three times
         for ts, cs in (([0, 0], []), ([6], []), ([-1], []), ([2, 5, 2], []), ([0, 1, 2, 3, 4, 5], []), ([0], [0]), ([0, 1], [3, 1]), ([0], [6]),
                        ([0], [-1]), ([0], [2, 2])):
@@ -436,7 +421,7 @@ def test_refusals(precision):
             v[5] = bad
             assert lib.qsim_apply_matrix(sim._h, v.ctypes.data_as(DP), _ints([0, 3]), 2, None, 0) == _lib.ERR_ARG
         assert lib.qsim_apply_matrix(sim._h, up, None, 0, None, 0) == _lib.QSIM_OK   # k = 0 needs no list: the scalar 1
-        assert _sweeps() == before + 4                           # nothing was launched for a refused call
+        assert plans.sweeps_launched("matrix") == before + 4                           # nothing was launched for a refused call
         assert np.array_equal(sim.read().view(np.uint64), state)
         with pytest.raises(QsimError):
             sim.apply_matrix(np.eye(2), [0], [0])
@@ -446,7 +431,7 @@ def test_refusals(precision):
             sim.apply_matrix(np.eye(4), [0])                     # the shape does not fit the targets
         with pytest.raises(ValueError):
             sim.apply_matrix(np.eye(64), [0, 1, 2, 3, 4, 5])
-        assert _sweeps() == before + 4
+        assert plans.sweeps_launched("matrix") == before + 4
     with Simulator(2, precision=precision) as sim:
         assert lib.qsim_apply_matrix(sim._h, up, _ints([0, 1, 1]), 3, None, 0) == _lib.ERR_ARG  # k > n
 

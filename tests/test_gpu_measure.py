@@ -10,7 +10,7 @@ Sizes: n <= 4 exhaustively, n = 13 for k = 1, 2, 5, 10, 13, and n = 22 (fp64) / 
 workgroup of the collapse sweep at the default grid."""
 import functools
 import math
-from ctypes import byref, c_double, c_int, c_long, c_uint64
+from ctypes import byref, c_double, c_uint64
 
 import numpy as np
 import pytest
@@ -19,7 +19,8 @@ import fp32_ref
 import lazy_cases
 import matrix_ref
 import measure_ref
-from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, channels, gate_matrix
+from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, channels, gate_matrix, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from gpu_quantum_simulator_amd._lib import QsimError
 from pauli_rot_ref import rand_state
 from test_gpu_lazy_states import Side, _dense
@@ -29,22 +30,8 @@ TOL = 1e-10
 PRECISIONS = [64, 32]
 
 
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _sweeps():
-    return _lib.load().qsim_collapse_sweeps_launched()
-
-
 def _bits(state):
     return np.ascontiguousarray(state).view(np.uint64)
-
-
-def _collapse_trips(qubits, outcome, n, precision):
-    wu, cu, wt, ct = c_uint64(0), c_uint64(0), c_long(-1), c_long(-1)
-    assert _lib.load().qsim_collapse_plan(_ints(qubits), len(qubits), outcome, n, precision, byref(wu), byref(cu), byref(wt), byref(ct)) == _lib.QSIM_OK
-    return ct.value
 
 
 def _check_state(got, before, qubits, outcome, precision, label):
@@ -70,9 +57,9 @@ def _check_weight(got_w, want_w, kept, label):
 
 
 def _postselect_and_check(sim, before, qubits, outcome, label=""):
-    count = _sweeps()
+    count = plans.sweeps_launched("collapse")
     W = sim.postselect(qubits, outcome)
-    assert _sweeps() == count + 2
+    assert plans.sweeps_launched("collapse") == count + 2
     got = sim.read()
     label = f"n={sim.num_qubits} p{sim.precision} q={qubits} o={outcome} {label}"
     want_w = _check_state(got, before, qubits, outcome, sim.precision, label)
@@ -119,7 +106,7 @@ def _large_state(n):
 @pytest.mark.parametrize("which", [0, 1])
 def test_looping_at_the_default_grid(which, precision):
     n, qubits, outcome = measure_ref.looping_cases(precision)[which]
-    assert _collapse_trips(qubits, outcome, n, precision) >= 2
+    assert plans.ok(plans.collapse_plan(qubits, outcome, n, precision))["collapse_trips"] >= 2
     with Simulator(n, precision=precision) as sim:
         sim.write(_large_state(n))
         _postselect_and_check(sim, sim.read(), qubits, outcome)
@@ -152,9 +139,9 @@ def test_the_discarded_part_is_never_read(precision):
             dirty = np.where(keep, clean, poison[np.arange(1 << n) % 3])
             sim.write(dirty)                                               # a plain copy: the buffer holds NaN and Inf outside the kept subspace
             held = np.where(keep, sim.read(), 0.0)                           # what the kept part holds, zeros elsewhere for the checker
-            count = _sweeps()
+            count = plans.sweeps_launched("collapse")
             W = sim.postselect(qubits, outcome)
-            assert _sweeps() == count + 2 and math.isfinite(W)
+            assert plans.sweeps_launched("collapse") == count + 2 and math.isfinite(W)
             got = sim.read()
             assert np.isfinite(got.real).all() and np.isfinite(got.imag).all(), (qubits, outcome)
             label = f"poisoned p{precision} q={qubits} o={outcome}"
@@ -174,9 +161,9 @@ def test_measure_agrees_with_the_sampler(qubits, precision):
             u = (i + 0.5) / 64
             sim.write(psi)
             drawn = int(sim.sample_shots(draws=[u], qubits=qubits)[0])
-            count = _sweeps()
+            count = plans.sweeps_launched("collapse")
             outcome, p = sim.measure(qubits, draw=u, return_probability=True)
-            assert _sweeps() == count + 2
+            assert plans.sweeps_launched("collapse") == count + 2
             assert outcome == drawn, (u, outcome, drawn)
             assert outcome in measure_ref.admissible_outcomes(n, psi, u, qubits), (u, outcome)
             got = sim.read()
@@ -204,11 +191,11 @@ def test_refusals(precision):
         psi[(np.arange(1 << n) & 0b100000100) == 0b100000000] = 0.0          # qubit 8 one and qubit 2 zero never happens
         sim.write(psi)
         state = _bits(sim.read()).copy()
-        before = _sweeps()
+        before = plans.sweeps_launched("collapse")
         with pytest.raises(QsimError) as err:                              # an outcome of probability zero
             sim.postselect([2, 8], 0b10)
         assert err.value.code == _lib.ERR_ARG and "probability zero" in str(err.value)
-        assert _sweeps() == before and np.array_equal(_bits(sim.read()), state)
+        assert plans.sweeps_launched("collapse") == before and np.array_equal(_bits(sim.read()), state)
         for bad in (lambda: sim.postselect([0, 0], 0), lambda: sim.postselect([2, 5, 2], 1), lambda: sim.postselect([n], 0), lambda: sim.postselect([-1], 0),
                     lambda: sim.postselect(list(range(n)) + [3], 0), lambda: sim.postselect([0, 1], 4), lambda: sim.postselect([], 1),
                     lambda: sim.measure([0, 0], draw=0.5), lambda: sim.measure([n], draw=0.5), lambda: sim.measure([0], draw=1.5),
@@ -223,21 +210,21 @@ def test_refusals(precision):
         assert lib.qsim_postselect(sim._h, _ints([0]), 1, 0, None) == _lib.ERR_ARG and lib.qsim_postselect(None, _ints([0]), 1, 0, byref(w)) == _lib.ERR_ARG
         assert lib.qsim_measure(sim._h, _ints([0]), 1, 0.5, None, byref(w)) == _lib.ERR_ARG and lib.qsim_measure(sim._h, _ints([0]), 1, 0.5, byref(out), None) == _lib.ERR_ARG
         assert lib.qsim_measure(sim._h, _ints(list(range(n + 1))), n + 1, 0.5, byref(out), byref(w)) == _lib.ERR_ARG
-        assert _sweeps() == before
+        assert plans.sweeps_launched("collapse") == before
         assert np.array_equal(_bits(sim.read()), state)
         sim.reset(holds_index0=False)                                      # a state that holds nothing: every outcome has probability zero
         for bad in (lambda: sim.postselect([0], 0), lambda: sim.measure([0], draw=0.5), lambda: sim.postselect([], 0)):
             with pytest.raises(QsimError) as err:
                 bad()
             assert err.value.code == _lib.ERR_ARG
-        assert _sweeps() == before and lib.qsim_holds_nothing(sim._h) == 1
+        assert plans.sweeps_launched("collapse") == before and lib.qsim_holds_nothing(sim._h) == 1
     with Simulator(3, precision=precision) as sim:                         # the zero vector, written out: its total is zero
         sim.write(np.zeros(8))
         for bad in (lambda: sim.postselect([1], 0), lambda: sim.measure([1], draw=0.5)):
             with pytest.raises(QsimError) as err:
                 bad()
             assert err.value.code == _lib.ERR_ARG
-        assert _sweeps() == before and not sim.read().any()
+        assert plans.sweeps_launched("collapse") == before and not sim.read().any()
 
 
 # ---- order with the gate queue ----------------------------------------------------------------------------------------------------------------
@@ -253,9 +240,9 @@ def test_queued_gates_land_first(precision):
     assert np.count_nonzero(before) == 16
     with Simulator(n, precision=precision) as sim:
         sim.run(circuit)                                                   # queued, not flushed
-        count = _sweeps()
+        count = plans.sweeps_launched("collapse")
         outcome, p = sim.measure(qubits, draw=u, return_probability=True)
-        assert _sweeps() == count + 2 and outcome == want_outcome
+        assert plans.sweeps_launched("collapse") == count + 2 and outcome == want_outcome
         assert (outcome >> 2) & 1 == 1 and (outcome & 1) == ((outcome >> 1) & 1)   # qubit 3 was flipped, qubit 8 copies qubit 0
         assert p == pytest.approx(0.25, abs=1e-12 if precision == 64 else 1e-6)
         _check_state(sim.read(), before, qubits, outcome, precision, f"queued gates p{precision}")
@@ -320,9 +307,9 @@ def test_lazy_starts_over_poisoned_memory(call, qubits, start, precision):
     for lazy in (True, False):
         with Side(precision, lazy) as side:
             sim = side.state(start)
-            count = _sweeps()
+            count = plans.sweeps_launched("collapse")
             returned = sim.postselect(qubits, outcome) if call == "postselect" else sim.measure(qubits, draw=0.37, return_probability=True)
-            assert _sweeps() == count + 2
+            assert plans.sweeps_launched("collapse") == count + 2
             results.append((returned, sim.read()))
     (lazy_ret, lazy_got), (twin_ret, twin_got) = results
     assert not np.isnan(lazy_got).any()

@@ -24,7 +24,7 @@ import fp32_ref
 import pauli_ref
 import pauli_rot_ref as ref
 from fp32_ref import check_fp32, report
-from gpu_quantum_simulator_amd import Circuit, Cluster, ShardPlanHandle, Simulator, _lib, circuits, gate_matrix, pauli_masks, trotter_rotations
+from gpu_quantum_simulator_amd import Circuit, Cluster, ShardPlanHandle, Simulator, _lib, circuits, gate_matrix, pauli_masks, trotter_rotations, plans
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -53,16 +53,9 @@ def _close(precision, a, b, want, ref32):
         assert fp32_ref.rel_err(a, b) <= 2 * fp32_ref.C * max(fp32_ref.rel_err(ref32, want), fp32_ref.FLOOR)
 
 
-def _sweeps():
-    return _lib.load().qsim_pauli_rotation_sweeps_launched()
-
-
 def _plan(rotations):
-    xs = np.array([x for _, x, _ in rotations], dtype=np.uint64)
-    zs = np.array([z for _, _, z in rotations], dtype=np.uint64)
-    sweeps, gates = ctypes.c_long(-1), ctypes.c_long(-1)
-    _lib.check(_lib.load().qsim_pauli_rotation_plan(xs.ctypes.data_as(UP), zs.ctypes.data_as(UP), xs.size, ctypes.byref(sweeps), ctypes.byref(gates)))
-    return sweeps.value, gates.value
+    p = plans.ok(plans.pauli_rotation_plan([x for _, x, _ in rotations], [z for _, _, z in rotations]))
+    return p["sweeps"], p["queued_as_gates"]
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -115,7 +108,7 @@ def test_every_weight_one_call_each_and_fused(n, precision):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_runs_longer_than_k(precision):
     n = 12
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     diag, paired = ref.long_run_rotations(K)
     assert len(diag) == len(paired) == 3 * K + 5 and (0.9, 0, 0) in diag
     thetas = {t for t, _, _ in diag + paired}
@@ -124,9 +117,9 @@ def test_runs_longer_than_k(precision):
         sim.write(ref.rand_state(n, 12))
         for label, run in (("diagonal", diag), ("paired", paired), ("both", diag + paired)):
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             sim.apply_pauli_rotations(ref.texts(run, n))
-            taken = _sweeps() - count
+            taken = plans.sweeps_launched("pauli_rotation") - count
             assert (taken, 0) == _plan(run) and taken == -(-len(diag) // K) * (len(run) // len(diag)), (label, taken)
             _check(precision, sim.read(), before, run, f"run of {len(run)} {label} p{precision}")
 
@@ -141,9 +134,9 @@ def test_order_matters(precision):
         with Simulator(n, precision=precision) as sim:
             sim.write(ref.rand_state(n, 6))
             before = sim.read()
-            count = _sweeps()
+            count = plans.sweeps_launched("pauli_rotation")
             sim.apply_pauli_rotations(ref.texts(order, n))
-            assert _sweeps() - count == 1  # one x: one sweep, the order kept inside it
+            assert plans.sweeps_launched("pauli_rotation") - count == 1  # one x: one sweep, the order kept inside it
             results.append(sim.read())
             _check(precision, results[-1], before, order, f"order p{precision}")
     assert np.max(np.abs(results[0] - results[1])) > 1e-2
@@ -281,9 +274,9 @@ def test_evolve_diagonal_hamiltonian_is_exact(precision):
     with Simulator(n, precision=precision) as sim:
         sim.write(ref.rand_state(n, 10))
         before = sim.read()
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         sim.evolve(terms, t, steps=1)
-        assert _sweeps() - count == 1  # 30 all-Z terms: one sweep
+        assert plans.sweeps_launched("pauli_rotation") - count == 1  # 30 all-Z terms: one sweep
         got = sim.read()
     exact = np.exp(-1j * energy * t) * before
     rotations = ref.masks_of(trotter_rotations(terms, t), n)
@@ -446,9 +439,9 @@ def test_errors(precision):
             sim.evolve([(1.0, "Z0")], 1.0, order=3)
         assert np.array_equal(_bits(sim), before)
         sim.reset(holds_index0=False)  # a shard that holds nothing stays untouched
-        count = _sweeps()
+        count = plans.sweeps_launched("pauli_rotation")
         sim.apply_pauli_rotations([(0.3, "Z0 Z1"), (0.2, "X0 X1")])
-        assert _sweeps() == count and sim.get_support()[1:] == (1, 0.0)
+        assert plans.sweeps_launched("pauli_rotation") == count and sim.get_support()[1:] == (1, 0.0)
     if precision == 64:
         with Cluster(n, 2, devices=[0, 0]) as cl:
             assert lib.qsim_cluster_apply_pauli_rotations(None, okp, okp, thp, 2) == _lib.ERR_ARG

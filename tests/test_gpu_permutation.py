@@ -11,13 +11,14 @@ Sizes: n <= 4 (the tile is smaller than a workgroup), both sides of the path swi
 n = 22 (fp64) / 23 (fp32), where the plan call reports two trips per workgroup at the default grid."""
 import functools
 import itertools
-from ctypes import POINTER, byref, c_int, c_long, c_uint32, c_uint64
+from ctypes import POINTER, c_uint32
 
 import numpy as np
 import pytest
 
 import permutation_ref
-from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, permutations
+from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, permutations, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from helpers import np_apply_1q
 from pauli_rot_ref import rand_state
 
@@ -28,31 +29,15 @@ H = np.array([[1, 1], [1, -1]]) / np.sqrt(2.0)
 X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 
 
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _plan(targets, controls, n, precision):
-    path, tile_bits, mask, tiles, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_apply_permutation_plan(_ints(targets), len(targets), _ints(controls), len(controls), n, precision, byref(path),
-                                                 byref(tile_bits), byref(mask), byref(tiles), byref(units), byref(trips))
-    assert rc == _lib.QSIM_OK
-    return dict(path=path.value, tile_bits=tile_bits.value, mask=mask.value, tiles=tiles.value, units=units.value, trips=trips.value)
-
-
-def _sweeps():
-    return _lib.load().qsim_permutation_sweeps_launched()
-
-
 def _bits(state):
     return np.ascontiguousarray(state).view(np.uint64)
 
 
 def _apply_and_check(sim, before, perm, targets, controls=(), inverse=False):
     """One call on the device against the checker on `before` (the state as read back), bit for bit; returns the state after it."""
-    count = _sweeps()
+    count = plans.sweeps_launched("permutation")
     sim.apply_permutation(perm, targets, controls, inverse=inverse)
-    assert _sweeps() == count + 1
+    assert plans.sweeps_launched("permutation") == count + 1
     got = sim.read()
     want = permutation_ref.apply_permutation(before, permutations.inverse_table(perm) if inverse else perm, targets, controls)
     assert np.array_equal(_bits(got), _bits(want)), (sim.num_qubits, sim.precision, list(targets), list(controls))
@@ -88,7 +73,7 @@ def test_small_registers_every_subset_and_control_choice(n, precision):
                 for c in range(0, len(rest) + 1):
                     for controls in itertools.combinations(rest, c):
                         for targets in {ts, ts[::-1]}:
-                            p = _plan(targets, controls, n, precision)
+                            p = plans.ok(plans.apply_permutation_plan(targets, controls, n, precision))
                             assert p["path"] == 0 and p["tiles"] == 1 and p["tile_bits"] == n - c
                             psi = _apply_and_check(sim, psi, rng.permutation(1 << k), targets, controls)
 
@@ -108,7 +93,7 @@ def test_tile_boundaries(offset, precision):
             for targets in ([0], [n - 1, 0, 5], list(range(n - 5 - c, n - c)), [7, 2, 9, 4]):
                 pool = [q for q in (n - 1, 0, 3) if q not in targets] + [q for q in range(n) if q not in targets and q not in (n - 1, 0, 3)]
                 controls = pool[:c]
-                p = _plan(targets, controls, n, precision)
+                p = plans.ok(plans.apply_permutation_plan(targets, controls, n, precision))
                 assert p["path"] == (0 if offset < 0 else 1) and p["tiles"] == (2 if offset > 0 else 1) and p["tile_bits"] == full + min(offset, 0)
                 for perm in _tables(len(targets), rng)[:2]:
                     psi = _apply_and_check(sim, psi, perm, targets, controls)
@@ -148,7 +133,7 @@ def test_n13_tables_places_and_controls(k, precision):
             for controls in _n13_controls(targets):
                 assert not set(controls) & set(targets)
                 seen |= {("q0" if q == 0 else "top" if q == n - 1 else "mid") for q in controls} | {len(controls)}
-                p = _plan(targets, controls, n, precision)
+                p = plans.ok(plans.apply_permutation_plan(targets, controls, n, precision))
                 assert p["tile_bits"] == min(12 if precision == 64 else 13, n - len(controls)) and p["tiles"] == 1 << (n - len(controls) - p["tile_bits"])
                 for perm in _tables(k, rng):
                     psi = _apply_and_check(sim, psi, perm, targets, controls)
@@ -169,7 +154,7 @@ def test_two_workgroups_walk_several_tiles(precision):
             walked = 0
             for targets, controls in cases:
                 perm = rng.permutation(1 << len(targets))
-                walked = max(walked, _plan(targets, controls, n, precision)["tiles"] // 2)
+                walked = max(walked, plans.ok(plans.apply_permutation_plan(targets, controls, n, precision))["tiles"] // 2)
                 sim.set_option(_lib.OPT_GRID_CAP, 2)
                 sim.write(start)
                 first = _bits(_apply_and_check(sim, sim.read(), perm, targets, controls)).copy()
@@ -191,7 +176,7 @@ def test_looping_at_the_default_grid(precision):
     """The size at which every workgroup of the default grid walks at least two tiles: one call, k = 10 spread over the register."""
     n = 22 if precision == 64 else 23
     targets = [n - 1, 3, 17, 8, 12, 5, 20, 10, 15, 0]
-    assert _plan(targets, [], n, precision)["trips"] >= 2
+    assert plans.ok(plans.apply_permutation_plan(targets, [], n, precision))["trips_per_workgroup"] >= 2
     rng = np.random.default_rng(840)
     with Simulator(n, precision=precision) as sim:
         sim.write(_large_state(n))
@@ -250,12 +235,12 @@ def test_queued_gates_land_first(precision):
             want = twin.read()
     with Simulator(n, precision=precision) as sim:
         sim.run(circuit)
-        before = _sweeps()
+        before = plans.sweeps_launched("permutation")
         for j in counting:
             a = pow(7, 1 << j, 15)
             sim.apply_modular_multiply(a, 15, work, controls=[j])
             want = permutation_ref.apply_permutation(want, permutations.modular_multiply_table(a, 15, 4), work, [j])
-        assert _sweeps() == before + len(counting)
+        assert plans.sweeps_launched("permutation") == before + len(counting)
         got = sim.read()
     worst = float(np.max(np.abs(got - want)))
     print(f"queued gates p{precision}: max abs err {worst:.3e}")
@@ -276,9 +261,9 @@ def test_fresh_state_moves_index_zero(precision):
             if perm[0] == 0:
                 perm = np.roll(perm, 1)
             sim.reset()                                          # |0...0>, held lazily: nothing has run
-            count = _sweeps()
+            count = plans.sweeps_launched("permutation")
             sim.apply_permutation(perm, targets)
-            assert _sweeps() == count + 1
+            assert plans.sweeps_launched("permutation") == count + 1
             got = sim.read()
             at = permutation_ref.deposit(int(perm[0]), targets)
             assert at != 0 and got[at] == 1.0 and np.count_nonzero(got) == 1, (targets, at)
@@ -292,10 +277,10 @@ def test_fresh_state_moves_index_zero(precision):
 def test_a_state_that_holds_nothing(precision):
     with Simulator(13, precision=precision) as sim:
         sim.reset(holds_index0=False)
-        before = _sweeps()
+        before = plans.sweeps_launched("permutation")
         sim.apply_permutation([1, 0], [5])
         sim.apply_permutation(np.arange(1024)[::-1], list(range(10)), [12])
-        assert _sweeps() == before and _lib.load().qsim_holds_nothing(sim._h) == 1
+        assert plans.sweeps_launched("permutation") == before and _lib.load().qsim_holds_nothing(sim._h) == 1
         assert np.array_equal(sim.read(), np.zeros(1 << 13))
 
 
@@ -306,14 +291,14 @@ def test_helpers_on_the_device():
     rng = np.random.default_rng(880)
     with sim:
         values = rng.integers(0, 8, 32)
-        count = _sweeps()
+        count = plans.sweeps_launched("permutation")
         sim.apply_function_xor(values, [12, 0, 3, 7, 5], [1, 9, 4], controls=[2])
         want = permutation_ref.apply_permutation(psi, permutations.xor_function_table(values, 5, 3), [12, 0, 3, 7, 5, 1, 9, 4], [2])
         psi = sim.read()
         assert np.array_equal(_bits(psi), _bits(want))
         sim.apply_modular_add(77, 1000, list(range(3, 13)))
         want = permutation_ref.apply_permutation(psi, permutations.modular_add_table(77, 1000, 10), list(range(3, 13)))
-        assert np.array_equal(_bits(sim.read()), _bits(want)) and _sweeps() == count + 2
+        assert np.array_equal(_bits(sim.read()), _bits(want)) and plans.sweeps_launched("permutation") == count + 2
 
 
 def test_cluster_has_no_permutation_methods():
@@ -331,15 +316,15 @@ def test_refusals(precision):
     with Simulator(12, precision=precision) as sim:
         sim.write(rand_state(12, 2))
         state = _bits(sim.read()).copy()
-        before = _sweeps()
+        before = plans.sweeps_launched("permutation")
         call = lambda ts, cs=(), k=None, c=None, perm=None: lib.qsim_apply_permutation(
             sim._h, (ident[min(len(ts), 11)] if perm is None else perm).ctypes.data_as(UP), _ints(ts), len(ts) if k is None else k, _ints(cs),
             len(cs) if c is None else c)
         assert call([0, 1]) == _lib.QSIM_OK and call([0, 1], [5]) == _lib.QSIM_OK and call([], [2]) == _lib.QSIM_OK
         assert lib.qsim_apply_permutation(sim._h, ident[0].ctypes.data_as(UP), None, 0, None, 0) == _lib.QSIM_OK   # k = 0 needs no list
-        assert _sweeps() == before + 4                           # the identity is swept like any other table
+        assert plans.sweeps_launched("permutation") == before + 4                           # the identity is swept like any other table
         assert np.array_equal(_bits(sim.read()), state)
-        before = _sweeps()
+        before = plans.sweeps_launched("permutation")
         for ts, cs in (([0, 0], []), ([12], []), ([-1], []), ([2, 5, 2], []), (list(range(11)), []), ([0], [0]), ([0, 1], [3, 1]), ([0], [12]),
                        ([0], [-1]), ([0], [2, 2])):
             assert call(ts, cs) == _lib.ERR_ARG, (ts, cs)
@@ -357,5 +342,5 @@ def test_refusals(precision):
                     lambda: sim.apply_permutation([0, 1.5], [0])):
             with pytest.raises(ValueError):
                 bad()
-        assert _sweeps() == before
+        assert plans.sweeps_launched("permutation") == before
         assert np.array_equal(_bits(sim.read()), state)

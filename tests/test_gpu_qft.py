@@ -10,7 +10,6 @@ for single passes and for two, three, four and thirteen passes, n = 16 with twel
 and n = 22 (fp64) / 23 (fp32), where the plan call reports two trips per workgroup at the default grid."""
 import functools
 import itertools
-from ctypes import byref, c_int, c_long, c_uint64
 
 import numpy as np
 import pytest
@@ -18,7 +17,8 @@ import pytest
 import fp32_ref
 import lazy_cases
 import qft_ref
-from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib
+from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from gpu_quantum_simulator_amd._lib import QsimError
 from pauli_rot_ref import rand_state
 from test_gpu_lazy_states import Side
@@ -26,23 +26,6 @@ from test_gpu_lazy_states import Side
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 PRECISIONS = [64, 32]
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _plan(qubits, n, precision, cap=0):
-    passes, tiles, units, trips = c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    digits, oop, masks = (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-    rc = _lib.load().qsim_apply_qft_plan(_ints(qubits), len(qubits), n, precision, cap, byref(passes), digits, oop, masks, byref(tiles), byref(units),
-                                         byref(trips))
-    assert rc == _lib.QSIM_OK
-    return dict(passes=passes.value, digits=list(digits[:passes.value]), oop=list(oop[:passes.value]), tiles=tiles.value, trips=trips.value)
-
-
-def _sweeps():
-    return _lib.load().qsim_qft_sweeps_launched()
 
 
 def _bits(state):
@@ -62,10 +45,10 @@ def _compare(got, before, qubits, inverse, precision, label):
 
 def _apply_and_check(sim, before, qubits, inverse=False, cap=0):
     """One call on the device against the checker on `before` (the state as read back); returns the state after it."""
-    passes = _plan(qubits, sim.num_qubits, sim.precision, cap)["passes"]
-    count = _sweeps()
+    passes = plans.ok(plans.apply_qft_plan(qubits, sim.num_qubits, sim.precision, cap))["passes"]
+    count = plans.sweeps_launched("qft")
     sim.apply_qft(qubits, inverse=inverse, max_digit_bits=cap)
-    assert _sweeps() == count + passes
+    assert plans.sweeps_launched("qft") == count + passes
     got = sim.read()
     _compare(got, before, qubits, inverse, sim.precision, f"n={sim.num_qubits} p{sim.precision} k={len(qubits)} cap={cap} inv={int(inverse)} passes={passes}")
     return got
@@ -99,7 +82,7 @@ def test_tile_boundaries(offset, precision):
     with sim:
         for case_n, qubits, cap in qft_ref.boundary_cases(precision):
             if case_n == n:
-                assert _plan(qubits, n, precision)["tiles"] == (2 if offset > 0 else 1)
+                assert plans.ok(plans.apply_qft_plan(qubits, n, precision, 0))["tiles"] == (2 if offset > 0 else 1)
                 psi = _apply_and_check(sim, psi, qubits, inverse=bool(len(qubits) & 1), cap=cap)
 
 
@@ -109,8 +92,8 @@ def test_single_pass_places_and_the_way_back(precision):
     sim, start = _sim_with(13, precision, 1020)
     with sim:
         for n, qubits, cap in qft_ref.single_pass_cases():
-            plan = _plan(qubits, n, precision, cap)
-            assert plan["passes"] == 1 and plan["oop"] == [0]
+            plan = plans.ok(plans.apply_qft_plan(qubits, n, precision, cap))
+            assert plan["passes"] == 1 and plan["out_of_place"] == [0]
             there = _apply_and_check(sim, start, qubits)
             back = _apply_and_check(sim, there, qubits, inverse=True)
             if precision == 64:
@@ -130,8 +113,8 @@ def test_several_passes(precision):
             if n not in sims:
                 sims[n] = _sim_with(n, precision, 1030 + n)
             sim, psi = sims[n]
-            plan = _plan(qubits, n, precision, cap)
-            assert plan["passes"] == passes and sum(plan["oop"]) % 2 == 0 and sum(plan["oop"]) >= passes - 1
+            plan = plans.ok(plans.apply_qft_plan(qubits, n, precision, cap))
+            assert plan["passes"] == passes and sum(plan["out_of_place"]) % 2 == 0 and sum(plan["out_of_place"]) >= passes - 1
             for inverse in (False, True):
                 psi = _apply_and_check(sim, psi, qubits, inverse, cap)
             sims[n] = (sim, psi)
@@ -145,7 +128,7 @@ def test_several_passes(precision):
 def test_equal_bits_whatever_the_grid(precision):
     for n, qubits, cap in qft_ref.grid_cases():
         start = rand_state(n, 1040 + n)
-        assert _plan(qubits, n, precision, cap)["passes"] == (1 if cap == 0 else 3)
+        assert plans.ok(plans.apply_qft_plan(qubits, n, precision, cap))["passes"] == (1 if cap == 0 else 3)
         with Simulator(n, precision=precision) as sim:
             sim.write(start)
             first = _bits(_apply_and_check(sim, sim.read(), qubits, cap=cap)).copy()
@@ -166,7 +149,7 @@ def _large_state(n):
 @pytest.mark.parametrize("which", [0, 1])
 def test_looping_at_the_default_grid(which, precision):
     n, qubits, cap = qft_ref.looping_cases(precision)[which]
-    assert _plan(qubits, n, precision, cap)["trips"] >= 2
+    assert plans.ok(plans.apply_qft_plan(qubits, n, precision, cap))["trips_per_workgroup"] >= 2
     with Simulator(n, precision=precision) as sim:
         sim.write(_large_state(n))
         _apply_and_check(sim, sim.read(), qubits, inverse=bool(which), cap=cap)
@@ -182,7 +165,7 @@ def test_the_state_stays_in_its_buffer(precision):
     n, qubits, cap = MOVING
     real = torch.float32 if precision == 32 else torch.float64
     view = np.complex64 if precision == 32 else np.complex128
-    assert _plan(qubits, n, precision, cap)["oop"] == [1, 1, 0]
+    assert plans.ok(plans.apply_qft_plan(qubits, n, precision, cap))["out_of_place"] == [1, 1, 0]
     sim, psi = _sim_with(n, precision, 1060)
     with sim:
         at = sim.device_ptr
@@ -230,9 +213,9 @@ def test_lazy_starts_over_poisoned_memory(case, start, precision):
     for lazy in (True, False):
         with Side(precision, lazy) as side:
             sim = side.state(start)
-            count = _sweeps()
+            count = plans.sweeps_launched("qft")
             sim.apply_qft(qubits, max_digit_bits=cap)
-            assert _sweeps() == count + _plan(qubits, lazy_cases.N, precision, cap)["passes"]
+            assert plans.sweeps_launched("qft") == count + plans.ok(plans.apply_qft_plan(qubits, lazy_cases.N, precision, cap))["passes"]
             results.append(sim.read())
     lazy_got, twin_got = results
     assert not np.isnan(lazy_got).any()
@@ -262,9 +245,9 @@ def test_queued_gates_land_first(precision):
     assert np.count_nonzero(before) == 16
     with Simulator(n, precision=precision) as sim:
         sim.run(circuit)                                         # queued, not flushed
-        count = _sweeps()
+        count = plans.sweeps_launched("qft")
         sim.apply_qft(qubits)
-        assert _sweeps() == count + 2
+        assert plans.sweeps_launched("qft") == count + 2
         _compare(sim.read(), before, qubits, False, precision, f"queued gates p{precision}")
 
 
@@ -308,10 +291,10 @@ def test_refusals(precision):
     with Simulator(12, precision=precision) as sim:
         sim.write(rand_state(12, 3))
         state = _bits(sim.read()).copy()
-        before = _sweeps()
+        before = plans.sweeps_launched("qft")
         sim.apply_qft([])                                        # k = 0 is accepted and does nothing
         assert lib.qsim_apply_qft(sim._h, None, 0, 0, 0) == _lib.QSIM_OK
-        assert _sweeps() == before and np.array_equal(_bits(sim.read()), state)
+        assert plans.sweeps_launched("qft") == before and np.array_equal(_bits(sim.read()), state)
         for bad in (lambda: sim.apply_qft([0, 0]), lambda: sim.apply_qft([2, 5, 2]), lambda: sim.apply_qft([12]), lambda: sim.apply_qft([-1]),
                     lambda: sim.apply_qft(list(range(12)) + [3]), lambda: sim.apply_qft([0, 1], max_digit_bits=11),
                     lambda: sim.apply_qft([0, 1], max_digit_bits=-1), lambda: sim.apply_qft([0, 1], inverse=True, max_digit_bits=12)):
@@ -320,8 +303,8 @@ def test_refusals(precision):
             assert err.value.code == _lib.ERR_ARG
         assert lib.qsim_apply_qft(sim._h, None, 1, 0, 0) == _lib.ERR_ARG and lib.qsim_apply_qft(sim._h, _ints([0]), -1, 0, 0) == _lib.ERR_ARG
         assert lib.qsim_apply_qft(sim._h, _ints(list(range(13))), 13, 0, 0) == _lib.ERR_ARG and lib.qsim_apply_qft(None, _ints([0]), 1, 0, 0) == _lib.ERR_ARG
-        assert _sweeps() == before
+        assert plans.sweeps_launched("qft") == before
         assert np.array_equal(_bits(sim.read()), state)
         sim.reset(holds_index0=False)                            # a state that holds nothing: accepted, no sweep
         sim.apply_qft(list(range(12)))
-        assert _sweeps() == before and lib.qsim_holds_nothing(sim._h) == 1
+        assert plans.sweeps_launched("qft") == before and lib.qsim_holds_nothing(sim._h) == 1

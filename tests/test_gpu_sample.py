@@ -5,16 +5,15 @@ is the exact widened contents, so the rounding of a write cancels.  It does not 
 must be ADMISSIBLE (p_i > 0 and E_(i-1) - gamma < r <= E_i + gamma, gamma = 2^(n-52) E_last, the any-order bound), a DETERMINED draw
 (farther than gamma from both edges of its interval) must return exactly searchsorted(E, r), and at least 99 % of the draws of every
 test must be determined.  One test has no tolerance at all: 64 amplitudes of exactly 1/8, every partial sum exact in any order.
-Sizes come from qsim_sample_geometry (cb: bits of a chunk, gb: bits of a group): registers below, at and above one chunk (the plain
+Sizes come from plans.sample_geometry (cb: bits of a chunk, gb: bits of a group): registers below, at and above one chunk (the plain
 path, exactly one chunk, several chunks of one group), several groups with empty ones among them, and shot counts around the four
 waves of a workgroup."""
-from ctypes import byref, c_int, c_uint64
 
 import numpy as np
 import pytest
 
 import sample_ref
-from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits
+from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits, plans
 from pauli_rot_ref import rand_state
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +22,8 @@ EDGES = [0.0, 1e-300, 1.0]
 
 
 def _geometry(n):
-    cb, gb, sb = c_int(), c_int(), c_uint64()
-    _lib.check(_lib.load().qsim_sample_geometry(n, byref(cb), byref(gb), byref(sb)))
-    return cb.value, gb.value
+    g = plans.ok(plans.sample_geometry(n))
+    return g["chunk_bits"], g["group_bits"]
 
 
 CB, GB = _geometry(30)

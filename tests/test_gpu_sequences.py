@@ -58,7 +58,7 @@ import measure_ref
 import pauli_ref
 import pauli_rot_ref
 import sequence_ref as S
-from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib
+from gpu_quantum_simulator_amd import Diagonal, Simulator, _lib, plans
 
 pytestmark = pytest.mark.gpu
 N = 14
@@ -472,22 +472,12 @@ def _sides(n, precision, family, **kw):
 
 def _path(kind, op, n, precision):
     """The *path the plan call of a matrix or permutation step reports (host only)."""
-    from ctypes import byref, c_int, c_long, c_uint64
-    lib = _lib.load()
-    ints = lambda qs: (c_int * max(len(qs), 1))(*qs)
-    path, i0, l0, u0, u1, u2 = c_int(-1), c_int(), c_long(), c_uint64(), c_uint64(), c_uint64()
-    t, c = op["targets"], op["controls"]
-    if kind.startswith("matrix"):
-        rc = lib.qsim_apply_matrix_plan(ints(t), len(t), ints(c), len(c), n, precision, byref(path), byref(i0), byref(u0), byref(u1), byref(l0))
-    else:
-        rc = lib.qsim_apply_permutation_plan(ints(t), len(t), ints(c), len(c), n, precision, byref(path), byref(i0), byref(u0), byref(u1), byref(u2), byref(l0))
-    assert rc == _lib.QSIM_OK
-    return path.value
+    probe = plans.apply_matrix_plan if kind.startswith("matrix") else plans.apply_permutation_plan
+    return plans.ok(probe(op["targets"], op["controls"], n, precision))["path"]
 
 
 def _uploads():
-    lib = _lib.load()
-    return lib.qsim_matrix_sweeps_launched() + lib.qsim_permutation_sweeps_launched() + lib.qsim_qft_sweeps_launched()
+    return plans.sweeps_launched("matrix") + plans.sweeps_launched("permutation") + plans.sweeps_launched("qft")
 
 
 # ---- a. every ordered pair ------------------------------------------------------------------------------------------------------------

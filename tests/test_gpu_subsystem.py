@@ -9,13 +9,14 @@ pairing mistake shows at 1e-2.  Every comparison also asks for exact Hermiticity
 norm2().  Sizes are the smallest at which each mechanism exists, taken from the plan call: both sides of the switch from the plain
 kernel to blocks, one block against several (n = 13), and the smallest registers with two slices and two trips per workgroup."""
 import ctypes
-from ctypes import byref, c_int, c_long, c_uint64
+from ctypes import c_int
 
 import numpy as np
 import pytest
 
 import density_ref
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from gpu_quantum_simulator_amd._lib import QsimError
 from helpers import random_unitary
 from pauli_rot_ref import rand_state
@@ -24,15 +25,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-10
 PRECISIONS = [64, 32]
 H = np.array([[1, 1], [1, -1]]) / np.sqrt(2.0)
-
-
-def _plan(qubits, n, precision):
-    arr = (c_int * max(len(qubits), 1))(*qubits)
-    path, rows, upper, slices, units, scratch, trips = c_int(-1), c_int(-1), c_long(-1), c_long(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_subsystem_density_plan(arr, len(qubits), n, precision, byref(path), byref(rows), byref(upper), byref(slices), byref(units),
-                                                 byref(scratch), byref(trips))
-    assert rc == _lib.QSIM_OK
-    return dict(path=path.value, block_rows=rows.value, upper_blocks=upper.value, slices=slices.value, trips=trips.value)
 
 
 def _check(sim, psi, qubits, label=""):
@@ -64,13 +56,13 @@ def _shuffled(qs, seed):
 @pytest.mark.parametrize("k", [6, 10])
 def test_path_switch(k, precision):
     """n = k and k + 1 take the plain kernel; the next register is the smallest for blocks: four environments, one matrix step."""
-    first = next(n for n in range(k, k + 8) if _plan(list(range(k)), n, precision)["path"] == 1)
+    first = next(n for n in range(k, k + 8) if plans.ok(plans.subsystem_density_plan(list(range(k)), n, precision))["path"] == 1)
     assert first - k == 2
     for n in range(k, first + 1):
         sim, psi = _sim_with(n, precision, 520 + n)
         with sim:
             for qs in {tuple(range(k)), tuple(range(n - k, n)), tuple(range(n - 1, n - 1 - k, -1))}:
-                assert _plan(list(qs), n, precision)["path"] == (1 if n == first else 0)
+                assert plans.ok(plans.subsystem_density_plan(list(qs), n, precision))["path"] == (1 if n == first else 0)
                 _check(sim, psi, list(qs), "switch")
 
 
@@ -79,7 +71,7 @@ def test_one_block_against_several(precision):
     """n = 13: the largest subset whose G is one block and the smallest with off-diagonal blocks, on the lowest and the highest
     qubits and on spread subsets with qubit 0 (fp32: the slot is a row bit) and without (an environment bit); k = 10 too."""
     n = 13
-    upper = {k: _plan(list(range(k)), n, precision)["upper_blocks"] for k in range(6, 11)}
+    upper = {k: plans.ok(plans.subsystem_density_plan(list(range(k)), n, precision))["upper_blocks"] for k in range(6, 11)}
     one, several = max(k for k in upper if upper[k] == 1), min(k for k in upper if upper[k] > 1)
     assert several == one + 1
     sim, psi = _sim_with(n, precision, 513)
@@ -90,7 +82,7 @@ def test_one_block_against_several(precision):
             for qs in (list(range(k)), list(range(n - k, n)), spread0, spread1):
                 assert len(set(qs)) == k
                 for order in (qs, _shuffled(qs, 7 * k + qs[1])):
-                    p = _plan(order, n, precision)
+                    p = plans.ok(plans.subsystem_density_plan(order, n, precision))
                     assert p["path"] == 1 and p["upper_blocks"] == upper[k]
                     _check(sim, psi, order, "blocks")
         _check(sim, psi, [12, 0, 3, 4, 5, 11, 7, 8, 9, 1], "blocks")
@@ -103,8 +95,8 @@ def _looping_size(k, precision, high):
     """The smallest register at which the plan reports two slices or more and two trips or more per workgroup."""
     for n in range(k + 2, 24):
         qs = list(range(n - k, n)) if high else list(range(k))
-        p = _plan(qs, n, precision)
-        if p["slices"] >= 2 and p["trips"] >= 2:
+        p = plans.ok(plans.subsystem_density_plan(qs, n, precision))
+        if p["slices"] >= 2 and p["trips_per_workgroup"] >= 2:
             return n, qs
     raise AssertionError("no register up to 23 qubits loops")
 
@@ -190,17 +182,16 @@ def test_product_state_and_the_complement_route(precision):
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_a_shard_that_holds_nothing(precision):
-    lib = _lib.load()
     with Simulator(13, precision=precision) as sim:
         sim.reset(holds_index0=False)
-        before = lib.qsim_subsystem_sweeps_launched()
+        before = plans.sweeps_launched("subsystem")
         for qs in ([0, 1, 2, 3, 4, 5], list(range(3, 13))):
             assert np.array_equal(sim.subsystem_density_matrix(qs), np.zeros((1 << len(qs), 1 << len(qs))))
-        assert lib.qsim_subsystem_sweeps_launched() == before
+        assert plans.sweeps_launched("subsystem") == before
         sim.reset()
         got = sim.subsystem_density_matrix([12, 3, 4, 0, 1, 2])   # never touched: |0...0> is still held lazily
         assert got[0, 0] == 1.0 and np.count_nonzero(got) == 1
-        assert lib.qsim_subsystem_sweeps_launched() == before + 1
+        assert plans.sweeps_launched("subsystem") == before + 1
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
@@ -210,12 +201,12 @@ def test_errors(precision):
     with Simulator(7, precision=precision) as sim:
         sim.write(rand_state(7, 1))
         state = sim.read().view(np.uint64).copy()
-        before, density_before = lib.qsim_subsystem_sweeps_launched(), lib.qsim_density_sweeps_launched()
-        call = lambda qs, k=None: lib.qsim_subsystem_density(sim._h, (c_int * max(len(qs), 1))(*qs), len(qs) if k is None else k, out)
+        before, density_before = plans.sweeps_launched("subsystem"), plans.sweeps_launched("density")
+        call = lambda qs, k=None: lib.qsim_subsystem_density(sim._h, _ints(qs), len(qs) if k is None else k, out)
         assert call([0, 1, 2, 3, 4, 5]) == _lib.QSIM_OK
-        assert lib.qsim_subsystem_sweeps_launched() == before + 1
+        assert plans.sweeps_launched("subsystem") == before + 1
         assert call([0, 1]) == _lib.QSIM_OK                      # forwarded: the one-wave call's sweep
-        assert lib.qsim_subsystem_sweeps_launched() == before + 1 and lib.qsim_density_sweeps_launched() == density_before + 1
+        assert plans.sweeps_launched("subsystem") == before + 1 and plans.sweeps_launched("density") == density_before + 1
         for qs in ([0, 0], [7], [-1], [2, 5, 2], [0, 1, 2, 3, 4, 5, 5], [0, 1, 2, 3, 4, 5, 6, 7]):
             assert call(qs) == _lib.ERR_ARG
         assert call([0], -1) == _lib.ERR_ARG
@@ -223,15 +214,15 @@ def test_errors(precision):
         assert lib.qsim_subsystem_density(sim._h, None, 0, out) == _lib.QSIM_OK
         assert lib.qsim_subsystem_density(sim._h, (c_int * 1)(0), 1, None) == _lib.ERR_ARG
         assert lib.qsim_subsystem_density(None, (c_int * 1)(0), 1, out) == _lib.ERR_ARG
-        assert lib.qsim_subsystem_sweeps_launched() == before + 1  # nothing was launched for a refused call
+        assert plans.sweeps_launched("subsystem") == before + 1  # nothing was launched for a refused call
         assert np.array_equal(sim.read().view(np.uint64), state)   # nor did a successful one touch the state
     with Simulator(12, precision=precision) as sim:
-        before = lib.qsim_subsystem_sweeps_launched()
+        before = plans.sweeps_launched("subsystem")
         assert lib.qsim_subsystem_density(sim._h, (c_int * 11)(*range(11)), 11, out) == _lib.ERR_ARG
         with pytest.raises(QsimError):
             sim.subsystem_density_matrix(list(range(11)))
         with pytest.raises(QsimError):
             sim.entanglement_entropy(list(range(11)) + [3])       # a repeated qubit takes no complement
-        assert lib.qsim_subsystem_sweeps_launched() == before
+        assert plans.sweeps_launched("subsystem") == before
         with pytest.raises(QsimError):
             sim.reduced_density_matrix([0, 1, 2, 3, 4, 5])        # the one-wave entry keeps its limit

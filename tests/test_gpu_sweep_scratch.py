@@ -8,7 +8,6 @@ tests/test_gpu_matrix.py say why that holds for a sweep of 2^10 amplitudes); a s
 1e-2 or above.  Every case runs in a child process of its own under `timeout -k 10 60`, which saves what the device returned; the
 assertions are made here, and after a case that failed no further one is started.
 """
-import ctypes
 import functools
 import os
 import subprocess
@@ -131,16 +130,10 @@ def _check_inner(got, tag):
 
 def test_the_calls_are_what_they_are_meant_to_be():
     """Host only: 130 sweeps for the strings, and the matrix call takes the matrix path on five kernel qubits."""
-    from gpu_quantum_simulator_amd import _lib
-    lib = _lib.load()
-    xs = np.array([x for x, _ in _masks()], dtype=np.uint64)
-    sweeps = ctypes.c_long()
-    assert lib.qsim_pauli_sweeps(xs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), xs.size, ctypes.byref(sweeps)) == 0
-    assert sweeps.value == STRINGS > 128
-    path, padded_k, mask, units, trips = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_long()
-    assert lib.qsim_apply_matrix_plan((ctypes.c_int * 5)(*TARGETS), 5, (ctypes.c_int * 1)(*CONTROLS), 1, N, 64, ctypes.byref(path),
-                                      ctypes.byref(padded_k), ctypes.byref(mask), ctypes.byref(units), ctypes.byref(trips)) == 0
-    assert (path.value, padded_k.value) == (1, 5)
+    from gpu_quantum_simulator_amd import plans
+    assert plans.ok(plans.pauli_sweeps([x for x, _ in _masks()]))["sweeps"] == STRINGS > 128
+    plan = plans.ok(plans.apply_matrix_plan(TARGETS, CONTROLS, N, 64))
+    assert (plan["path"], plan["padded_k"]) == (1, 5)
 
 
 def test_expectation_first(run_case):

@@ -1,5 +1,5 @@
 """Host side of the Lanczos ground-state solver, no GPU: the tridiagonal eigensolver qsim_tridiag_lowest against numpy.linalg.eigh,
-the host-only plan qsim_lanczos_plan against sweep counts worked out by hand, and the numpy checker tests/lanczos_ref.py pinned
+the host-only plan plans.lanczos_plan against sweep counts worked out by hand, and the numpy checker tests/lanczos_ref.py pinned
 against dense operators.
 
 Bounds.  With |T| := max|alpha| + 2 max|beta| (a Gershgorin bound on the spectrum) LAPACK's own accuracy is a few eps |T|; the
@@ -13,7 +13,7 @@ import pytest
 
 import adjoint_ref
 import lanczos_ref as ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
 
 DP = ctypes.POINTER(ctypes.c_double)
 UP = ctypes.POINTER(ctypes.c_uint64)
@@ -73,17 +73,15 @@ def test_tridiag_lowest_refuses_bad_arguments():
 
 
 def _plan(terms, max_steps=10, vector=1):
-    hx = np.array([x for _, x, _ in terms], dtype=np.uint64)
-    a, b, v = ctypes.c_long(-1), ctypes.c_long(-1), ctypes.c_double(-1.0)
-    rc = _lib.load().qsim_lanczos_plan(hx.ctypes.data_as(UP) if hx.size else None, hx.size, max_steps, vector, ctypes.byref(a), ctypes.byref(b), ctypes.byref(v))
-    return rc, a.value, b.value, v.value
+    rc, p = plans.lanczos_plan([x for _, x, _ in terms] or None, max_steps, vector)
+    return rc, p["sum_sweeps_per_step"], p["other_sweeps_per_step"], p["volumes_per_step"]
 
 
 @pytest.mark.parametrize("n", [2, 10, 30])
 def test_plan_ising_chain(n):
     """2n - 1 terms: the ZZ terms share x = 0 (one sweep), every X_q is an x group of its own: G = 1 + n sweeps; the first stores (2
     volumes), the others accumulate (3), alpha reads two vectors, the update reads three and writes one."""
-    assert _lib.load().qsim_pauli_terms_per_sweep() >= 29  # the ZZ group of n = 30 fits one sweep
+    assert plans.pauli_terms_per_sweep() >= 29  # the ZZ group of n = 30 fits one sweep
     rc, sums, others, volumes = _plan(ref.ising(n))
     assert (rc, sums, others) == (0, 1 + n, 2)
     assert volumes == 3 * (1 + n) - 1 + 2 + 4
@@ -96,7 +94,7 @@ def test_plan_all_z_and_empty():
     assert _plan(ref.zz_chain(5), max_steps=0)[0] == _lib.ERR_ARG
     lib = _lib.load()
     hx = np.zeros(2, dtype=np.uint64)
-    assert lib.qsim_lanczos_plan(hx.ctypes.data_as(UP), 2, 5, 0, None, None, None) == _lib.ERR_ARG
+    assert lib.qsim_lanczos_plan(hx.ctypes.data_as(UP), 2, 5, 0, None, None, None) == _lib.ERR_ARG  # raw: NULL for the out-parameters
 
 
 def test_checker_against_dense_operators():

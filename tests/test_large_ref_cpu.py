@@ -7,7 +7,6 @@
    index); at least one checked quantity must move by 100 tolerances — of the fp64 bound 1e-10 AND of the largest bound an fp32 run
    can be given, 8 * 1e-5 (fp32_ref.C * REF_CAP).  For the exact sampling cases the returned index must differ.
 3. The host geometry of the calls at n = 33 ... 40 from the plan probes: nothing wrapped."""
-from ctypes import byref, c_int, c_long, c_ubyte, c_uint64
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ import fp32_ref
 import large_ref as lr
 import qft_ref
 import sample_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import plans
 from helpers import np_apply_1q, np_apply_2q
 
 N_PIN = 16
@@ -241,15 +240,6 @@ def test_reach_of_the_exact_sampling_cases():
 # ---- host geometry at n = 33 ... 40: every plan probe, no device ----------------------------------------------------------------------
 SIZES = range(33, 41)
 PRECISIONS = [64, 32]
-U64 = c_uint64 * 1
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _masks(values):
-    return (c_uint64 * max(len(values), 1))(*values)
 
 
 def _state_units(n, precision):
@@ -272,110 +262,89 @@ def _subsets(n):
 
 
 def test_pauli_plans_take_masks_above_bit_31():
-    lib = _lib.load()
     for n in SIZES:
         top, below = 1 << (n - 1), 1 << (n - 2)
         xs = [top | 1, top | 1, top | 1, below | 2, 0, top]
         zs = [0, top, below, top, top | 1, top]
-        sweeps, queued = c_long(-1), c_long(-1)
-        assert lib.qsim_pauli_rotation_plan(_masks(xs), _masks(zs), len(xs), byref(sweeps), byref(queued)) == _lib.QSIM_OK
+        p = plans.ok(plans.pauli_rotation_plan(xs, zs))
         # three strings share x (one sweep), the fourth has another, x = 0 is a sweep of its own kind, the last is a single-qubit Y: a gate
-        assert sweeps.value == 3 and queued.value == 1, (n, sweeps.value, queued.value)
+        assert p["sweeps"] == 3 and p["queued_as_gates"] == 1, (n, p)
         # x strings that differ ONLY above bit 31 do not share a sweep: the plan compares 64-bit masks
-        s2, q2 = c_long(-1), c_long(-1)
-        assert lib.qsim_pauli_rotation_plan(_masks([top | 1, (top >> 1) | 1, top | 1]), _masks([2, 2, 2]), 3, byref(s2), byref(q2)) == _lib.QSIM_OK
-        assert (s2.value, q2.value) == (3, 0)
-        adj, sums = c_long(-1), c_long(-1)
-        assert lib.qsim_pauli_gradient_plan(_masks(xs), len(xs), _masks(xs[:4]), 4, byref(adj), byref(sums)) == _lib.QSIM_OK
-        assert adj.value > 0 and sums.value == 2   # H's strings: two distinct x
+        assert plans.ok(plans.pauli_rotation_plan([top | 1, (top >> 1) | 1, top | 1], [2, 2, 2])) == dict(sweeps=3, queued_as_gates=0)
+        g = plans.ok(plans.pauli_gradient_plan(xs, xs[:4]))
+        assert g["adjoint_sweeps"] > 0 and g["sum_sweeps"] == 2   # H's strings: two distinct x
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_controlled_plans_visit_the_control_subspace(precision):
-    lib = _lib.load()
     seen = []
     for n in SIZES:
         top = 1 << (n - 1)
         for cs, xs, zs, share in (([top], [1 | 4], [2], 2), ([top | (top >> 1)], [8], [0], 4), ([2], [top | 4], [top >> 1], 2)):
-            sweeps, queued, units = c_long(-1), c_long(-1), c_uint64(0)
-            assert lib.qsim_controlled_rotation_plan(_masks(cs), _masks(xs), _masks(zs), 1, n, precision, byref(sweeps), byref(queued), byref(units)) == _lib.QSIM_OK
-            assert sweeps.value + queued.value == 1
+            p = plans.ok(plans.controlled_rotation_plan(cs, xs, zs, n, precision))
+            assert p["sweeps"] + p["queued_as_gates"] == 1
             # every control bit 1 and the highest bit of x clear (tests/test_controlled_rot_cpu.py enumerates it at n = 10)
-            assert sweeps.value == 1 and units.value == _state_units(n, precision) // (2 * share), (n, cs, units.value)
-            adj, sums, visited = c_long(-1), c_long(-1), c_uint64(0)
-            assert lib.qsim_controlled_gradient_plan(_masks(cs), _masks(xs), 1, _masks([top | 1]), 1, n, precision, byref(adj), byref(sums), byref(visited)) == _lib.QSIM_OK
-            assert adj.value == 1 and sums.value == 1 and visited.value == _state_units(n, precision) // (2 * share)
-        seen.append(units.value)
+            assert p["sweeps"] == 1 and p["units_visited"] == _state_units(n, precision) // (2 * share), (n, cs, p["units_visited"])
+            g = plans.ok(plans.controlled_gradient_plan(cs, xs, [top | 1], n, precision))
+            assert g["adjoint_sweeps"] == 1 and g["sum_sweeps"] == 1 and g["units_visited"] == _state_units(n, precision) // (2 * share)
+        seen.append(p["units_visited"])
     _doubles(seen, "controlled rotation units")
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_density_plans_read_the_whole_state(precision):
-    lib = _lib.load()
     trips, reads = [], []
     for n in SIZES:
         for qubits in _subsets(n):
-            path, padded, mask, units, t = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-            assert lib.qsim_reduced_density_plan(_ints(qubits), len(qubits), n, precision, byref(path), byref(padded), byref(mask), byref(units), byref(t)) == _lib.QSIM_OK
-            assert units.value == _state_units(n, precision) and t.value > 0
-            want = sum(1 << q for q in qubits)
-            assert mask.value & want == want and mask.value >> n == 0 and bin(mask.value).count("1") == padded.value
-        trips.append(t.value)
+            p = plans.ok(plans.reduced_density_plan(qubits, n, precision))
+            assert p["units_visited"] == _state_units(n, precision) and p["trips_per_workgroup_at_grid_cap"] > 0
+            want, mask = sum(1 << q for q in qubits), p["kernel_mask"]
+            assert mask & want == want and mask >> n == 0 and bin(mask).count("1") == p["padded_k"]
+        trips.append(p["trips_per_workgroup_at_grid_cap"])
         for qubits in ([0, 1, 2, 3, n - 2, n - 1], [1, 2, 3, 4, 5, 6, 7, 8, 9, n - 1], list(range(n - 10, n))):
-            path, rows, blocks, slices = c_int(-1), c_int(-1), c_long(-1), c_long(-1)
-            read, scratch, t = c_uint64(0), c_uint64(0), c_long(-1)
-            assert lib.qsim_subsystem_density_plan(_ints(qubits), len(qubits), n, precision, byref(path), byref(rows), byref(blocks), byref(slices),
-                                                   byref(read), byref(scratch), byref(t)) == _lib.QSIM_OK
-            assert path.value == 1 and rows.value == 128 and blocks.value > 0 and slices.value > 0 and t.value > 0 and scratch.value > 0
-            assert len(qubits) < 10 or (slices.value > 1 and blocks.value > 1)                                        # k = 10: several slices
-            assert read.value % _state_units(n, precision) == 0 and read.value // _state_units(n, precision) >= 1   # whole state volumes
-        reads.append(read.value)
+            p = plans.ok(plans.subsystem_density_plan(qubits, n, precision))
+            assert p["path"] == 1 and p["block_rows"] == 128 and p["upper_blocks"] > 0 and p["slices"] > 0 and p["trips_per_workgroup"] > 0 and p["scratch_bytes"] > 0
+            assert len(qubits) < 10 or (p["slices"] > 1 and p["upper_blocks"] > 1)                                    # k = 10: several slices
+            read = p["units_read"]
+            assert read % _state_units(n, precision) == 0 and read // _state_units(n, precision) >= 1               # whole state volumes
+        reads.append(read)
     _doubles(trips, "reduced density trips")
     _doubles(reads, "subsystem density units read")
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_matrix_and_permutation_plans_cover_the_control_subspace(precision):
-    lib = _lib.load()
     m_trips, p_trips, p_tiles = [], [], []
     for n in SIZES:
         for targets in _subsets(n):
             for controls in ([], [n - 4], [2, n - 4]):
-                path, padded, mask, units, t = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-                assert lib.qsim_apply_matrix_plan(_ints(targets), len(targets), _ints(controls), len(controls), n, precision, byref(path), byref(padded),
-                                                  byref(mask), byref(units), byref(t)) == _lib.QSIM_OK
-                assert units.value == _state_units(n, precision) >> len(controls), (n, targets, controls)
-                want = sum(1 << q for q in targets)
-                assert mask.value & want == want and mask.value >> n == 0 and not mask.value & sum(1 << q for q in controls)
+                m = plans.ok(plans.apply_matrix_plan(targets, controls, n, precision))
+                assert m["units"] == _state_units(n, precision) >> len(controls), (n, targets, controls)
+                want, mask = sum(1 << q for q in targets), m["kernel_mask"]
+                assert mask & want == want and mask >> n == 0 and not mask & sum(1 << q for q in controls)
                 # the matrix path (16 environments a step and more are left); a workgroup's trips at the grid's cap: 1024 workgroups, 512 for
                 # five qubits, each taking a whole number of units per trip — so the units are a multiple of trips x cap and no field wrapped
                 cap = 512 if len(targets) == 5 else 1024
-                assert path.value == 1 and t.value > 0 and units.value % (t.value * cap) == 0, (n, targets, controls, t.value)
+                t = m["trips_per_workgroup"]
+                assert m["path"] == 1 and t > 0 and m["units"] % (t * cap) == 0, (n, targets, controls, t)
                 if not controls and len(targets) == 3:
-                    m_trips.append(t.value)
-                path, bits, tmask, tiles, units, t = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_uint64(0), c_long(-1)
-                assert lib.qsim_apply_permutation_plan(_ints(targets), len(targets), _ints(controls), len(controls), n, precision, byref(path), byref(bits),
-                                                       byref(tmask), byref(tiles), byref(units), byref(t)) == _lib.QSIM_OK
-                b = 12 if precision == 64 else 13
-                assert path.value == 1 and bits.value == b and bin(tmask.value).count("1") == b and tmask.value & want == want and tmask.value >> n == 0
-                assert tiles.value == 1 << (n - len(controls) - b) and units.value == _state_units(n, precision) >> len(controls)
-                assert t.value == _ceil_div(tiles.value, 512)
-        p_trips.append(t.value)
-        p_tiles.append(tiles.value)
+                    m_trips.append(t)
+                p = plans.ok(plans.apply_permutation_plan(targets, controls, n, precision))
+                b, tmask = 12 if precision == 64 else 13, p["tile_mask"]
+                assert p["path"] == 1 and p["tile_bits"] == b and bin(tmask).count("1") == b and tmask & want == want and tmask >> n == 0
+                assert p["tiles"] == 1 << (n - len(controls) - b) and p["units"] == _state_units(n, precision) >> len(controls)
+                assert p["trips_per_workgroup"] == _ceil_div(p["tiles"], 512)
+        p_trips.append(p["trips_per_workgroup"])
+        p_tiles.append(p["tiles"])
         emb = lr.Embedding(33, 1) if n == 33 else None
         if emb is not None:   # the plain kernel: the step of test_matrix_off_the_matrix_path leaves fewer than 16 environments
             (_, tg, cs), _small = lr.plain_matrix_step(emb)
-            path, padded, mask, units, t = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-            assert lib.qsim_apply_matrix_plan(_ints(tg), 2, _ints(cs), len(cs), n, precision, byref(path), byref(padded), byref(mask), byref(units), byref(t)) == _lib.QSIM_OK
-            assert path.value == 0 and units.value == _state_units(n, precision) >> len(cs) and t.value == 1
+            m = plans.ok(plans.apply_matrix_plan(tg, cs, n, precision, k=2))
+            assert m["path"] == 0 and m["units"] == _state_units(n, precision) >> len(cs) and m["trips_per_workgroup"] == 1
             for st in lr.CASES["matrix"][1]:
-                assert lib.qsim_apply_matrix_plan(_ints(emb.qubits(st[2])), len(st[2]), _ints(emb.qubits(st[3])), len(st[3]), n, precision, byref(path),
-                                                  byref(padded), byref(mask), byref(units), byref(t)) == _lib.QSIM_OK
-                assert path.value == 1, st[2:]
+                assert plans.ok(plans.apply_matrix_plan(emb.qubits(st[2]), emb.qubits(st[3]), n, precision, k=len(st[2]), num_controls=len(st[3])))["path"] == 1, st[2:]
         if precision == 32:   # a control on qubit 0: the odd amplitude of twice as many units
-            path, padded, mask, units, t = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-            assert lib.qsim_apply_matrix_plan(_ints([n - 1]), 1, _ints([0]), 1, n, 32, byref(path), byref(padded), byref(mask), byref(units), byref(t)) == _lib.QSIM_OK
-            assert units.value == _state_units(n, 32)
+            assert plans.ok(plans.apply_matrix_plan([n - 1], [0], n, 32))["units"] == _state_units(n, 32)
     _doubles(m_trips, "matrix trips")
     _doubles(p_trips, "permutation trips")
     _doubles(p_tiles, "permutation tiles")
@@ -387,16 +356,14 @@ def test_diagonal_plans_count_the_table(precision):
     trips_p, trips_e, trips_a = [], [], []
     for n in SIZES:
         p = diagonal_ref.plan(n, precision)
-        assert p["items"] == 1 << (n - 1) and p["per_trip_phase"] > 0 and p["per_trip_expect"] > 0   # 16 bytes of the table: two entries
-        trips_p.append(p["trips_phase"])
-        trips_e.append(p["trips_expect"])
-        flags = (c_ubyte * 3)(0, 1, 0)
+        assert p["items"] == 1 << (n - 1) and p["items_per_trip_phase"] > 0 and p["items_per_trip_expect"] > 0   # 16 bytes of the table: two entries
+        trips_p.append(p["trips_at_cap_phase"])
+        trips_e.append(p["trips_at_cap_expect"])
         top = 1 << (n - 1)
-        pa, da, ss, per, trips = c_long(-1), c_long(-1), c_long(-1), c_int(-1), c_long(-1)
-        assert _lib.load().qsim_diagonal_gradient_plan(flags, _masks([0, 0, top]), _masks([top | 1, 0, 2]), 3, _masks([top, 1]), 2, 1, n, precision,
-                                                       byref(pa), byref(da), byref(ss), byref(per), byref(trips)) == _lib.QSIM_OK
-        assert pa.value == 2 and da.value == 1 and ss.value == 3 and per.value > 0 and trips.value > 0
-        trips_a.append(trips.value)
+        g = plans.ok(plans.diagonal_gradient_plan([0, 1, 0], [0, 0, top], [top | 1, 0, 2], [top, 1], 1, n, precision))
+        assert g["pauli_adjoint_sweeps"] == 2 and g["diag_adjoint_sweeps"] == 1 and g["sum_sweeps"] == 3
+        assert g["diag_adjoint_items_per_trip"] > 0 and g["diag_adjoint_trips_at_cap"] > 0
+        trips_a.append(g["diag_adjoint_trips_at_cap"])
     _doubles(trips_p, "diagonal phase trips")
     _doubles(trips_e, "diagonal expectation trips")
     _doubles(trips_a, "diagonal adjoint trips")
@@ -404,46 +371,38 @@ def test_diagonal_plans_count_the_table(precision):
 
 def test_sample_geometry_is_the_documented_pyramid():
     for n in SIZES:
-        cb, gb, scratch = c_int(-1), c_int(-1), c_uint64(0)
-        assert _lib.load().qsim_sample_geometry(n, byref(cb), byref(gb), byref(scratch)) == _lib.QSIM_OK
-        assert (cb.value, gb.value) == (8, 18) and scratch.value == 8 * ((1 << (n - 8)) + (1 << (n - 18)))
+        assert plans.ok(plans.sample_geometry(n)) == dict(chunk_bits=8, group_bits=18, scratch_bytes=8 * ((1 << (n - 8)) + (1 << (n - 18))))
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_qft_plans_partition_the_register(precision):
-    lib = _lib.load()
     all_trips = []
     for n in SIZES:
         regs = [[n - 1, 0, n - 2, 5], [1, 3, 6, n - 3, n - 2, n - 1, 9, 0, 4, 7], list(range(11)) + [n - 2, n - 1], list(range(n))]
         for reg in regs:
-            passes, digits, oop, tmask = c_int(-1), (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-            tiles, units, trips = c_uint64(0), c_uint64(0), c_long(-1)
-            assert lib.qsim_apply_qft_plan(_ints(reg), len(reg), n, precision, 0, byref(passes), digits, oop, tmask, byref(tiles), byref(units),
-                                           byref(trips)) == _lib.QSIM_OK
-            p = passes.value
+            plan = plans.ok(plans.apply_qft_plan(reg, n, precision, 0))
+            p, digits, oop, tmask = plan["passes"], plan["digit_bits"], plan["out_of_place"], plan["tile_mask"]
             b = min(12 if precision == 64 else 13, n)
-            assert 1 <= p <= 40 and sum(digits[i] for i in range(p)) == len(reg) and all(1 <= digits[i] <= 10 for i in range(p))
-            assert sum(oop[i] for i in range(p)) % 2 == 0 and (len(reg) > 10 or p == 1)
-            assert units.value == _state_units(n, precision) and tiles.value == 1 << (n - b) and trips.value == _ceil_div(tiles.value, 512)
+            assert 1 <= p <= 40 and len(digits) == len(oop) == len(tmask) == p and sum(digits) == len(reg) and all(1 <= d <= 10 for d in digits)
+            assert sum(oop) % 2 == 0 and (len(reg) > 10 or p == 1)
+            assert plan["units"] == _state_units(n, precision) and plan["tiles"] == 1 << (n - b) and plan["trips_per_workgroup"] == _ceil_div(plan["tiles"], 512)
             for i in range(p):   # every sweep works on the register's top digits[i] qubits (the rest has moved up behind the digits done)
                 digit = sum(1 << q for q in reg[len(reg) - digits[i]:])
                 assert bin(tmask[i]).count("1") == b and tmask[i] >> n == 0 and tmask[i] & digit == digit, (n, reg, i, hex(tmask[i]))
-        all_trips.append(trips.value)
+        all_trips.append(plan["trips_per_workgroup"])
     _doubles(all_trips, "qft trips")
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_collapse_plans_count_the_kept_part_and_the_whole_state(precision):
-    lib = _lib.load()
     for n in SIZES:
         for qubits, outcome in (([n - 1], 1), ([0, n - 1], 2), ([n - 3, n - 2, n - 1], 5), ([1, 2, 4, 6, 8, 10, 12, n - 3, n - 2, n - 1], 0b1011001101)):
-            wu, cu, wt, ct = c_uint64(0), c_uint64(0), c_long(-1), c_long(-1)
-            assert lib.qsim_collapse_plan(_ints(qubits), len(qubits), outcome, n, precision, byref(wu), byref(cu), byref(wt), byref(ct)) == _lib.QSIM_OK
+            p = plans.ok(plans.collapse_plan(qubits, outcome, n, precision))
             kept = 1 << (n - len(qubits))
-            assert cu.value == _state_units(n, precision)
-            assert wu.value == (kept if precision == 64 or 0 in qubits else kept // 2), (n, qubits, wu.value)
+            assert p["collapse_units"] == _state_units(n, precision)
+            assert p["weight_units"] == (kept if precision == 64 or 0 in qubits else kept // 2), (n, qubits, p["weight_units"])
             per_trip = 1024 * 256 * 8
-            assert wt.value == _ceil_div(wu.value, per_trip) and ct.value == _ceil_div(cu.value, per_trip)
+            assert p["weight_trips"] == _ceil_div(p["weight_units"], per_trip) and p["collapse_trips"] == _ceil_div(p["collapse_units"], per_trip)
 
 
 def test_helpers_of_the_gpu_test(pin):

@@ -1,6 +1,6 @@
 """Dense matrices on target qubits under controls, checked on the CPU: the checker of tests/test_gpu_matrix.py (matrix_ref.apply_matrix)
-against dense Kronecker operators and the helpers of the 1q / 2q / cx tests, the host-only plan call (qsim_apply_matrix_plan) against
-its rules, and the operand the kernel is handed (qsim_apply_matrix_operand) pushed through a numpy emulation of the matrix
+against dense Kronecker operators and the helpers of the 1q / 2q / cx tests, the host-only plan call (plans.apply_matrix_plan) against
+its rules, and the operand the kernel is handed (plans.apply_matrix_operand) pushed through a numpy emulation of the matrix
 instruction's documented operand and result maps."""
 import itertools
 from ctypes import POINTER, byref, c_double, c_int, c_long, c_uint64
@@ -9,25 +9,14 @@ import numpy as np
 import pytest
 
 import matrix_ref
-from gpu_quantum_simulator_amd import _lib
+from gpu_quantum_simulator_amd import _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from helpers import np_apply_1q, np_apply_2q, np_apply_cx, random_unitary
 from pauli_rot_ref import rand_state
 
-NEW_NAMES = ("qsim_apply_matrix", "qsim_apply_matrix_max_qubits", "qsim_apply_matrix_plan", "qsim_apply_matrix_operand", "qsim_matrix_sweeps_launched")
+NEW_NAMES = ("qsim_apply_matrix", "qsim_apply_matrix_max_qubits", "qsim_apply_matrix_plan", "qsim_apply_matrix_operand", "qsim_matrix_sweeps_launched")  # census of the signature table
 X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 P1 = np.diag([0.0, 1.0]).astype(np.complex128)
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _c_plan(targets, controls, n, bits, k=None, c=None, null_targets=False, null_controls=False):
-    path, padded, mask, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_apply_matrix_plan(None if null_targets else _ints(targets), len(targets) if k is None else k,
-                                            None if null_controls else _ints(controls), len(controls) if c is None else c, n, bits,
-                                            byref(path), byref(padded), byref(mask), byref(units), byref(trips))
-    return rc, dict(path=path.value, padded_k=padded.value, mask=mask.value, units=units.value, trips=trips.value)
 
 
 def _model(targets, controls, n, f32):
@@ -43,13 +32,13 @@ def _model(targets, controls, n, f32):
     if not path:
         subset = sorted(targets)
     units = max(1, (1 << (n - c)) >> (1 if f32 and 0 not in controls else 0))
-    return dict(path=path, padded_k=len(subset), mask=sum(1 << q for q in subset), units=units)
+    return dict(path=path, padded_k=len(subset), kernel_mask=sum(1 << q for q in subset), units=units)
 
 
 def test_signatures_have_the_new_names():
     for name in NEW_NAMES:
         assert name in _lib.SIGNATURES
-    assert _lib.load().qsim_apply_matrix_max_qubits() == 5
+    assert plans.apply_matrix_max_qubits() == 5
 
 
 # ---- the checker ----------------------------------------------------------------------------------------------------------------------
@@ -134,25 +123,25 @@ def test_plan_call_path_padding_and_mask(bits):
                 rest = [q for q in range(n) if q not in ts]
                 for controls in ([], rest[:1], rest[-1:], rest[:2], rest[1:4]):
                     for targets in (list(ts), list(ts)[::-1]):
-                        rc, got = _c_plan(targets, controls, n, bits)
+                        rc, got = plans.apply_matrix_plan(targets, controls, n, bits)
                         want = _model(targets, controls, n, f32)
                         assert rc == _lib.QSIM_OK, (n, targets, controls)
                         assert {key: got[key] for key in want} == want, (n, targets, controls, got, want)
-                        pad = [q for q in range(n) if got["mask"] >> q & 1 and q not in targets]
+                        pad = [q for q in range(n) if got["kernel_mask"] >> q & 1 and q not in targets]
                         free = [q for q in range(n) if q not in targets and q not in controls]
                         assert pad == free[:len(pad)] and len(pad) == got["padded_k"] - k   # the lowest free bits, never a control
-                        assert got["trips"] >= 1
+                        assert got["trips_per_workgroup"] >= 1
 
 
 def test_plan_call_k_from_0_to_5():
     """n = 12, fp64: every k takes the matrix path on a subset of max(k, 3) qubits."""
     for k in range(0, 6):
         targets = list(range(4, 4 + k))
-        rc, got = _c_plan(targets, [], 12, 64)
+        rc, got = plans.apply_matrix_plan(targets, [], 12, 64)
         assert rc == _lib.QSIM_OK and got["path"] == 1 and got["padded_k"] == max(k, 3)
         pad = list(range(0, max(3 - k, 0)))
-        assert got["mask"] == sum(1 << q for q in targets + pad) and got["units"] == 1 << 12
-    assert _c_plan([0, 1], [2, 3], 12, 64)[1]["mask"] == 0b10011  # the padding steps over the controls
+        assert got["kernel_mask"] == sum(1 << q for q in targets + pad) and got["units"] == 1 << 12
+    assert plans.apply_matrix_plan([0, 1], [2, 3], 12, 64)[1]["kernel_mask"] == 0b10011  # the padding steps over the controls
 
 
 @pytest.mark.parametrize("bits", [64, 32])
@@ -160,11 +149,11 @@ def test_plan_call_both_sides_of_the_switch(bits):
     for k in (3, 4, 5):
         for targets, shift in ((list(range(k)), 0), (list(range(1, k + 1)), 1 if bits == 32 else 0)):
             first = k + 4 + shift                                # 16 environment units; fp32 without qubit 0: a unit is two environments
-            assert _c_plan(targets, [], first, bits)[1]["path"] == 1 and _c_plan(targets, [], first - 1, bits)[1]["path"] == 0
+            assert plans.apply_matrix_plan(targets, [], first, bits)[1]["path"] == 1 and plans.apply_matrix_plan(targets, [], first - 1, bits)[1]["path"] == 0
             # every control takes a factor of two of environments away
-            assert _c_plan(targets, [first], first + 1, bits)[1]["path"] == 1 and _c_plan(targets, [first - 1], first, bits)[1]["path"] == 0
-    assert _c_plan([1, 2, 3], [0], 8, 32)[1]["path"] == 1        # fp32, the control on qubit 0: the odd slot of 16 units
-    assert _c_plan([1, 2, 3], [0], 7, 32)[1]["path"] == 0
+            assert plans.apply_matrix_plan(targets, [first], first + 1, bits)[1]["path"] == 1 and plans.apply_matrix_plan(targets, [first - 1], first, bits)[1]["path"] == 0
+    assert plans.apply_matrix_plan([1, 2, 3], [0], 8, 32)[1]["path"] == 1        # fp32, the control on qubit 0: the odd slot of 16 units
+    assert plans.apply_matrix_plan([1, 2, 3], [0], 7, 32)[1]["path"] == 0
 
 
 def test_plan_call_trips_at_the_looping_sizes():
@@ -172,13 +161,13 @@ def test_plan_call_trips_at_the_looping_sizes():
     for bits, n in ((64, 22), (32, 23)):
         for targets in ([0, 1, 2], [n - 4, n - 3, n - 2], [0, 1, 2, 3, 4], [n - 6, n - 5, n - 4, n - 3, n - 2], [n - 2, 3, 9, 7, 1], [n - 2, 3, 9]):
             for controls in ([], [n - 1]):
-                rc, got = _c_plan(targets, controls, n, bits)
-                assert rc == _lib.QSIM_OK and got["path"] == 1 and got["trips"] >= 2, (bits, targets, controls, got)
-    assert _c_plan([0, 1, 2], [], 12, 64)[1]["trips"] == 1
+                rc, got = plans.apply_matrix_plan(targets, controls, n, bits)
+                assert rc == _lib.QSIM_OK and got["path"] == 1 and got["trips_per_workgroup"] >= 2, (bits, targets, controls, got)
+    assert plans.apply_matrix_plan([0, 1, 2], [], 12, 64)[1]["trips_per_workgroup"] == 1
 
 
 def test_plan_call_refusals():
-    ok = lambda *a, **kw: _c_plan(*a, **kw)[0]
+    ok = lambda *a, **kw: plans.apply_matrix_plan(*a, **kw)[0]
     assert ok([0, 1], [2], 6, 64) == _lib.QSIM_OK
     assert ok([0, 0], [], 6, 64) == _lib.ERR_ARG                 # a repeated target
     assert ok([0], [2, 2], 6, 64) == _lib.ERR_ARG                # a repeated control
@@ -187,32 +176,21 @@ def test_plan_call_refusals():
     assert ok([0], [6], 6, 64) == _lib.ERR_ARG and ok([0], [-1], 6, 64) == _lib.ERR_ARG
     assert ok([0, 1, 2, 3, 4, 5], [], 8, 64) == _lib.ERR_ARG     # k > 5
     assert ok([0, 1, 2], [], 2, 64) == _lib.ERR_ARG              # k > n
-    assert ok([0], [], 6, 64, k=-1) == _lib.ERR_ARG and ok([0], [1], 6, 64, c=-1) == _lib.ERR_ARG
-    assert ok([0], [], 6, 64, null_targets=True) == _lib.ERR_ARG and ok([0], [1], 6, 64, null_controls=True) == _lib.ERR_ARG
-    assert ok([], [], 6, 64, null_targets=True, null_controls=True) == _lib.QSIM_OK
+    assert ok([0], [], 6, 64, k=-1) == _lib.ERR_ARG and ok([0], [1], 6, 64, num_controls=-1) == _lib.ERR_ARG
+    assert ok(None, [], 6, 64, k=1) == _lib.ERR_ARG and ok([0], None, 6, 64, num_controls=1) == _lib.ERR_ARG
+    assert ok(None, None, 6, 64) == _lib.QSIM_OK
     assert ok([0], [], -1, 64) == _lib.ERR_ARG and ok([0], [], 41, 64) == _lib.ERR_ARG
     assert ok([0], [], 40, 64) == _lib.QSIM_OK and ok([], [], 0, 32) == _lib.QSIM_OK
     assert ok([0], [], 6, 16) == _lib.ERR_ARG                    # precision_bits
     lib = _lib.load()
     padded, mask, units, trips = c_int(), c_uint64(), c_uint64(), c_long()
-    assert lib.qsim_apply_matrix_plan(_ints([0]), 1, None, 0, 6, 64, None, byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG
+    assert lib.qsim_apply_matrix_plan(_ints([0]), 1, None, 0, 6, 64, None, byref(padded), byref(mask), byref(units), byref(trips)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
     # the call itself refuses a NULL state before it looks at anything else
     u = np.eye(2, dtype=np.complex128).view(np.float64)
     assert lib.qsim_apply_matrix(None, u.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, None, 0) == _lib.ERR_ARG
 
 
 # ---- the operand ------------------------------------------------------------------------------------------------------------------------
-def _operand(U, targets, controls, n, bits):
-    m = np.zeros(64 * 64)
-    amp, part, rows = (c_int * 64)(), (c_int * 64)(), c_int(-1)
-    flat = np.ascontiguousarray(np.asarray(U, dtype=np.complex128).reshape(-1)).view(np.float64)
-    rc = _lib.load().qsim_apply_matrix_operand(flat.ctypes.data_as(POINTER(c_double)), _ints(targets), len(targets), _ints(controls), len(controls), n,
-                                               bits, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows))
-    assert rc == _lib.QSIM_OK
-    r = rows.value
-    return m[:r * r].reshape(r, r).copy(), list(amp[:r]), list(part[:r])
-
-
 OPERAND_CASES = [  # (targets, controls): K = 3, 4, 5 with and without qubit 0 in the kernel's subset, padded and not, any order
     ([0, 1, 2], []), ([3, 1, 2], []), ([5, 2, 8], [0]), ([4], []), ([4], [0, 1]), ([], [3]), ([6, 0], [1]),
     ([0, 1, 2, 3], []), ([4, 3, 2, 1], []), ([7, 0, 3, 5], [2]), ([1, 9, 4, 6], [0]),
@@ -229,12 +207,13 @@ def test_operand_through_the_instruction_maps(bits):
     for targets, controls in OPERAND_CASES:
         k = len(targets)
         U = rng.standard_normal((1 << k, 1 << k)) + 1j * rng.standard_normal((1 << k, 1 << k))
-        rc, plan = _c_plan(targets, controls, n, bits)
+        rc, plan = plans.apply_matrix_plan(targets, controls, n, bits)
         assert rc == _lib.QSIM_OK and plan["path"] == 1
-        M, amp, part = _operand(U, targets, controls, n, bits)
+        operand = plans.ok(plans.apply_matrix_operand(U, targets, controls, n, bits))
+        M, amp, part = operand["M"], operand["row_amp"].tolist(), operand["row_part"].tolist()
         kk = plan["padded_k"]
         assert M.shape == (2 << kk, 2 << kk)
-        subset = [q for q in range(n) if plan["mask"] >> q & 1]
+        subset = [q for q in range(n) if plan["kernel_mask"] >> q & 1]
         # U (x) 1 over the sorted subset, from the checker: column b of it is the image of basis state b
         dense = np.stack([matrix_ref.apply_matrix(np.eye(1 << kk)[b], U, [subset.index(q) for q in targets]) for b in range(1 << kk)], axis=1)
         cols = rng.standard_normal((1 << kk, 16)) + 1j * rng.standard_normal((1 << kk, 16))
@@ -247,16 +226,15 @@ def test_operand_through_the_instruction_maps(bits):
 
 
 def test_operand_of_the_plain_path_and_refusals():
-    lib = _lib.load()
-    m, amp, part, rows = np.zeros(64 * 64), (c_int * 64)(), (c_int * 64)(), c_int(-1)
-    u = np.eye(2, dtype=np.complex128).reshape(-1).view(np.float64).copy()
-    args =lambda uu, n: (uu.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, None, 0, n, 64, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows))
-    assert lib.qsim_apply_matrix_operand(*args(u, 3)) == _lib.QSIM_OK and rows.value == 0     # the plain kernel takes U as it is
-    assert lib.qsim_apply_matrix_operand(*args(u, 8)) == _lib.QSIM_OK and rows.value == 16
+    u = np.eye(2, dtype=np.complex128)
+    operand = lambda uu, n: plans.apply_matrix_operand(uu, [0], None, n, 64)
+    rc, got = operand(u, 3)
+    assert rc == _lib.QSIM_OK and got["rows"] == 0               # the plain kernel takes U as it is
+    rc, got = operand(u, 8)
+    assert rc == _lib.QSIM_OK and got["rows"] == 16
     for bad in (np.nan, np.inf, -np.inf):
         v = u.copy()
-        v[3] = bad
-        assert lib.qsim_apply_matrix_operand(*args(v, 8)) == _lib.ERR_ARG
-    assert lib.qsim_apply_matrix_operand(None, _ints([0]), 1, None, 0, 8, 64, m.ctypes.data_as(POINTER(c_double)), amp, part, byref(rows)) == _lib.ERR_ARG
-    assert lib.qsim_apply_matrix_operand(u.ctypes.data_as(POINTER(c_double)), _ints([0]), 1, _ints([0]), 1, 8, 64, m.ctypes.data_as(POINTER(c_double)), amp,
-                                         part, byref(rows)) == _lib.ERR_ARG
+        v.view(np.float64).reshape(-1)[3] = bad
+        assert operand(v, 8)[0] == _lib.ERR_ARG
+    assert operand(None, 8)[0] == _lib.ERR_ARG
+    assert plans.apply_matrix_operand(u, [0], [0], 8, 64)[0] == _lib.ERR_ARG

@@ -5,7 +5,7 @@ library for the plan call, no device."""
 import math
 import os
 import re
-from ctypes import byref, c_double, c_int, c_long, c_uint64
+from ctypes import byref, c_double, c_long, c_uint64
 from fractions import Fraction
 
 import numpy as np
@@ -15,22 +15,12 @@ import fp32_ref
 import matrix_ref
 import measure_ref
 import sample_ref
-from gpu_quantum_simulator_amd import Cluster, Simulator, _lib, channels
+from gpu_quantum_simulator_amd import Cluster, Simulator, _lib, channels, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from pauli_rot_ref import rand_state
 
 GRID_CAP = 1024      # workgroups of either sweep at most
 PER_TRIP = 256 * 8   # units a workgroup takes per trip
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _c_plan(qubits, outcome, n, bits, k=None, null=False):
-    wu, cu, wt, ct = c_uint64(0), c_uint64(0), c_long(-1), c_long(-1)
-    rc = _lib.load().qsim_collapse_plan(None if null else _ints(qubits), len(qubits) if k is None else k, outcome, n, bits, byref(wu), byref(cu), byref(wt),
-                                        byref(ct))
-    return rc, dict(weight_units=wu.value, collapse_units=cu.value, weight_trips=wt.value, collapse_trips=ct.value)
 
 
 def test_signatures_and_header_census():
@@ -121,7 +111,7 @@ def test_plan_against_its_rule(bits):
             choices = [list(range(k)), list(range(n - k, n))[::-1], [int(q) for q in rng.permutation(n)[:k]]]
             for qubits in choices:
                 for outcome in {0, (1 << k) - 1, int(rng.integers(0, 1 << k))}:
-                    rc, plan = _c_plan(qubits, outcome, n, bits)
+                    rc, plan = plans.collapse_plan(qubits, outcome, n, bits)
                     assert rc == _lib.QSIM_OK, (n, qubits, outcome)
                     per_unit = 2 if bits == 32 else 1
                     whole = max(1, (1 << n) // per_unit)
@@ -132,13 +122,13 @@ def test_plan_against_its_rule(bits):
                     assert plan["weight_trips"] == max(1, -(-kept_units // (PER_TRIP * GRID_CAP)))
     for precision in (64, 32):                                   # the looping sizes of the GPU test
         for n, qubits, outcome in measure_ref.looping_cases(precision):
-            assert _c_plan(qubits, outcome, n, precision)[1]["collapse_trips"] >= 2
+            assert plans.collapse_plan(qubits, outcome, n, precision)[1]["collapse_trips"] >= 2
 
 
 def test_plan_refusals():
-    ok = lambda *a, **kw: _c_plan(*a, **kw)[0]
-    assert ok([0, 1], 3, 6, 64) == _lib.QSIM_OK and ok([], 0, 6, 64, null=True) == _lib.QSIM_OK
-    assert ok([0], 0, 6, 64, null=True) == _lib.ERR_ARG                                      # a NULL list with k > 0
+    ok = lambda *a, **kw: plans.collapse_plan(*a, **kw)[0]
+    assert ok([0, 1], 3, 6, 64) == _lib.QSIM_OK and ok(None, 0, 6, 64) == _lib.QSIM_OK
+    assert ok(None, 0, 6, 64, k=1) == _lib.ERR_ARG                                      # a NULL list with k > 0
     assert ok([0], 0, 6, 64, k=-1) == _lib.ERR_ARG and ok(list(range(7)), 0, 6, 64) == _lib.ERR_ARG   # k outside [0, n]
     assert ok([0, 0], 0, 6, 64) == _lib.ERR_ARG and ok([2, 5, 2], 0, 6, 64) == _lib.ERR_ARG           # a repeated qubit
     assert ok([6], 0, 6, 64) == _lib.ERR_ARG and ok([-1], 0, 6, 64) == _lib.ERR_ARG                   # out of range
@@ -146,8 +136,8 @@ def test_plan_refusals():
     assert ok([0], 1, 6, 16) == _lib.ERR_ARG and ok([0], 1, -1, 64) == _lib.ERR_ARG and ok([0], 1, 41, 64) == _lib.ERR_ARG
     assert ok(list(range(40)), (1 << 40) - 1, 40, 64) == _lib.QSIM_OK and ok(list(range(40)), 1 << 40, 40, 64) == _lib.ERR_ARG
     wu, cu, wt, ct = c_uint64(), c_uint64(), c_long(), c_long()
-    assert _lib.load().qsim_collapse_plan(_ints([0]), 1, 0, 6, 64, None, byref(cu), byref(wt), byref(ct)) == _lib.ERR_ARG
-    assert _lib.load().qsim_collapse_plan(_ints([0]), 1, 0, 6, 64, byref(wu), byref(cu), byref(wt), None) == _lib.ERR_ARG
+    assert _lib.load().qsim_collapse_plan(_ints([0]), 1, 0, 6, 64, None, byref(cu), byref(wt), byref(ct)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+    assert _lib.load().qsim_collapse_plan(_ints([0]), 1, 0, 6, 64, byref(wu), byref(cu), byref(wt), None) == _lib.ERR_ARG  # raw: NULL for an out-parameter
     w, d = (c_uint64 * 1)(), c_double()
     assert _lib.load().qsim_postselect(None, _ints([0]), 1, 0, byref(d)) == _lib.ERR_ARG    # the calls refuse a NULL state before anything else
     assert _lib.load().qsim_measure(None, _ints([0]), 1, 0.5, w, byref(d)) == _lib.ERR_ARG

@@ -1,12 +1,12 @@
 """Pauli-string expectation values, the parts that need no GPU: the string parser, the host-side sweep count of
-qsim_pauli_sweeps, and the numpy checker (tests/pauli_ref.py) the GPU tests lean on, pinned against dense operators."""
+plans.pauli_sweeps, and the numpy checker (tests/pauli_ref.py) the GPU tests lean on, pinned against dense operators."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import pauli_ref
-from gpu_quantum_simulator_amd import pauli_masks
+from gpu_quantum_simulator_amd import pauli_masks, plans
 
 
 def test_pauli_masks_examples():
@@ -38,13 +38,11 @@ def test_pauli_masks_round_trip():
 def test_sweep_count_matches_grouping():
     from gpu_quantum_simulator_amd import _lib
     lib = _lib.load()
-    K = lib.qsim_pauli_terms_per_sweep()
+    K = plans.pauli_terms_per_sweep()
     assert K in (8, 16, 32)
     up = ctypes.POINTER(ctypes.c_uint64)
     rng = np.random.default_rng(11)
-    got = ctypes.c_long(-1)
-    _lib.check(lib.qsim_pauli_sweeps(None, 0, ctypes.byref(got)))
-    assert got.value == 0
+    assert plans.ok(plans.pauli_sweeps(None))["sweeps"] == 0
     for trial in range(60):
         distinct = int(rng.integers(1, 9))
         pool = rng.integers(0, 1 << 40, size=distinct, dtype=np.uint64)
@@ -52,14 +50,12 @@ def test_sweep_count_matches_grouping():
             pool[0] = 0  # a diagonal group
         xs = np.ascontiguousarray(rng.choice(pool, size=int(rng.integers(1, 6 * K))))
         want = sum(-(-int(np.sum(xs == v)) // K) for v in np.unique(xs))
-        _lib.check(lib.qsim_pauli_sweeps(xs.ctypes.data_as(up), xs.size, ctypes.byref(got)))
-        assert got.value == want, (trial, xs.size, distinct)
+        assert plans.ok(plans.pauli_sweeps(xs.tolist()))["sweeps"] == want, (trial, xs.size, distinct)
     one = np.zeros(3 * K + 1, dtype=np.uint64)
-    _lib.check(lib.qsim_pauli_sweeps(one.ctypes.data_as(up), one.size, ctypes.byref(got)))
-    assert got.value == 4
-    assert lib.qsim_pauli_sweeps(one.ctypes.data_as(up), -1, ctypes.byref(got)) == _lib.ERR_ARG
-    assert lib.qsim_pauli_sweeps(None, 3, ctypes.byref(got)) == _lib.ERR_ARG
-    assert lib.qsim_pauli_sweeps(one.ctypes.data_as(up), 3, None) == _lib.ERR_ARG
+    assert plans.ok(plans.pauli_sweeps(one.tolist()))["sweeps"] == 4
+    assert plans.pauli_sweeps(one.tolist(), num_terms=-1) == (_lib.ERR_ARG, {"sweeps": -1})
+    assert plans.pauli_sweeps(None, num_terms=3) == (_lib.ERR_ARG, {"sweeps": -1})
+    assert lib.qsim_pauli_sweeps(one.ctypes.data_as(up), 3, None) == _lib.ERR_ARG  # raw: NULL for an out-parameter
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 8])

@@ -1,5 +1,5 @@
 """Pauli-string rotations, the parts that need no GPU: the numpy checker (tests/pauli_rot_ref.py) pinned against dense
-operators, the routing plan of qsim_pauli_rotation_plan, the fp32 legality of every sequence the GPU tests run, and the list
+operators, the routing plan of plans.pauli_rotation_plan, the fp32 legality of every sequence the GPU tests run, and the list
 Simulator.evolve hands to the C call."""
 import ctypes
 import math
@@ -10,7 +10,7 @@ import pytest
 import fp32_ref
 import pauli_ref
 import pauli_rot_ref
-from gpu_quantum_simulator_amd import _lib, pauli_masks, trotter_rotations
+from gpu_quantum_simulator_amd import _lib, pauli_masks, trotter_rotations, plans
 
 UP = ctypes.POINTER(ctypes.c_uint64)
 
@@ -42,17 +42,13 @@ def test_checker_replay_is_a_product_in_order():
 
 
 def _plan(rotations):
-    lib = _lib.load()
-    xs = np.array([x for _, x, _ in rotations], dtype=np.uint64)
-    zs = np.array([z for _, _, z in rotations], dtype=np.uint64)
-    sweeps, gates = ctypes.c_long(-1), ctypes.c_long(-1)
-    _lib.check(lib.qsim_pauli_rotation_plan(xs.ctypes.data_as(UP), zs.ctypes.data_as(UP), xs.size, ctypes.byref(sweeps), ctypes.byref(gates)))
-    return sweeps.value, gates.value
+    p = plans.ok(plans.pauli_rotation_plan([x for _, x, _ in rotations], [z for _, _, z in rotations]))
+    return p["sweeps"], p["queued_as_gates"]
 
 
 def test_routing_plan():
     lib = _lib.load()
-    K = lib.qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     assert K == 32
     rng = np.random.default_rng(70)
     all_z = [(0.1, 0, int(z)) for z in rng.integers(1, 1 << 20, size=70)]
@@ -75,16 +71,18 @@ def test_routing_plan():
     # errors
     ok = np.array([1, 2], dtype=np.uint64).ctypes.data_as(UP)
     s, g = ctypes.c_long(), ctypes.c_long()
-    assert lib.qsim_pauli_rotation_plan(ok, ok, -1, ctypes.byref(s), ctypes.byref(g)) == _lib.ERR_ARG
+    assert plans.pauli_rotation_plan([1, 2], [1, 2], num_terms=-1)[0] == _lib.ERR_ARG
     assert b"negative" in lib.qsim_last_error()
-    for args in ((None, ok, 2, ctypes.byref(s), ctypes.byref(g)), (ok, None, 2, ctypes.byref(s), ctypes.byref(g)), (ok, ok, 2, None, ctypes.byref(g)),
-                 (ok, ok, 2, ctypes.byref(s), None)):
-        assert lib.qsim_pauli_rotation_plan(*args) == _lib.ERR_ARG
+    for masks in ((None, [1, 2]), ([1, 2], None)):
+        assert plans.pauli_rotation_plan(*masks, num_terms=2)[0] == _lib.ERR_ARG
+        assert b"NULL" in lib.qsim_last_error()
+    for args in ((ok, ok, 2, None, ctypes.byref(g)), (ok, ok, 2, ctypes.byref(s), None)):
+        assert lib.qsim_pauli_rotation_plan(*args) == _lib.ERR_ARG  # raw: NULL for an out-parameter
         assert b"NULL" in lib.qsim_last_error()
 
 
 def test_fp32_sequences_are_legal():
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    K = plans.pauli_rotations_per_sweep()
     labels = []
     for label, n, start, rotations in pauli_rot_ref.fp32_sequences(K):
         start32 = start.astype(np.complex64)

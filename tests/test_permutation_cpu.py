@@ -1,43 +1,26 @@
 """Permutations of basis states under controls, checked on the CPU: the checker of tests/test_gpu_permutation.py
 (permutation_ref.apply_permutation) against matrix_ref.apply_matrix with the permutation matrix, the host-only plan call
-(qsim_apply_permutation_plan) against a restatement of the tile rule, the operand the kernel is handed
-(qsim_apply_permutation_operand) pushed through a numpy walk of the tiles, and the table builders of
+(plans.apply_permutation_plan) against a restatement of the tile rule, the operand the kernel is handed
+(plans.apply_permutation_operand) pushed through a numpy walk of the tiles, and the table builders of
 gpu_quantum_simulator_amd.permutations.  Every comparison of amplitudes is exact."""
 import itertools
-from ctypes import POINTER, byref, c_int, c_long, c_uint16, c_uint32, c_uint64
+from ctypes import POINTER, byref, c_int, c_long, c_uint32, c_uint64
 
 import numpy as np
 import pytest
 
 import matrix_ref
 import permutation_ref
-from gpu_quantum_simulator_amd import _lib, permutations
+from gpu_quantum_simulator_amd import _lib, permutations, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 
-NEW_NAMES = ("qsim_apply_permutation", "qsim_apply_permutation_max_qubits", "qsim_apply_permutation_plan", "qsim_apply_permutation_operand",
-             "qsim_permutation_sweeps_launched")
+NEW_NAMES = ("qsim_apply_permutation", "qsim_apply_permutation_max_qubits", "qsim_apply_permutation_plan", "qsim_apply_permutation_operand",  # census
+             "qsim_permutation_sweeps_launched")  # both lines: census of the signature table
 GRID_CAP = 512
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
 
 
 def _table(perm):
     return np.ascontiguousarray(perm, dtype=np.uint32).ctypes.data_as(POINTER(c_uint32))
-
-
-def _c_plan(targets, controls, n, bits, k=None, c=None, null_targets=False, null_controls=False):
-    path, tile_bits, mask, tiles, units, trips = c_int(-1), c_int(-1), c_uint64(0), c_uint64(0), c_uint64(0), c_long(-1)
-    rc = _lib.load().qsim_apply_permutation_plan(None if null_targets else _ints(targets), len(targets) if k is None else k,
-                                                 None if null_controls else _ints(controls), len(controls) if c is None else c, n, bits,
-                                                 byref(path), byref(tile_bits), byref(mask), byref(tiles), byref(units), byref(trips))
-    return rc, dict(path=path.value, tile_bits=tile_bits.value, mask=mask.value, tiles=tiles.value, units=units.value, trips=trips.value)
-
-
-def _c_operand(perm, targets, controls, n, bits):
-    out, entries = (c_uint16 * 8192)(), c_int(-1)
-    rc = _lib.load().qsim_apply_permutation_operand(_table(perm), _ints(targets), len(targets), _ints(controls), len(controls), n, bits, out, byref(entries))
-    return rc, np.array(out[:max(entries.value, 0)], dtype=np.int64)
 
 
 def _model(targets, controls, n, f32):
@@ -48,8 +31,8 @@ def _model(targets, controls, n, f32):
     free = [q for q in range(n) if q not in targets and q not in controls]
     tile = sorted(list(targets) + free[:B - len(targets)])
     tiles = 1 << (n - c - B)
-    return dict(path=1 if B == full else 0, tile_bits=B, mask=sum(1 << q for q in tile), tiles=tiles, units=max(1, (1 << (n - c)) >> (1 if f32 else 0)),
-                trips=-(-tiles // GRID_CAP))
+    return dict(path=1 if B == full else 0, tile_bits=B, tile_mask=sum(1 << q for q in tile), tiles=tiles, units=max(1, (1 << (n - c)) >> (1 if f32 else 0)),
+                trips_per_workgroup=-(-tiles // GRID_CAP))
 
 
 def _int_state(n, seed, dtype=np.complex128):
@@ -61,7 +44,7 @@ def _int_state(n, seed, dtype=np.complex128):
 def test_signatures_have_the_new_names():
     for name in NEW_NAMES:
         assert name in _lib.SIGNATURES
-    assert _lib.load().qsim_apply_permutation_max_qubits() == 10 == permutations.MAX_QUBITS
+    assert plans.apply_permutation_max_qubits() == 10 == permutations.MAX_QUBITS
 
 
 # ---- the checker ----------------------------------------------------------------------------------------------------------------------
@@ -104,36 +87,36 @@ def test_plan_call_against_the_tile_rule(bits):
                 rest = [q for q in range(n) if q not in targets]
                 choices = [[], rest[:1], rest[-1:], rest[len(rest) // 2:len(rest) // 2 + 1], sorted(set(rest[:1] + rest[-1:])), rest[1:4]]
                 for controls in choices:
-                    rc, got = _c_plan(targets, controls, n, bits)
+                    rc, got = plans.apply_permutation_plan(targets, controls, n, bits)
                     assert rc == _lib.QSIM_OK, (n, targets, controls)
                     assert got == _model(targets, controls, n, f32), (n, targets, controls)
-                    assert got["mask"] & sum(1 << q for q in controls) == 0 and all(got["mask"] >> q & 1 for q in targets)
+                    assert got["tile_mask"] & sum(1 << q for q in controls) == 0 and all(got["tile_mask"] >> q & 1 for q in targets)
 
 
 def test_plan_call_named_cases():
     # k = 10 with all targets high: two padding bits in fp64 (64-byte runs), three in fp32
-    rc, got = _c_plan(list(range(6, 16)), [], 16, 64)
-    assert rc == _lib.QSIM_OK and got["mask"] == 0b11 | sum(1 << q for q in range(6, 16)) and got["tile_bits"] == 12 and got["tiles"] == 16
-    rc, got = _c_plan(list(range(6, 16)), [], 16, 32)
-    assert got["mask"] == 0b111 | sum(1 << q for q in range(6, 16)) and got["tile_bits"] == 13
+    rc, got = plans.apply_permutation_plan(list(range(6, 16)), [], 16, 64)
+    assert rc == _lib.QSIM_OK and got["tile_mask"] == 0b11 | sum(1 << q for q in range(6, 16)) and got["tile_bits"] == 12 and got["tiles"] == 16
+    rc, got = plans.apply_permutation_plan(list(range(6, 16)), [], 16, 32)
+    assert got["tile_mask"] == 0b111 | sum(1 << q for q in range(6, 16)) and got["tile_bits"] == 13
     # k = 9 high keeps three in fp64; a control on qubit 0 is stepped over
-    assert _c_plan(list(range(7, 16)), [], 16, 64)[1]["mask"] & 0x7F == 0b111
-    assert _c_plan(list(range(7, 16)), [0], 16, 64)[1]["mask"] & 0x7F == 0b1110
+    assert plans.apply_permutation_plan(list(range(7, 16)), [], 16, 64)[1]["tile_mask"] & 0x7F == 0b111
+    assert plans.apply_permutation_plan(list(range(7, 16)), [0], 16, 64)[1]["tile_mask"] & 0x7F == 0b1110
     # controls on qubit 0, in between and on top take one factor of two of tiles each and leave the tile's size alone
-    assert _c_plan([3, 9], [0, 5, 15], 16, 64)[1] == dict(path=1, tile_bits=12, mask=0b11_1111_1101_1110, tiles=2, units=1 << 13, trips=1)
+    assert plans.apply_permutation_plan([3, 9], [0, 5, 15], 16, 64)[1] == dict(path=1, tile_bits=12, tile_mask=0b11_1111_1101_1110, tiles=2, units=1 << 13, trips_per_workgroup=1)
     # both sides of the path switch: n - c = 11 | 12 (fp64), 12 | 13 (fp32)
     for bits, full in ((64, 12), (32, 13)):
-        assert _c_plan([0], [], full - 1, bits)[1]["path"] == 0 and _c_plan([0], [], full, bits)[1]["path"] == 1
-        assert _c_plan([0], [full], full + 1, bits)[1]["path"] == 1 and _c_plan([0], [full - 1], full, bits)[1]["path"] == 0
+        assert plans.apply_permutation_plan([0], [], full - 1, bits)[1]["path"] == 0 and plans.apply_permutation_plan([0], [], full, bits)[1]["path"] == 1
+        assert plans.apply_permutation_plan([0], [full], full + 1, bits)[1]["path"] == 1 and plans.apply_permutation_plan([0], [full - 1], full, bits)[1]["path"] == 0
     # the looping sizes of tests/test_gpu_permutation.py: two tiles per workgroup at the default cap
-    assert _c_plan(list(range(2, 22, 2)), [], 22, 64)[1]["trips"] == 2 and _c_plan(list(range(2, 22, 2)), [], 21, 64)[1]["trips"] == 1
-    assert _c_plan(list(range(2, 22, 2)), [], 23, 32)[1]["trips"] == 2 and _c_plan(list(range(2, 22, 2)), [], 22, 32)[1]["trips"] == 1
-    assert _c_plan([0], [], 30, 64)[1]["units"] == 1 << 30 and _c_plan([0], [29], 30, 32)[1]["units"] == 1 << 28
-    assert _c_plan([], [], 0, 32)[1] == dict(path=0, tile_bits=0, mask=0, tiles=1, units=1, trips=1)
+    assert plans.apply_permutation_plan(list(range(2, 22, 2)), [], 22, 64)[1]["trips_per_workgroup"] == 2 and plans.apply_permutation_plan(list(range(2, 22, 2)), [], 21, 64)[1]["trips_per_workgroup"] == 1
+    assert plans.apply_permutation_plan(list(range(2, 22, 2)), [], 23, 32)[1]["trips_per_workgroup"] == 2 and plans.apply_permutation_plan(list(range(2, 22, 2)), [], 22, 32)[1]["trips_per_workgroup"] == 1
+    assert plans.apply_permutation_plan([0], [], 30, 64)[1]["units"] == 1 << 30 and plans.apply_permutation_plan([0], [29], 30, 32)[1]["units"] == 1 << 28
+    assert plans.apply_permutation_plan([], [], 0, 32)[1] == dict(path=0, tile_bits=0, tile_mask=0, tiles=1, units=1, trips_per_workgroup=1)
 
 
 def test_plan_call_and_operand_refusals():
-    ok = lambda *a, **kw: _c_plan(*a, **kw)[0]
+    ok = lambda *a, **kw: plans.apply_permutation_plan(*a, **kw)[0]
     assert ok([0, 1], [2], 6, 64) == _lib.QSIM_OK
     assert ok([0, 0], [], 6, 64) == _lib.ERR_ARG                 # a repeated target
     assert ok([0], [2, 2], 6, 64) == _lib.ERR_ARG                # a repeated control
@@ -143,24 +126,23 @@ def test_plan_call_and_operand_refusals():
     assert ok(list(range(11)), [], 16, 64) == _lib.ERR_ARG       # k > 10
     assert ok(list(range(10)), [], 16, 64) == _lib.QSIM_OK
     assert ok([0, 1, 2], [], 2, 64) == _lib.ERR_ARG              # k > n
-    assert ok([0], [], 6, 64, k=-1) == _lib.ERR_ARG and ok([0], [1], 6, 64, c=-1) == _lib.ERR_ARG
-    assert ok([0], [], 6, 64, null_targets=True) == _lib.ERR_ARG and ok([0], [1], 6, 64, null_controls=True) == _lib.ERR_ARG
-    assert ok([], [], 6, 64, null_targets=True, null_controls=True) == _lib.QSIM_OK
+    assert ok([0], [], 6, 64, k=-1) == _lib.ERR_ARG and ok([0], [1], 6, 64, num_controls=-1) == _lib.ERR_ARG
+    assert ok(None, [], 6, 64, k=1) == _lib.ERR_ARG and ok([0], None, 6, 64, num_controls=1) == _lib.ERR_ARG
+    assert ok(None, None, 6, 64) == _lib.QSIM_OK
     assert ok([0], [], -1, 64) == _lib.ERR_ARG and ok([0], [], 41, 64) == _lib.ERR_ARG
     assert ok([0], [], 40, 64) == _lib.QSIM_OK and ok([], [], 0, 32) == _lib.QSIM_OK
     assert ok([0], [], 6, 16) == _lib.ERR_ARG                    # precision_bits
     lib = _lib.load()
     tile_bits, mask, tiles, units, trips = c_int(), c_uint64(), c_uint64(), c_uint64(), c_long()
-    assert lib.qsim_apply_permutation_plan(_ints([0]), 1, None, 0, 6, 64, None, byref(tile_bits), byref(mask), byref(tiles), byref(units),
-                                           byref(trips)) == _lib.ERR_ARG
+    assert lib.qsim_apply_permutation_plan(_ints([0]), 1, None, 0, 6, 64, None, byref(tile_bits), byref(mask), byref(tiles), byref(units),  # raw, as below
+                                           byref(trips)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
     # the table: an entry >= 2^k, two equal entries
-    assert _c_operand([0, 1, 2, 3], [0, 1], [], 6, 64)[0] == _lib.QSIM_OK
-    assert _c_operand([0, 1, 2, 4], [0, 1], [], 6, 64)[0] == _lib.ERR_ARG
-    assert _c_operand([0, 1, 2, 2], [0, 1], [], 6, 64)[0] == _lib.ERR_ARG
-    assert _c_operand([1], [], [], 6, 64)[0] == _lib.ERR_ARG and _c_operand([0], [], [], 6, 64)[0] == _lib.QSIM_OK
-    assert _c_operand([0, 1], [0], [0], 6, 64)[0] == _lib.ERR_ARG
-    out, entries = (c_uint16 * 8192)(), c_int()
-    assert lib.qsim_apply_permutation_operand(None, _ints([0]), 1, None, 0, 6, 64, out, byref(entries)) == _lib.ERR_ARG
+    assert plans.apply_permutation_operand([0, 1, 2, 3], [0, 1], [], 6, 64)[0] == _lib.QSIM_OK
+    assert plans.apply_permutation_operand([0, 1, 2, 4], [0, 1], [], 6, 64)[0] == _lib.ERR_ARG
+    assert plans.apply_permutation_operand([0, 1, 2, 2], [0, 1], [], 6, 64)[0] == _lib.ERR_ARG
+    assert plans.apply_permutation_operand([1], [], [], 6, 64)[0] == _lib.ERR_ARG and plans.apply_permutation_operand([0], [], [], 6, 64)[0] == _lib.QSIM_OK
+    assert plans.apply_permutation_operand([0, 1], [0], [0], 6, 64)[0] == _lib.ERR_ARG
+    assert plans.apply_permutation_operand(None, [0], None, 6, 64)[0] == _lib.ERR_ARG
     # the call itself refuses a NULL state before it looks at anything else
     assert lib.qsim_apply_permutation(None, _table([0, 1]), _ints([0]), 1, None, 0) == _lib.ERR_ARG
 
@@ -185,15 +167,16 @@ def test_tile_walk_with_plan_and_operand_reproduces_the_checker(n, bits):
     cases += [([int(v) for v in rng.permutation(1 << len(top))], top, []), ([int(v) for v in rng.permutation(1 << len(top))], top[::-1], []),
               ([1, 0], [0], [n - 1]), ([1, 0], [n - 1], [0]), ([0], [], [0, n - 1]), ([0], [], [])]
     for perm, targets, controls in cases:
-        rc, plan = _c_plan(targets, controls, n, bits)
+        rc, plan = plans.apply_permutation_plan(targets, controls, n, bits)
         assert rc == _lib.QSIM_OK
-        rc, local_map = _c_operand(perm, targets, controls, n, bits)
+        rc, operand = plans.apply_permutation_operand(perm, targets, controls, n, bits)
+        local_map = operand["local_map"]
         assert rc == _lib.QSIM_OK and local_map.size == 1 << plan["tile_bits"]
         assert np.array_equal(np.sort(local_map), np.arange(local_map.size))                       # a bijection of range(2^B)
-        tile_bits = [q for q in range(n) if plan["mask"] >> q & 1]
+        tile_bits = [q for q in range(n) if plan["tile_mask"] >> q & 1]
         pad = sum(1 << i for i, q in enumerate(tile_bits) if q not in targets)
         assert np.array_equal(local_map & pad, np.arange(local_map.size) & pad)                    # the padding bits are kept
-        got = permutation_ref.walk_tiles(psi, plan["mask"], controls, local_map)
+        got = permutation_ref.walk_tiles(psi, plan["tile_mask"], controls, local_map)
         assert np.array_equal(got, permutation_ref.apply_permutation(psi, perm, targets, controls)), (perm[:8], targets, controls)
 
 

@@ -1,6 +1,6 @@
 """The quantum Fourier transform, checked on the CPU: the checker of tests/test_gpu_qft.py (qft_ref.apply_qft) against the dense DFT
 through matrix_ref.apply_matrix, the pass rule (qft_ref.walk_plan) against the checker for the digit lists the host-only plan call
-(qsim_apply_qft_plan) reports, the plan itself against a restatement of its rule, its refusals, the complex64 replay's error on every
+(plans.apply_qft_plan) reports, the plan itself against a restatement of its rule, its refusals, the complex64 replay's error on every
 shape the GPU test uses, the textbook circuit the GPU test cross-checks against, and a census of include/qsim_qft.h against
 _lib.QFT_SIGNATURES.  Needs the built library for the plan call, no device."""
 import itertools
@@ -14,26 +14,13 @@ import pytest
 import fp32_ref
 import matrix_ref
 import qft_ref
-from gpu_quantum_simulator_amd import Cluster, Simulator, _lib
+from gpu_quantum_simulator_amd import Cluster, Simulator, _lib, plans
+from gpu_quantum_simulator_amd._marshal import ints as _ints
 from pauli_rot_ref import rand_state
 
 GRID_CAP = 512
 MAX_DIGIT = 10
 OWN_LONG_CAP = 9   # the plan's own cap for a register of more than ten qubits: three padding bits in an fp64 tile
-
-
-def _ints(values):
-    return (c_int * max(len(values), 1))(*values)
-
-
-def _c_plan(qubits, n, bits, cap=0, k=None, null=False):
-    passes, tiles, units, trips = c_int(-1), c_uint64(0), c_uint64(0), c_long(-1)
-    digits, oop, masks = (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-    rc = _lib.load().qsim_apply_qft_plan(None if null else _ints(qubits), len(qubits) if k is None else k, n, bits, cap, byref(passes), digits, oop,
-                                         masks, byref(tiles), byref(units), byref(trips))
-    m = max(passes.value, 0)
-    return rc, dict(passes=passes.value, digits=list(digits[:m]), oop=list(oop[:m]), masks=list(masks[:m]), tiles=tiles.value, units=units.value,
-                    trips=trips.value)
 
 
 def _pad_subset(subset, size, n):
@@ -56,7 +43,7 @@ def test_signatures_and_header_census():
     lib = _lib.load()
     for name in _lib.QFT_SIGNATURES:
         assert getattr(lib, name).restype is _lib.QFT_SIGNATURES[name][0]   # load() has applied the table
-    assert lib.qsim_apply_qft_max_digit_bits() == MAX_DIGIT
+    assert plans.apply_qft_max_digit_bits() == MAX_DIGIT
     assert hasattr(Simulator, "apply_qft") and not hasattr(Cluster, "apply_qft")
 
 
@@ -104,20 +91,20 @@ def test_plan_against_its_rule_and_walk_plan_against_the_checker(bits):
         for k in sorted({max(0, min(k, n)) for k in (0, 1, 2, 5, 10, n - 1, n)}):
             for qubits in _register_choices(n, k, rng):
                 for cap in (0, 1, 3, 4, 10):
-                    rc, plan = _c_plan(qubits, n, bits, cap)
+                    rc, plan = plans.apply_qft_plan(qubits, n, bits, cap)
                     assert rc == _lib.QSIM_OK, (n, qubits, cap)
                     limit = cap or (MAX_DIGIT if k <= MAX_DIGIT else OWN_LONG_CAP)
-                    digits = plan["digits"]
+                    digits = plan["digit_bits"]
                     assert sum(digits) == k and all(1 <= d <= limit for d in digits) and plan["passes"] == -(-k // limit)
-                    assert sum(plan["oop"]) % 2 == 0 and all(plan["oop"][:-1]) and (k > limit or plan["oop"] == [0] * plan["passes"])
+                    assert sum(plan["out_of_place"]) % 2 == 0 and all(plan["out_of_place"][:-1]) and (k > limit or plan["out_of_place"] == [0] * plan["passes"])
                     B = min(full, n)
                     first = 0
-                    for d, mask in zip(digits, plan["masks"]):
+                    for d, mask in zip(digits, plan["tile_mask"]):
                         top = qubits[k - d:]                     # the sub-register's top d bits: the rest has moved up behind the digits done
                         assert mask == _pad_subset(sum(1 << q for q in top), B, n), (n, qubits, cap, first)
                         first += d
                     assert plan["tiles"] == 1 << (n - B) and plan["units"] == max(1, (1 << n) >> (1 if bits == 32 else 0))
-                    assert plan["trips"] == -(-plan["tiles"] // GRID_CAP)
+                    assert plan["trips_per_workgroup"] == -(-plan["tiles"] // GRID_CAP)
                     if n <= 12 or cap in (0, 4):
                         for inverse in (False, True):
                             got = qft_ref.walk_plan(psi, qubits, digits, inverse)
@@ -125,28 +112,28 @@ def test_plan_against_its_rule_and_walk_plan_against_the_checker(bits):
 
 
 def test_plan_named_cases():
-    assert _c_plan(list(range(10)), 30, 64)[1]["digits"] == [10] and _c_plan(list(range(10)), 30, 64)[1]["oop"] == [0]
-    p = _c_plan(list(range(20)), 30, 64, 10)[1]
-    assert p["digits"] == [10, 10] and p["oop"] == [1, 1] and p["masks"] == [0b11 | sum(1 << q for q in range(10, 20))] * 2
-    p = _c_plan(list(range(20)), 30, 64)[1]                                        # the plan's own cap beyond ten qubits is nine bits
-    assert p["digits"] == [7, 7, 6] and p["oop"] == [1, 1, 0] and p["masks"][0] == 0b11111 | sum(1 << q for q in range(13, 20))
-    assert _c_plan(list(range(18)), 30, 64)[1]["digits"] == [9, 9]
-    p = _c_plan(list(range(30)), 30, 64, 10)[1]
-    assert p["digits"] == [10, 10, 10] and p["oop"] == [1, 1, 0] and p["tiles"] == 1 << 18 and p["trips"] == 512
-    assert _c_plan(list(range(30)), 30, 64)[1]["digits"] == [8, 8, 7, 7] and _c_plan(list(range(30)), 30, 64)[1]["oop"] == [1, 1, 1, 1]
-    assert _c_plan(list(range(11)), 13, 64)[1]["digits"] == [6, 5]                 # as even as the cap allows
-    assert _c_plan(list(range(12)), 13, 64, 4)[1]["oop"] == [1, 1, 0] and _c_plan(list(range(13)), 13, 64, 4)[1]["oop"] == [1, 1, 1, 1]
-    assert _c_plan(list(range(13)), 13, 64, 1)[1]["passes"] == 13 and sum(_c_plan(list(range(13)), 13, 64, 1)[1]["oop"]) == 12
-    assert _c_plan([], 0, 32)[1] == dict(passes=0, digits=[], oop=[], masks=[], tiles=1, units=1, trips=1)
+    assert plans.apply_qft_plan(list(range(10)), 30, 64, 0)[1]["digit_bits"] == [10] and plans.apply_qft_plan(list(range(10)), 30, 64, 0)[1]["out_of_place"] == [0]
+    p = plans.apply_qft_plan(list(range(20)), 30, 64, 10)[1]
+    assert p["digit_bits"] == [10, 10] and p["out_of_place"] == [1, 1] and p["tile_mask"] == [0b11 | sum(1 << q for q in range(10, 20))] * 2
+    p = plans.apply_qft_plan(list(range(20)), 30, 64, 0)[1]                                        # the plan's own cap beyond ten qubits is nine bits
+    assert p["digit_bits"] == [7, 7, 6] and p["out_of_place"] == [1, 1, 0] and p["tile_mask"][0] == 0b11111 | sum(1 << q for q in range(13, 20))
+    assert plans.apply_qft_plan(list(range(18)), 30, 64, 0)[1]["digit_bits"] == [9, 9]
+    p = plans.apply_qft_plan(list(range(30)), 30, 64, 10)[1]
+    assert p["digit_bits"] == [10, 10, 10] and p["out_of_place"] == [1, 1, 0] and p["tiles"] == 1 << 18 and p["trips_per_workgroup"] == 512
+    assert plans.apply_qft_plan(list(range(30)), 30, 64, 0)[1]["digit_bits"] == [8, 8, 7, 7] and plans.apply_qft_plan(list(range(30)), 30, 64, 0)[1]["out_of_place"] == [1, 1, 1, 1]
+    assert plans.apply_qft_plan(list(range(11)), 13, 64, 0)[1]["digit_bits"] == [6, 5]                 # as even as the cap allows
+    assert plans.apply_qft_plan(list(range(12)), 13, 64, 4)[1]["out_of_place"] == [1, 1, 0] and plans.apply_qft_plan(list(range(13)), 13, 64, 4)[1]["out_of_place"] == [1, 1, 1, 1]
+    assert plans.apply_qft_plan(list(range(13)), 13, 64, 1)[1]["passes"] == 13 and sum(plans.apply_qft_plan(list(range(13)), 13, 64, 1)[1]["out_of_place"]) == 12
+    assert plans.apply_qft_plan([], 0, 32, 0)[1] == dict(passes=0, digit_bits=[], out_of_place=[], tile_mask=[], tiles=1, units=1, trips_per_workgroup=1)
     for precision in (64, 32):                                                       # the looping sizes of the GPU test
         n = 22 if precision == 64 else 23
-        assert _c_plan(list(range(n)), n, precision)[1]["trips"] >= 2
+        assert plans.apply_qft_plan(list(range(n)), n, precision, 0)[1]["trips_per_workgroup"] >= 2
 
 
 def test_plan_refusals():
-    ok = lambda *a, **kw: _c_plan(*a, **kw)[0]
-    assert ok([0, 1], 6, 64) == _lib.QSIM_OK and ok([], 6, 64, null=True) == _lib.QSIM_OK
-    assert ok([0], 6, 64, null=True) == _lib.ERR_ARG                                 # a NULL list with k > 0
+    ok = lambda qubits, n, bits, cap=0, **kw: plans.apply_qft_plan(qubits, n, bits, cap, **kw)[0]
+    assert ok([0, 1], 6, 64) == _lib.QSIM_OK and ok(None, 6, 64) == _lib.QSIM_OK
+    assert ok(None, 6, 64, k=1) == _lib.ERR_ARG                                 # a NULL list with k > 0
     assert ok([0], 6, 64, k=-1) == _lib.ERR_ARG and ok(list(range(7)), 6, 64) == _lib.ERR_ARG   # k outside [0, n]
     assert ok([0, 0], 6, 64) == _lib.ERR_ARG and ok([2, 5, 2], 6, 64) == _lib.ERR_ARG           # a repeated qubit
     assert ok([6], 6, 64) == _lib.ERR_ARG and ok([-1], 6, 64) == _lib.ERR_ARG                   # out of range
@@ -156,8 +143,8 @@ def test_plan_refusals():
     assert ok(list(range(40)), 40, 64) == _lib.QSIM_OK
     passes, tiles, units, trips = c_int(), c_uint64(), c_uint64(), c_long()
     digits, oop, masks = (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-    assert _lib.load().qsim_apply_qft_plan(_ints([0]), 1, 6, 64, 0, None, digits, oop, masks, byref(tiles), byref(units), byref(trips)) == _lib.ERR_ARG
-    assert _lib.load().qsim_apply_qft_plan(_ints([0]), 1, 6, 64, 0, byref(passes), digits, oop, None, byref(tiles), byref(units), byref(trips)) == _lib.ERR_ARG
+    assert _lib.load().qsim_apply_qft_plan(_ints([0]), 1, 6, 64, 0, None, digits, oop, masks, byref(tiles), byref(units), byref(trips)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+    assert _lib.load().qsim_apply_qft_plan(_ints([0]), 1, 6, 64, 0, byref(passes), digits, oop, None, byref(tiles), byref(units), byref(trips)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
     assert _lib.load().qsim_apply_qft(None, _ints([0]), 1, 0, 0) == _lib.ERR_ARG     # the call refuses a NULL state before anything else
 
 

@@ -1,5 +1,5 @@
 """Shots drawn on the device, what can be checked without one: the checker of tests/test_gpu_sample.py (sample_ref) against a brute-force
-loop in exact rational arithmetic at n <= 6, the host-only geometry call (qsim_sample_geometry) against the rule in include/qsim.h, and
+loop in exact rational arithmetic at n <= 6, the host-only geometry call (plans.sample_geometry) against the rule in include/qsim.h, and
 the new names in the binding."""
 from ctypes import byref, c_int, c_uint64
 
@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 
 import sample_ref
-from gpu_quantum_simulator_amd import Simulator, _lib
+from gpu_quantum_simulator_amd import Simulator, _lib, plans
 from pauli_rot_ref import rand_state
 
-NEW_NAMES = ("qsim_sample_geometry", "qsim_sample_shots", "qsim_sample_stage_times")
+NEW_NAMES = ("qsim_sample_geometry", "qsim_sample_shots", "qsim_sample_stage_times")  # census of the signature table
 EDGES = [0.0, 1e-300, 1.0]
-
-
-def _geometry(n):
-    cb, gb, sb = c_int(-1), c_int(-1), c_uint64(0)
-    rc = _lib.load().qsim_sample_geometry(n, byref(cb), byref(gb), byref(sb))
-    return rc, cb.value, gb.value, sb.value
 
 
 def test_signatures_and_exports_have_the_new_names():
@@ -29,8 +23,8 @@ def test_signatures_and_exports_have_the_new_names():
 
 @pytest.mark.parametrize("n", [1, 7, 8, 9, 18, 19, 30])
 def test_geometry_clips_the_bits_by_n(n):
-    rc, cb, gb, sb = _geometry(n)
-    assert rc == _lib.QSIM_OK
+    got = plans.ok(plans.sample_geometry(n))
+    cb, gb, sb = got["chunk_bits"], got["group_bits"], got["scratch_bytes"]
     assert (cb, gb) == (min(8, n), min(18, n))
     assert sb == 8 * ((1 << (n - cb)) + (1 << (n - gb)))
     if n == 30:
@@ -41,12 +35,13 @@ def test_geometry_refusals():
     lib = _lib.load()
     cb, gb, sb = c_int(), c_int(), c_uint64()
     for n in (-1, 41):
-        assert lib.qsim_sample_geometry(n, byref(cb), byref(gb), byref(sb)) == _lib.ERR_ARG
-        assert b"qsim_sample_geometry" in lib.qsim_last_error()
-    assert lib.qsim_sample_geometry(8, None, byref(gb), byref(sb)) == _lib.ERR_ARG
-    assert lib.qsim_sample_geometry(8, byref(cb), None, byref(sb)) == _lib.ERR_ARG
-    assert lib.qsim_sample_geometry(8, byref(cb), byref(gb), None) == _lib.ERR_ARG
-    assert _geometry(0)[:3] == (_lib.QSIM_OK, 0, 0) and _geometry(40)[:3] == (_lib.QSIM_OK, 8, 18)
+        assert plans.sample_geometry(n) == (_lib.ERR_ARG, dict(chunk_bits=-1, group_bits=-1, scratch_bytes=0))
+        assert b"qsim_sample_geometry" in lib.qsim_last_error()  # the library's message names the call
+    assert lib.qsim_sample_geometry(8, None, byref(gb), byref(sb)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+    assert lib.qsim_sample_geometry(8, byref(cb), None, byref(sb)) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+    assert lib.qsim_sample_geometry(8, byref(cb), byref(gb), None) == _lib.ERR_ARG  # raw: NULL for an out-parameter
+    geometry = lambda n: (plans.sample_geometry(n)[0],) + tuple(plans.sample_geometry(n)[1][key] for key in ("chunk_bits", "group_bits"))
+    assert geometry(0) == (_lib.QSIM_OK, 0, 0) and geometry(40) == (_lib.QSIM_OK, 8, 18)
 
 
 # ---- the checker --------------------------------------------------------------------------------------------------------------------

@@ -284,10 +284,7 @@ def test_the_conditions_hold_for_every_program(family, precision):
 def test_the_operands_take_the_path_their_kind_is_named_for():
     """Host only: at n = 14 the main kinds take the main kernels and the small kinds the plain ones, a moving transform has at least
     three sweeps, two of them out of place, a single one is one sweep in place."""
-    from ctypes import byref, c_int, c_long, c_uint64
-    from gpu_quantum_simulator_amd import _lib
-    lib = _lib.load()
-    ints = lambda qs: (c_int * max(len(qs), 1))(*qs)
+    from gpu_quantum_simulator_amd import plans
     seen = set()
     for precision in PRECISIONS:
         for family in ("pair", "ring", "tenants", "walk"):
@@ -296,23 +293,18 @@ def test_the_operands_take_the_path_their_kind_is_named_for():
                 steps += [("permutation_main", op["partner"]["after"]) for _, op in program if "partner" in op]
                 steps += [("qft_moving", op["partner"]["qft"]) for _, op in program if "partner" in op]
                 for kind, op in steps:
-                    path, i0, l0, u0, u1, u2 = c_int(-1), c_int(), c_long(), c_uint64(), c_uint64(), c_uint64()
                     if kind in ("matrix_main", "matrix_small"):
                         t, c = op["targets"], op["controls"]
-                        assert lib.qsim_apply_matrix_plan(ints(t), len(t), ints(c), len(c), n, precision, byref(path), byref(i0), byref(u0), byref(u1), byref(l0)) == 0
-                        assert (path.value, len(t), len(c)) == ((1, 5, 1) if kind == "matrix_main" else (0, 2, 9)), (label, kind)
+                        path = plans.ok(plans.apply_matrix_plan(t, c, n, precision))["path"]
+                        assert (path, len(t), len(c)) == ((1, 5, 1) if kind == "matrix_main" else (0, 2, 9)), (label, kind)
                     elif kind in ("permutation_main", "permutation_small"):
                         t, c = op["targets"], op["controls"]
-                        assert lib.qsim_apply_permutation_plan(ints(t), len(t), ints(c), len(c), n, precision, byref(path), byref(i0), byref(u0), byref(u1), byref(u2),
-                                                               byref(l0)) == 0
-                        assert (path.value, len(t)) == ((1, 10) if kind == "permutation_main" else (0, 3)), (label, kind)
+                        path = plans.ok(plans.apply_permutation_plan(t, c, n, precision))["path"]
+                        assert (path, len(t)) == ((1, 10) if kind == "permutation_main" else (0, 3)), (label, kind)
                     elif kind in ("qft_single", "qft_moving"):
-                        qs = op["qubits"]
-                        passes, digits, oop, masks = c_int(-1), (c_int * 40)(), (c_int * 40)(), (c_uint64 * 40)()
-                        assert lib.qsim_apply_qft_plan(ints(qs), len(qs), n, precision, op["max_digit_bits"], byref(passes), digits, oop, masks, byref(u0), byref(u1),
-                                                       byref(l0)) == 0
-                        moving = sum(oop[p] for p in range(passes.value))
-                        assert (passes.value, moving) == ((1, 0) if kind == "qft_single" else (3, 2)), (label, kind, passes.value, moving)
+                        plan = plans.ok(plans.apply_qft_plan(op["qubits"], n, precision, op["max_digit_bits"]))
+                        passes, moving = plan["passes"], sum(plan["out_of_place"])
+                        assert (passes, moving) == ((1, 0) if kind == "qft_single" else (3, 2)), (label, kind, passes, moving)
                     else:
                         continue
                     seen.add(kind)

@@ -11,7 +11,7 @@ sweep is a difference of whole calls — the C ABI has no entry that launches on
   call_0                 the call without rotations: lambda = H psi and the energy sweep
   per row:  call         the whole call;  forward: the G rotations alone (apply_pauli_rotations + sync), one sweep
             backward     call - call_0 - forward
-            units        what qsim_controlled_gradient_plan reports for the backward sweep
+            units        what plans.controlled_gradient_plan reports for the backward sweep
             share        backward / backward of `uncontrolled`; the traffic model of DESIGN "Adjoint gradients under controls" says 2^-c
 Rows, per precision (64, 32):
   uncontrolled           the yardstick (k_pauli_adjoint)
@@ -19,7 +19,6 @@ Rows, per precision (64, 32):
   low_0                  one control on qubit 0 (fp32: the odd slot of every unit; fp64: every other amplitude of a line)
 Each precision runs in a child process of its own under its own `timeout -k 10`; the first failure ends the run."""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -35,21 +34,17 @@ G = 8
 
 
 def child(args):
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib
+    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, plans
     n = args.n
     assert n >= 16
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     reps = max(5, args.reps)
     rows = {}
-    up = ctypes.POINTER(ctypes.c_uint64)
 
     def units(controls):
-        c, x, hx = ((ctypes.c_uint64 * G)(*[v] * G) for v in (sum(1 << q for q in controls), STRING_X, 0))
-        a, s, u = ctypes.c_long(), ctypes.c_long(), ctypes.c_uint64()
-        _lib.check(lib.qsim_controlled_gradient_plan(ctypes.cast(c, up), ctypes.cast(x, up), G, ctypes.cast(hx, up), 1, n, args.precision,
-                                                     ctypes.byref(a), ctypes.byref(s), ctypes.byref(u)))
-        assert (a.value, s.value) == (1, 1)
-        return int(u.value)
+        p = plans.ok(plans.controlled_gradient_plan([sum(1 << q for q in controls)] * G, [STRING_X] * G, [0], n, args.precision))
+        assert (p["adjoint_sweeps"], p["sum_sweeps"]) == (1, 1)
+        return p["units_visited"]
 
     with Simulator(n, precision=args.precision) as sim:
         sim.run(Circuit.from_gates(n, [("h", q) for q in range(n)] + [("rz", 0.1 + 0.05 * q, q) for q in range(n)]))
@@ -70,9 +65,9 @@ def child(args):
 
         def row(name, controls):
             rots = [(0.3 + 0.01 * k, TEXT, controls) for k in range(G)]
-            before = lib.qsim_pauli_adjoint_sweeps_launched()
+            before = plans.sweeps_launched("pauli_adjoint")
             sim.energy_and_gradient(rots, ham)
-            assert lib.qsim_pauli_adjoint_sweeps_launched() - before == 1
+            assert plans.sweeps_launched("pauli_adjoint") - before == 1
 
             def forward():
                 sim.apply_pauli_rotations(rots)

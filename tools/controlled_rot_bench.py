@@ -4,7 +4,7 @@ the same x on the same state, in the same process, and prints ONE JSON line.
   python tools/controlled_rot_bench.py [--n 30] [--reps 7]
 
 The state is a layer of H and rz gates at n qubits (a sweep's time does not depend on the amplitudes).  Every row is timed with HIP
-events on the state's stream, warm, median of --reps (>= 5): ms, the units the plan reports (qsim_controlled_rotation_plan) and
+events on the state's stream, warm, median of --reps (>= 5): ms, the units the plan reports (plans.controlled_rotation_plan) and
 `share` = ms / ms of the uncontrolled sweep — the traffic model of DESIGN "Controlled Pauli rotations" says 2^-c for c controls.
 Rows, per precision (64, 32), all with the one string "X3 Z5 X9" (x = qubits 3 and 9, a paired sweep):
   uncontrolled           the yardstick: the sweep without controls (k_pauli_rot)
@@ -27,24 +27,20 @@ TEXT = "X3 Z5 X9"
 
 
 def child(args):
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib
+    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, plans
     n = args.n
     assert n >= 16
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
     ev = [ctypes.c_void_p(), ctypes.c_void_p()]
     for e in ev:
         assert hip.hipEventCreate(ctypes.byref(e)) == 0
     rows = {}
-    up = ctypes.POINTER(ctypes.c_uint64)
 
     def units(controls):
-        c, x, z = ((ctypes.c_uint64 * 1)(v) for v in (sum(1 << q for q in controls), STRING_X, STRING_Z))
-        s, g, u = ctypes.c_long(), ctypes.c_long(), ctypes.c_uint64()
-        _lib.check(lib.qsim_controlled_rotation_plan(ctypes.cast(c, up), ctypes.cast(x, up), ctypes.cast(z, up), 1, n, args.precision,
-                                                     ctypes.byref(s), ctypes.byref(g), ctypes.byref(u)))
-        assert (s.value, g.value) == (1, 0)
-        return int(u.value)
+        p = plans.ok(plans.controlled_rotation_plan([sum(1 << q for q in controls)], [STRING_X], [STRING_Z], n, args.precision))
+        assert (p["sweeps"], p["queued_as_gates"]) == (1, 0)
+        return p["units_visited"]
 
     with Simulator(n, precision=args.precision) as sim:
         sim.run(Circuit.from_gates(n, [("h", q) for q in range(n)] + [("rz", 0.1 + 0.05 * q, q) for q in range(n)]))
@@ -52,9 +48,9 @@ def child(args):
         stream = ctypes.c_void_p(sim.stream)
 
         def timed(name, fn, sweeps, extra):
-            before = lib.qsim_pauli_rotation_sweeps_launched()
+            before = plans.sweeps_launched("pauli_rotation")
             fn()  # warm
-            assert lib.qsim_pauli_rotation_sweeps_launched() - before == sweeps
+            assert plans.sweeps_launched("pauli_rotation") - before == sweeps
             ms = []
             for _ in range(max(5, args.reps)):
                 assert hip.hipEventRecord(ev[0], stream) == 0

@@ -39,9 +39,9 @@ def pair_terms(n):
 
 
 def child(args):
-    from gpu_quantum_simulator_amd import Circuit, Diagonal, Simulator, _lib
+    from gpu_quantum_simulator_amd import Circuit, Diagonal, Simulator, _lib, plans
     n, gamma, beta = args.n, 0.37, 0.52
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     pairs = pair_terms(n)
     mixer = [(2.0 * beta, f"X{q}") for q in range(n)]
     result = {}
@@ -67,9 +67,9 @@ def child(args):
             two = timed("diag_2", lambda: sim.energy_and_gradient([(gamma, cost)] * 2, cost))
             for p in LAYERS:
                 layers = ([(gamma, cost)] + mixer) * p
-                before = (lib.qsim_diagonal_adjoint_sweeps_launched(), lib.qsim_pauli_adjoint_sweeps_launched())
+                before = (plans.sweeps_launched("diagonal_adjoint"), plans.sweeps_launched("pauli_adjoint"))
                 energy, grad = sim.energy_and_gradient(layers, cost)
-                taken = (lib.qsim_diagonal_adjoint_sweeps_launched() - before[0], lib.qsim_pauli_adjoint_sweeps_launched() - before[1])
+                taken = (plans.sweeps_launched("diagonal_adjoint") - before[0], plans.sweeps_launched("pauli_adjoint") - before[1])
                 row = timed(f"qaoa_p{p}", lambda: sim.energy_and_gradient(layers, cost))
                 row.update(parameters=len(layers), diag_adjoint_sweeps=taken[0], pauli_adjoint_sweeps=taken[1], energy=energy, dE_dgamma_0=float(grad[0]))
             spelled = [(2.0 * gamma * c, text) for c, text in pairs] + mixer

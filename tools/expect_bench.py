@@ -53,10 +53,10 @@ def host_ising(psi, n):
 
 def child(args):
     import numpy as np
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits
+    from gpu_quantum_simulator_amd import Circuit, Simulator, circuits, _lib, plans
     n, K = args.n, args.k
-    lib = _lib.load()
-    assert lib.qsim_pauli_terms_per_sweep() == K
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
+    assert plans.pauli_terms_per_sweep() == K
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
     ev = [ctypes.c_void_p(), ctypes.c_void_p()]
     for e in ev:
@@ -98,10 +98,8 @@ def child(args):
             timed("pair_5bit", lambda: sim.expectation_terms([f"X1 Y4 X9 Y{n // 2} X{n - 2}"]))
             for name, terms in (("ising", ising_terms(n)), ("heisenberg", heisenberg_terms(n))):
                 from gpu_quantum_simulator_amd import pauli_masks
-                xs = np.array([pauli_masks(t, n)[0] for t in terms], dtype=np.uint64)
-                sweeps = ctypes.c_long()
-                _lib.check(lib.qsim_pauli_sweeps(xs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), xs.size, ctypes.byref(sweeps)))
-                timed(name, lambda terms=terms: sim.expectation_terms(terms), sweeps.value)
+                sweeps = plans.ok(plans.pauli_sweeps([pauli_masks(t, n)[0] for t in terms]))["sweeps"]
+                timed(name, lambda terms=terms: sim.expectation_terms(terms), sweeps)
                 rows[name]["terms"] = len(terms)
         for G in CANDIDATES:
             timed(f"group_{G}_k{K}", lambda: sim.expectation_terms([text(x_pair, z) for z in zs[:G]]), -(-G // K))
@@ -130,7 +128,7 @@ def main():
         return child(args)
     # the parent never opens the GPU: it reads the library's default K through a child too
     env = {k: v for k, v in os.environ.items() if k != "QSIM_PAULI_TERMS_PER_SWEEP"}
-    probe = "import sys; sys.path.insert(0, %r); from gpu_quantum_simulator_amd import _lib; print(_lib.load().qsim_pauli_terms_per_sweep())" % ROOT
+    probe = "import sys; sys.path.insert(0, %r); from gpu_quantum_simulator_amd import plans; print(plans.pauli_terms_per_sweep())" % ROOT
     default_k = int(subprocess.run([sys.executable, "-c", probe], env=env, check=True, capture_output=True, text=True).stdout.split()[-1])
     result = {"n": args.n, "reps": max(5, args.reps), "terms_per_sweep": default_k, "fp64": {}, "fp32": {}}
     for precision in (64, 32):

@@ -33,9 +33,9 @@ GROUPS = (1, 8, 32)
 
 def child(args):
     import numpy as np
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib
+    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, plans
     n = args.n
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     reps = max(5, args.reps)
     rows = {}
     prep = Circuit.from_gates(n, [("h", q) for q in range(n)] + [("rz", 0.1 + 0.05 * q, q) for q in range(n)])
@@ -66,9 +66,9 @@ def child(args):
         for G in GROUPS:
             rots = [(0.3 + 0.01 * k, text(x, zs[k])) for k in range(G)]
             strings = [p for _, p in rots]
-            before = lib.qsim_pauli_adjoint_sweeps_launched()
+            before = plans.sweeps_launched("pauli_adjoint")
             sim.energy_and_gradient(rots, ham)
-            assert lib.qsim_pauli_adjoint_sweeps_launched() - before == 1
+            assert plans.sweeps_launched("pauli_adjoint") - before == 1
 
             def forward():
                 sim.apply_pauli_rotations(rots)
@@ -91,9 +91,9 @@ def child(args):
         layers = 2
         ising = [(-1.0, f"Z{q} Z{q + 1}") for q in range(n - 1)] + [(-0.5, f"X{q}") for q in range(n)]
         ansatz = [(0.1 + 0.01 * k, p) for k, (_, p) in enumerate(ising * layers)]
-        before = lib.qsim_pauli_adjoint_sweeps_launched()
+        before = plans.sweeps_launched("pauli_adjoint")
         timed("ising_2_layers", lambda: sim.energy_and_gradient(ansatz, ising), {"parameters": len(ansatz), "hamiltonian_terms": len(ising)})
-        rows["ising_2_layers"]["adjoint_sweeps_per_call"] = (lib.qsim_pauli_adjoint_sweeps_launched() - before) // (reps + 1)
+        rows["ising_2_layers"]["adjoint_sweeps_per_call"] = (plans.sweeps_launched("pauli_adjoint") - before) // (reps + 1)
     print("ROWS " + json.dumps(rows), flush=True)
 
 

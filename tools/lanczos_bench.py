@@ -17,11 +17,10 @@ row reads and writes, `gbps` = volumes * state bytes / ms.
   step_ising, step_zz                        one Lanczos step for the transverse-field Ising chain (2n - 1 terms, G = n + 1 sweeps) and for
                                              H = sum Z_q Z_(q+1) alone (G = 1): (call of 4 steps - call of 2 steps) / 2, vector=False, tol = 0 —
                                              steps 2 and 3, which have all three vectors; allocation and the start norm cancel.  `volumes`
-                                             is qsim_lanczos_plan's; model_ms_sum / model_ms_norm2 = those volumes at the rate of
+                                             is plans.lanczos_plan's; model_ms_sum / model_ms_norm2 = those volumes at the rate of
                                              sum_accumulate / norm2, ratio_* = ms / model
 The measurement runs in a child process under its own `timeout -k 10`; a failure ends the run."""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -34,9 +33,9 @@ sys.path.insert(0, ROOT)
 
 
 def child(args):
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib
+    from gpu_quantum_simulator_amd import Circuit, Simulator, pauli_masks, _lib, plans
     n = args.n
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     reps = max(5, args.reps)
     state_bytes = float(16 << n)
     rows = {}
@@ -86,15 +85,13 @@ def child(args):
             long = timed(name + "_4_steps", lambda: dst.ground_state(terms, 0.0, max_steps=4, vector=False), 0)
             for k in (name + "_2_steps", name + "_4_steps"):
                 del rows[k]["volumes"], rows[k]["gbps"]
-            from gpu_quantum_simulator_amd.simulator import _hamiltonian_arrays
-            xs, _, _, xp, _, _ = _hamiltonian_arrays(terms, n)
-            sums, others, volumes = ctypes.c_long(), ctypes.c_long(), ctypes.c_double()
-            _lib.check(lib.qsim_lanczos_plan(xp, xs.size, 4, 0, ctypes.byref(sums), ctypes.byref(others), ctypes.byref(volumes)))
+            plan = plans.ok(plans.lanczos_plan([pauli_masks(text, n)[0] for _, text in terms], 4, 0))
+            sums, others, volumes = plan["sum_sweeps_per_step"], plan["other_sweeps_per_step"], plan["volumes_per_step"]
             step = 0.5 * (long - short)
-            model_sum = volumes.value * state_bytes / (rows["sum_accumulate"]["gbps"] * 1e6)
-            model_norm = volumes.value * state_bytes / (rows["norm2"]["gbps"] * 1e6)
-            rows[name] = {"ms": round(step, 4), "how": "(4 steps - 2 steps) / 2", "terms": len(terms), "sum_sweeps": sums.value, "other_sweeps": others.value,
-                          "volumes": volumes.value, "gbps": round(volumes.value * state_bytes / step / 1e6, 1), "model_ms_sum": round(model_sum, 4),
+            model_sum = volumes * state_bytes / (rows["sum_accumulate"]["gbps"] * 1e6)
+            model_norm = volumes * state_bytes / (rows["norm2"]["gbps"] * 1e6)
+            rows[name] = {"ms": round(step, 4), "how": "(4 steps - 2 steps) / 2", "terms": len(terms), "sum_sweeps": sums, "other_sweeps": others,
+                          "volumes": volumes, "gbps": round(volumes * state_bytes / step / 1e6, 1), "model_ms_sum": round(model_sum, 4),
                           "model_ms_norm2": round(model_norm, 4), "ratio_sum": round(step / model_sum, 4), "ratio_norm2": round(step / model_norm, 4)}
     for name in ("combine_three", "combine_two", "combine_d0_two", "combine_d0_one", "inner"):
         rows[name]["rate_vs_sum_accumulate"] = round(rows[name]["gbps"] / rows["sum_accumulate"]["gbps"], 4)

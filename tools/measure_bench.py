@@ -41,10 +41,10 @@ def cases(n):
 
 def child(args):
     import numpy as np
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits
+    from gpu_quantum_simulator_amd import Circuit, Simulator, circuits, _lib, plans
     import torch
     n = args.n
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
     ev = [ctypes.c_void_p(), ctypes.c_void_p()]
     for e in ev:
@@ -98,15 +98,13 @@ def child(args):
 
         for name, qs in cases(n).items():
             k = len(qs)
-            arr = (ctypes.c_int * k)(*qs)
-            wu, cu, wt, ct = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_long(), ctypes.c_long()
-            assert lib.qsim_collapse_plan(arr, k, 0, n, args.precision, ctypes.byref(wu), ctypes.byref(cu), ctypes.byref(wt), ctypes.byref(ct)) == 0
-            r = wu.value / cu.value
+            p = plans.ok(plans.collapse_plan(qs, 0, n, args.precision))
+            r = p["weight_units"] / p["collapse_units"]
             outcome = sim.measure(qs, draw=0.5)  # an outcome that has a probability; the state is collapsed onto it from here on
-            before = lib.qsim_collapse_sweeps_launched()
+            before = plans.sweeps_launched("collapse")
             modelled(timed(f"postselect_{name}", lambda: sim.postselect(qs, outcome)), 2, r, 1, qs)
             modelled(timed(f"measure_{name}", lambda: sim.measure(qs, draw=0.5)), 2, r, 2, qs)
-            assert lib.qsim_collapse_sweeps_launched() - before == 4 * (reps + 1)
+            assert plans.sweeps_launched("collapse") - before == 4 * (reps + 1)
             if k == 1:
                 proj = np.zeros((2, 2))
                 proj[outcome, outcome] = 1.0

@@ -58,8 +58,8 @@ def gradient_cases(K):
 def cases():
     """(name, bytes) of every case, in a fixed order."""
     import torch
-    from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, _lib, circuits
-    K = _lib.load().qsim_pauli_rotations_per_sweep()
+    from gpu_quantum_simulator_amd import Circuit, Cluster, Simulator, circuits, plans
+    K = plans.pauli_rotations_per_sweep()
     for n in NS:
         for precision in (64, 32):
             with Simulator(n, precision=precision) as sim:

@@ -66,9 +66,9 @@ def check_ladder():
 
 def child(args):
     import numpy as np
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, gate_matrix
+    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, gate_matrix, plans
     n = args.n
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
     ev = [ctypes.c_void_p(), ctypes.c_void_p()]
     for e in ev:
@@ -102,9 +102,9 @@ def child(args):
 
         def sweep(x, G):
             rots = [(0.3 + 0.01 * k, text(x, zs[k])) for k in range(G)]
-            before = lib.qsim_pauli_rotation_sweeps_launched()
+            before = plans.sweeps_launched("pauli_rotation")
             sim.apply_pauli_rotations(rots)
-            assert lib.qsim_pauli_rotation_sweeps_launched() - before == 1
+            assert plans.sweeps_launched("pauli_rotation") - before == 1
             return lambda: sim.apply_pauli_rotations(rots)
 
         # the yardstick: one launch per gate at fusion level 0, target bit >= 6

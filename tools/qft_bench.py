@@ -53,10 +53,10 @@ def registers(n):
 
 def child(args):
     import numpy as np
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits
+    from gpu_quantum_simulator_amd import Circuit, Simulator, circuits, _lib, plans
     import torch
     n = args.n
-    lib = _lib.load()
+    _lib.load()  # libqsim (and torch's HIP runtime, where there is one) before anything else opens the device
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
     ev = [ctypes.c_void_p(), ctypes.c_void_p()]
     for e in ev:
@@ -84,10 +84,10 @@ def child(args):
             return rows[name]
 
         def qft_row(name, qs, cap, rot, circ):
-            before = lib.qsim_qft_sweeps_launched()
+            before = plans.sweeps_launched("qft")
             row = timed(name, lambda: sim.apply_qft(qs, max_digit_bits=cap))
             row["qubits"], row["cap"] = qs, cap
-            row["passes"] = int(lib.qsim_qft_sweeps_launched() - before) // (max(5, args.reps) + 1)
+            row["passes"] = int(plans.sweeps_launched("qft") - before) // (max(5, args.reps) + 1)
             row["x_rot"] = round(row["ms"] / (row["passes"] * rot["ms"]), 3)
             row["x_circuit"] = round(row["ms"] / circ["ms"], 3)
             return row

@@ -22,7 +22,7 @@ import os
 import statistics
 import subprocess
 import sys
-from ctypes import byref, c_double, c_int, c_long, c_uint64
+from ctypes import byref, c_double, c_int, c_long
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -34,7 +34,7 @@ def subsets(n, k):
 
 
 def child(args):
-    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits
+    from gpu_quantum_simulator_amd import Circuit, Simulator, _lib, circuits, plans
     n = args.n
     lib = _lib.load()
     hip = ctypes.CDLL("libamdhip64.so.7")  # the runtime libqsim.so itself is linked against
@@ -46,11 +46,7 @@ def child(args):
     rows = {}
 
     def plan(qs):
-        arr = (c_int * len(qs))(*qs)
-        path, brows, upper, slices, units, scratch, trips = c_int(), c_int(), c_long(), c_long(), c_uint64(), c_uint64(), c_long()
-        assert lib.qsim_subsystem_density_plan(arr, len(qs), n, args.precision, byref(path), byref(brows), byref(upper), byref(slices), byref(units),
-                                               byref(scratch), byref(trips)) == 0
-        return dict(path=path.value, upper_blocks=upper.value, slices=slices.value, units_read=units.value, scratch_bytes=scratch.value, trips=trips.value)
+        return plans.ok(plans.subsystem_density_plan(qs, n, args.precision))
 
     c = Circuit.from_gates(n, circuits.random_gates(n, 1000, 20240117 + n, "all"))
     with Simulator(n, precision=args.precision) as sim:
@@ -78,8 +74,8 @@ def child(args):
             p = plan(list(range(k)))
             blocks = 1 << (k - 6)
             # per chunk of 32 environments a wave issues 8 steps of 16 products off the diagonal, of 9 in a diagonal block
-            launches = [(p["trips"] * 8 * 16, (p["upper_blocks"] - blocks) * p["slices"], SWEEP_LDS_BYTES),
-                        (p["trips"] * 8 * 9, blocks * p["slices"], SWEEP_LDS_BYTES // 2)]
+            launches = [(p["trips_per_workgroup"] * 8 * 16, (p["upper_blocks"] - blocks) * p["slices"], SWEEP_LDS_BYTES),
+                        (p["trips_per_workgroup"] * 8 * 9, blocks * p["slices"], SWEEP_LDS_BYTES // 2)]
             ms = []
             for _ in range(3):
                 total = 0.0
